@@ -6,9 +6,13 @@
 
 One "step" = augmentation + forward + backward + AdamW update of ACT_PointDistillation on a synthetic batch of
 B=128 clouds x 1024 points per GPU (64 groups x 32 neighbours, 12-layer d=384 student, frozen ViT-B teacher),
-fp32, random weights, inputs resident in HBM.  Rank 0 prints ONE JSON line: whole-job clouds/s, plus
+fp32, random weights, inputs resident in HBM.  Rank 0 prints ONE JSON line: whole-job clouds/s and ms_per_step.
+A plain run sets up, warms up, times the K steps and prints that line; with --full it also reports
   roofline      live hipEvent timing of the dominant HIP kernel (instrumented pass after the timed region)
   cpu_baseline  the CPU oracle (pure-PyTorch restatement of the reference path) timed on the host cores (N=1 only)
+  and the idle-GPU host cost per step, the all-reduce probe (N>1), 50-step windows (K>=100), the FPS / kNN figures and other_workloads.
+--dump-outputs DIR writes what the last timed step computed (loss terms / logits, a seeded sample of the updated trainable
+parameters) as DIR/<name>.npy: the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import math
@@ -288,6 +292,26 @@ def allreduce_probe(device, numel, world, backend, reps=10, warm=3):
                               "(in the training step the 25 MB DDP buckets overlap the backward); world 1 moves no data"}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20          # trainable-parameter elements written by --dump-outputs (4 MB of float32)
+
+
+def dump_outputs(dirname, last, model=None, seed=0):
+    """--dump-outputs: the tensors the last timed step handed to its caller (loss terms, accuracy or logits) and, for the training
+    stages, a fixed seeded sample of the trainable parameters it updated, as DIR/<name>.npy in float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach() for k, v in last.items()}
+    if model is not None:
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters() if p.requires_grad])
+        if flat.numel() > DUMP_PARAM_SAMPLE:
+            idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), DUMP_PARAM_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["params_sample"] = flat
+    for k, v in arrays.items():
+        v = v.cpu()
+        np.save(os.path.join(dirname, k + ".npy"), v.numpy() if v.dtype == torch.float64 else v.float().numpy())
+
+
 _NEXT = None
 
 
@@ -304,6 +328,11 @@ def main():
     ap.add_argument("--config", default="c2", choices=("c2", "c5"),
                     help="c2: BASELINE configs[1] geometry (default, the driver's line); c5: BASELINE configs[4] stress geometry "
                          "(N=8192 pts, 512 groups x 64 nbrs, 24-layer d=768 student, B=32/GPU) -- stage 2 only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: instrumented per-kernel / roofline pass, FPS + kNN figures, idle-GPU host "
+                         "cost, all-reduce probe, 50-step windows, other_workloads and the CPU baseline (the --no-* switches below thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last one as DIR/<name>.npy (float32 / float64, a few MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-instrument", action="store_true")
     ap.add_argument("--preflight", action="store_true",
@@ -311,8 +340,10 @@ def main():
                          "gradient payload, ONE warm-up + TWO timed DDP steps, per-rank core pinning; one JSON line with preflight.world_size_seen_by_rccl. "
                          "At --gpus 1 a world-1 RCCL group is initialised so the same code path runs")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short configs[2] (Stage I) and configs[4] (C5 stress) timings that the default single-GPU run appends as other_workloads")
+                    help="skip the short configs[2] (Stage I) and configs[4] (C5 stress) timings that the --full single-GPU run appends as other_workloads")
     args = ap.parse_args()
+    if not args.full:                                   # a plain run does only what the headline needs
+        args.no_instrument = args.no_cpu_baseline = args.no_other_workloads = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: launch the ranks ourselves (a SCALE run must not depend on the caller's launcher)
@@ -404,12 +435,15 @@ def main():
         if args.stage == 4:
             model.eval()
 
+    last = {}                                          # what the caller of the step received (--dump-outputs)
+
     def step(i):
         global _NEXT
         if args.stage == 3:                                # look-ahead: the next raw batch is prepared (FPS pool etc.) during this backward
             cur = _NEXT if _NEXT is not None else pool[i % len(pool)].clone()
             _NEXT = pool[(i + 1) % len(pool)].clone()
-            return train_step_ft(wrapped, optimizer, cur, labels, config, next_points=_NEXT)[0]
+            last["loss"], last["acc"] = train_step_ft(wrapped, optimizer, cur, labels, config, next_points=_NEXT)
+            return last["loss"]
         if args.stage == 4:                                # as runner_finetune.validate: next batch's FPS on the auxiliary stream
             from act_amd.tools.runner_finetune import fps_ahead
             with torch.no_grad():
@@ -418,15 +452,18 @@ def main():
                 main = torch.cuda.current_stream(device)
                 main.wait_event(cur[1])
                 cur[0].record_stream(main)
-                return model(cur[0]).sum()
+                last["logits"] = model(cur[0])
+                return last["logits"].sum()
         if args.stage == 1:
             l1, l2, _ = train_step_ae(wrapped, optimizer, pool[i % len(pool)], config, 20000 + i)
+            last["loss_1"], last["loss_2"] = l1, l2
             return l1 + l2
         # software pipelining across steps: the NEXT batch is handed over too, so its (frozen) teacher forward runs on the
         # auxiliary stream during this batch's backward; every step still executes exactly one teacher forward
         cur = _NEXT if _NEXT is not None else pool[i % len(pool)].clone()
         _NEXT = pool[(i + 1) % len(pool)].clone()
-        return train_step(wrapped, optimizer, cur, config, next_points=_NEXT)
+        last["loss"] = train_step(wrapped, optimizer, cur, config, next_points=_NEXT)
+        return last["loss"]
 
     def barrier():
         if world > 1:
@@ -442,7 +479,7 @@ def main():
         step(i)
     barrier()
     WIN = 50                                             # sustained-clock evidence: GPU time per window of 50 steps (hipEvents)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps // WIN + 1)] if args.steps >= 2 * WIN else []
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps // WIN + 1)] if args.full and args.steps >= 2 * WIN else []
     t0 = time.perf_counter()
     for i in range(args.steps):
         if marks and i % WIN == 0:
@@ -454,17 +491,20 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     windows = [marks[j].elapsed_time(marks[j + 1]) / WIN for j in range(len(marks) - 1)] if marks and args.steps % WIN == 0 else []
-    # host cost of ONE step against an idle GPU: nothing to wait for, so this is the pure Python + launch time
-    idle = []
-    for i in range(3):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model if args.stage <= 3 else None)
+    host_idle_ms = host_by_rank = None
+    if args.full or args.preflight:
+        # host cost of ONE step against an idle GPU: nothing to wait for, so this is the pure Python + launch time
+        idle = []
+        for i in range(3):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step(i)
+            idle.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step(i)
-        idle.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
-    host_idle_ms = 1e3 * min(idle)
-    host_by_rank = None
-    if world > 1:
+        host_idle_ms = 1e3 * min(idle)
+    if world > 1 and host_idle_ms is not None:
         hb = [torch.zeros(2, device=device, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(hb, torch.tensor([host_idle_ms, 1e3 * host_issue / args.steps], device=device, dtype=torch.float64))
         host_by_rank = [[round(v, 3) for v in t.tolist()] for t in hb]
@@ -481,7 +521,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     comm = None
-    if world > 1 or force_ddp:
+    if (world > 1 or force_ddp) and (args.full or args.preflight):
         n_train = sum(p.numel() for p in model.parameters() if p.requires_grad)
         comm = allreduce_probe(device, n_train, world, dist.get_backend())
         comm["launched_by"] = "bench.py itself (torch.distributed.run child)" if os.environ.get("ACT_BENCH_SELF_LAUNCHED") == "1" else "external launcher"
@@ -489,7 +529,7 @@ def main():
             comm["gpus_flag"] = gpus_flag
     loss_val = float(loss.item())
     if not math.isfinite(loss_val):                      # a diverged / NaN step would still be timed happily: refuse to report it
-        raise RuntimeError(f"bench: non-finite loss {loss_val} after {args.warmup + args.steps + 3} steps")
+        raise RuntimeError(f"bench: non-finite loss {loss_val} after {args.warmup + args.steps + (3 if host_idle_ms is not None else 0)} steps")
 
     import act_amd.composite as _CP
     x3_on = bool(_CP.TEACHER_BF16X3) and args.stage in (1, 2)          # (Stage I: the products of the same frozen ViT inside the prompt-tuning graph)
@@ -514,9 +554,10 @@ def main():
                                 "B=%d clouds/GPU x 1024 pts, tokenizer + prompt-tuned frozen ViT-B + FoldingNet, "
                                 "Chamfer-L1 + KL losses, fwd+bwd+AdamW" % B),
                    "clouds_per_gpu": B, "points_per_cloud": N, "parallelism": f"dp{world}", "final_loss": loss_val,
-                   "host_enqueue_ms_per_step": host_idle_ms,
-                   "host_enqueue_note": "wall time to enqueue one whole step against an idle GPU (min of 3): pure host cost; "
-                                        "host_loop_ms_per_step is the enqueue loop of the timed region, which includes waiting on a full GPU queue",
+                   **({"host_enqueue_ms_per_step": host_idle_ms,
+                       "host_enqueue_note": "wall time to enqueue one whole step against an idle GPU (min of 3): pure host cost; "
+                                            "host_loop_ms_per_step is the enqueue loop of the timed region, which includes waiting on a full GPU queue"}
+                      if host_idle_ms is not None else {}),
                    "host_loop_ms_per_step": 1e3 * host_issue / args.steps,
                    **({"host_ms_per_step_by_rank": host_by_rank,
                        "host_by_rank_note": "[idle-GPU enqueue ms, timed-loop enqueue ms] of every rank (all ranks share this host's cores)"}

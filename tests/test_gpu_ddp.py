@@ -222,7 +222,7 @@ def test_bench_two_ranks_on_one_gpu_prints_one_line(tmp_path, launcher):
     env = dict(os.environ, ACT_BENCH_SHARE_GPU="1", ACT_BENCH_BACKEND="gloo", ACT_GEMM_AUTOTUNE="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--no-cpu-baseline"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29547"] + tail
     else:
@@ -281,6 +281,38 @@ def test_bench_preflight_self_launched(tmp_path, gpus):
     assert "roofline" not in d and "cpu_baseline" not in d and "other_workloads" not in d
     print(f"[preflight] gpus={gpus}: wall {wall:.1f} s (in-process {pf['wall_s']} s), process group init {pf['process_group_init_s']} s, "
           f"all-reduce {pf['allreduce_ms']:.2f} ms, affinity {aff}")
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """a plain ``python bench.py --steps K --warmup W --dump-outputs DIR``: exactly K timed steps, the headline fields only (the instrumented
+    pass, CPU baseline and other workloads are --full), and the last timed step's outputs as DIR/<name>.npy -- the same bits in two processes."""
+    import json
+    import subprocess
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["ACT_GEMM_AUTOTUNE"] = "0"
+    dumps = []
+    for run in range(2):
+        out = os.path.join(tmp_path, "run%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", out], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "clouds/s" and d["higher_is_better"] and d["dtype"] == "f32"
+        assert d["metric"] == "stage2_pretrain_point_clouds_per_sec" and abs(d["value"] - 8 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+        assert not {"roofline", "kernels", "group_fps_knn", "other_workloads", "cpu_baseline", "comm"} & set(d)
+        files = sorted(os.listdir(out))
+        assert files == ["loss.npy", "params_sample.npy"], files
+        arrays = {f: np.load(os.path.join(out, f)) for f in files}
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert float(arrays["loss.npy"]) == d["config"]["final_loss"] and arrays["params_sample.npy"].shape == (1 << 20,)
+        assert np.isfinite(arrays["params_sample.npy"]).all()
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_bench_tolerates_a_gpus_flag_that_disagrees_with_the_launcher(tmp_path):

@@ -90,6 +90,17 @@ def test_point_transformer_golden(dev, ttype):
         assert _rel(model(pts), g[f"{ttype}_logits_eval"]) <= TOL
 
 
+class _Float32Grouping(torch.nn.Module):
+    """the oracle's Group on the float32 cloud (FPS / kNN choices exactly as the HIP path makes them), coordinates handed on in the caller's dtype"""
+
+    def __init__(self, group):
+        super().__init__()
+        self.group = group
+
+    def forward(self, xyz):
+        return tuple(t.to(xyz.dtype) for t in self.group(xyz.float()))
+
+
 def test_point_transformer_vs_oracle_with_dropout_and_droppath(dev):
     """B=8, N=256, drop_path 0.2, head dropout 0.5: all draws recorded on the oracle and replayed on the HIP path."""
     from act_amd.models import build_model_from_cfg
@@ -113,11 +124,21 @@ def test_point_transformer_vs_oracle_with_dropout_and_droppath(dev):
     loss.backward()
     assert _rel(logits, ref_logits) <= TOL
     assert abs(loss.item() - ref_loss.item()) <= TOL and float(acc) == float(ref_acc)
-    rp = dict(ref.named_parameters())
+    # gradients against the same oracle in float64, all draws replayed: the conv biases in front of BatchNorm have exactly-zero
+    # gradients, and the fp32 oracle's own rounding noise in them (~2e-5 Frobenius, and a different value for every CPU thread count)
+    # is as large as the absolute slack below -- the float64 oracle holds none, so the bound measures the HIP path alone
+    ref64 = fill_module(OM.PointTransformer(OM.edict(cfg)), "ft.").double().train()
+    ref64.group_divider = _Float32Grouping(ref64.group_divider)
+    od64 = ODraws(od.table, record=True)
+    ref64_logits = ref64(pts.double(), od64)
+    ref64.get_loss_acc(ref64_logits, label)[0].backward()
+    assert set(od64.table) == set(od.table)                            # nothing drawn afresh: the same dropout / DropPath masks
+    assert _rel(ref64_logits, ref_logits) <= TOL
+    rp = dict(ref64.named_parameters())
     for n, p in model.named_parameters():
         # Frobenius-relative: the graph has discrete switch points (max-pool arg-max, ReLU kink); an element within rounding
         # distance of one moves a handful of gradient entries by ~1e-3 between summation orders, never the bulk
-        # (+2e-5 absolute: conv biases in front of BatchNorm have exactly-zero gradients, both sides hold rounding noise)
+        # (+2e-5 absolute: conv biases in front of BatchNorm have exactly-zero gradients, the HIP side holds rounding noise)
         d = (p.grad.double().cpu() - rp[n].grad.double()).norm().item()
         assert d <= 5e-4 * rp[n].grad.double().norm().item() + 2e-5, (n, d)
 
