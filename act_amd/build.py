@@ -20,7 +20,8 @@ ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result", "-Wno-unused-value", "-DNDEBUG"]
 # bit-exact index kernels: never contract a*b+c
-PER_FILE = {"point_ops.hip": ["-ffp-contract=off"], "chamfer.hip": ["-ffp-contract=off"]}
+PER_FILE = {"point_ops.hip": ["-ffp-contract=off"], "chamfer.hip": ["-ffp-contract=off"],
+            "seg.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

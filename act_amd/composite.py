@@ -441,15 +441,24 @@ def _stock_blocks(blocks):
     return True
 
 
-def block_stack(blocks, x, pos, gates, draws=None, tag="enc", chunk=None):
+def block_stack(blocks, x, pos, gates, draws=None, tag="enc", chunk=None, taps=False):
     """the loop ``for blk in blocks: x = blk(x + pos)`` -- one BlockStackFn per chunk of blocks when the composite path is on, else one
     Block.forward per block (ACT_COMPOSITE=0 / ACT_BLOCK_STACK=0).  ``chunk``: blocks per host call (None: the ACT_BLOCK_STACK_CHUNK default,
-    0: the whole stack); the owning TransformerEncoder / Decoder passes its ``stack_chunk`` (set by runner_pretrain.wrap_ddp under multi-rank DDP)."""
+    0: the whole stack); the owning TransformerEncoder / Decoder passes its ``stack_chunk`` (set by runner_pretrain.wrap_ddp under multi-rank DDP).
+    ``taps=True``: return the list of every chunk's output -- the outputs of blocks chunk-1, 2*chunk-1, ..., n-1 (the semantic-segmentation
+    model keeps blocks 3, 7, 11 with chunk=4) -- instead of the last one."""
     n = len(blocks)
-    if not (ENABLED and STACK) or n == 0 or not _stock_blocks(blocks):
+
+    def per_block(x, draws):
+        outs = []
+        every = chunk if chunk else n
         for i, blk in enumerate(blocks):
             x = blk(x, pos, draws, f"{tag}.{i}", gates[i] if gates is not None else None)
-        return x
+            if (i + 1) % every == 0 or i == n - 1:
+                outs.append(x)
+        return outs if taps else x
+    if not (ENABLED and STACK) or n == 0 or not _stock_blocks(blocks):
+        return per_block(x, draws)
     if draws is not None:                                    # injected DropPath draws (parity tests): the gates every Block.forward would compute
         gates = [blk.gates(x.shape[0], x.device, draws, f"{tag}.{i}") for i, blk in enumerate(blocks)]
         gates = [tuple(g) if g[0] is not None else None for g in gates]
@@ -457,13 +466,12 @@ def block_stack(blocks, x, pos, gates, draws=None, tag="enc", chunk=None):
     b0 = blocks[0]
     heads, eps, tw = b0.attn.num_heads, b0.norm1.eps, (2 if b0.overlap_wgrad else 1)
     if any(l[6].attn.num_heads != heads or l[0].eps != eps or l[3].eps != eps or bool(l[6].overlap_wgrad) != bool(b0.overlap_wgrad) for l in leaves[1:]):
-        for i, blk in enumerate(blocks):                     # blocks that differ in more than their weights: one call each
-            x = blk(x, pos, None, f"{tag}.{i}", gates[i] if gates is not None else None)
-        return x
+        return per_block(x, None)                            # blocks that differ in more than their weights: one call each
     if chunk is None:
         chunk = STACK_CHUNK
     chunk = chunk if chunk > 0 else n
     carry = pos is not None and chunk < n and torch.is_grad_enabled() and pos.requires_grad
+    outs = []
     for c0 in range(0, n, chunk):
         params = []
         for n1, qkv, proj, n2, fc1, fc2, _ in leaves[c0:c0 + chunk]:
@@ -473,7 +481,8 @@ def block_stack(blocks, x, pos, gates, draws=None, tag="enc", chunk=None):
         emit = carry and c0 + chunk < n                      # every chunk but the deepest hands pos on (see BlockStackFn)
         r = BlockStackFn.apply(x, pos, gates[c0:c0 + chunk] if gates is not None else None, heads, eps, tw, emit, *params)
         x, pos = r if emit else (r, pos)
-    return x
+        outs.append(x)
+    return outs if taps else x
 
 
 # ---- prefix block (prompts = keys / values only) ---------------------------------------------------------------------------

@@ -1334,6 +1334,226 @@ def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, b
     return gemm(a, w2, True, True, bias=b2, res=x1)
 
 
+# ---- dense per-point prediction (csrc/seg.hip): three-NN feature propagation, log-softmax, weighted NLL, confusion matrix -------------------
+_C._declare({
+    "act_three_nn_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "act_interp_rows_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_rows_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_xyz_grad_workspace": [ctypes.c_longlong, _i],
+    "act_interp_xyz_grad_f32": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_log_softmax_fwd_f32": [_vp, ctypes.c_longlong, _i, _vp, _vp],
+    "act_log_softmax_bwd_f32": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
+    "act_nll_weighted_workspace": [ctypes.c_longlong],
+    "act_nll_weighted_fwd_f32": [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_nll_weighted_bwd_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
+    "act_confusion_i64": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
+})
+_C.lib.act_interp_xyz_grad_workspace.restype = _sz
+_C.lib.act_nll_weighted_workspace.restype = _sz
+for _n in ("act_three_nn_f32", "act_interp_rows_fwd_f32", "act_interp_rows_bwd_f32", "act_interp_xyz_grad_workspace", "act_interp_xyz_grad_f32",
+           "act_log_softmax_fwd_f32", "act_log_softmax_bwd_f32", "act_nll_weighted_workspace", "act_nll_weighted_fwd_f32", "act_nll_weighted_bwd_f32",
+           "act_confusion_i64"):
+    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
+
+
+def three_nn(xyz, centers, want_adj=True):
+    """xyz [B,N,3], centers [B,G,3] -> (idx int32 [B,N,3], weight [B,N,3], adj_off int32 [B,G+1] | None, adj_ent int32 [B,3N] | None):
+    the three nearest centres of every point in ascending (difference-form distance, index) order, their normalised inverse-distance
+    weights (semantic_segmentation/models/pointnet2_utils.py:293-299) and the inverse adjacency the interpolation backward gathers over."""
+    xyz, centers = _f32c(xyz), _f32c(centers)
+    B, N, _ = xyz.shape
+    G = centers.shape[1]
+    dev = xyz.device
+    idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
+    w = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    off = torch.empty(B, G + 1, dtype=torch.int32, device=dev) if want_adj else None
+    ent = torch.empty(B, 3 * N, dtype=torch.int32, device=dev) if want_adj else None
+    check(lib.act_three_nn_f32(ptr(xyz), ptr(centers), B, N, G, ptr(idx), ptr(w), ptr(off), ptr(ent), stream()), "act_three_nn_f32")
+    return idx, w, off, ent
+
+
+def interp_rows_fwd(P, idx, w, B, N, G, xyz=None, wxyz=None, bias=None):
+    """P [B*G,C] -> Y [B*N,C] = sum_k w * P[idx] (+ xyz . wxyz^T + bias)"""
+    P = _f32c(P)
+    C = P.shape[1]
+    Y = torch.empty(B * N, C, dtype=torch.float32, device=P.device)
+    check(lib.act_interp_rows_fwd_f32(ptr(P), ptr(idx), ptr(w), ptr(xyz), ptr(wxyz), ptr(bias), B, N, G, C, ptr(Y), stream()),
+          "act_interp_rows_fwd_f32")
+    return Y
+
+
+def interp_rows_bwd(dY, off, ent, w, B, N, G):
+    dY = _f32c(dY)
+    C = dY.shape[1]
+    dP = torch.empty(B * G, C, dtype=torch.float32, device=dY.device)
+    check(lib.act_interp_rows_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_bwd_f32")
+    return dP
+
+
+def interp_xyz_grad(dY, xyz, want_w=True, want_b=True):
+    """-> (dY^T xyz [C,3] | None, column sums of dY [C] | None)"""
+    dY = _f32c(dY)
+    R, C = dY.shape
+    dw = torch.empty(C, 3, dtype=torch.float32, device=dY.device) if want_w else None
+    db = torch.empty(C, dtype=torch.float32, device=dY.device) if want_b else None
+    ws = workspace(dY.device, lib.act_interp_xyz_grad_workspace(R, C))
+    check(lib.act_interp_xyz_grad_f32(ptr(dY), ptr(xyz), R, C, ptr(dw), ptr(db), ptr(ws), ws.numel() * 4, stream()), "act_interp_xyz_grad_f32")
+    return dw, db
+
+
+class InterpRowsFn(torch.autograd.Function):
+    """three-NN interpolation of per-centre rows to the points: x [B*G,C] -> [B*N,C] (pointnet2_utils.py:300); backward is a gather over the
+    inverse adjacency (deterministic, bit-identical run to run).  The neighbour indices / weights are constants: the reference's distances come
+    from the input cloud, a leaf."""
+
+    @staticmethod
+    def forward(ctx, x, nn3, B, N, G):
+        idx, w, off, ent = nn3
+        y = interp_rows_fwd(x, idx, w, B, N, G)
+        ctx.save_for_backward(w, off, ent)
+        ctx.dims = (B, N, G)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        w, off, ent = ctx.saved_tensors
+        return interp_rows_bwd(dy, off, ent, w, *ctx.dims), None, None, None, None
+
+
+def interp_rows(x, nn3, B, N, G):
+    return InterpRowsFn.apply(x, nn3, B, N, G)
+
+
+class InterpConvFn(torch.autograd.Function):
+    """the first conv of PointNetFeaturePropagation on cat(xyz, interp(x)) in the per-group form: W [C, 3+K] (xyz columns first), x [B*G,K],
+    xyz [B*N,3].  P = x . W[:,3:]^T once per centre (B*G rows instead of B*N), then Y = sum_k w_k P[idx_k] + xyz . W[:,:3]^T + b in one kernel.
+    Equal in real arithmetic to the plain form W . cat(xyz, sum_k w_k x[idx_k]) + b (the weights enter linearly)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, xyz, nn3, B, N, G):
+        idx, w, off, ent = nn3
+        x = _f32c(x)
+        wf = W[:, 3:].contiguous()
+        wxyz = W[:, :3].contiguous()
+        P = gemm(x, wf, True, True)
+        y = interp_rows_fwd(P, idx, w, B, N, G, xyz=xyz, wxyz=wxyz, bias=b)
+        ctx.save_for_backward(x, wf, xyz, w, off, ent)
+        ctx.dims = (B, N, G)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wf, xyz, w, off, ent = ctx.saved_tensors
+        dy = _f32c(dy)
+        dP = interp_rows_bwd(dy, off, ent, w, *ctx.dims)
+        dx = gemm(dP, wf, True, False) if ctx.needs_input_grad[0] else None
+        dW = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dwxyz, db = interp_xyz_grad(dy, xyz, want_w=ctx.needs_input_grad[1], want_b=ctx.has_bias and ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[1]:
+                dW = torch.cat((dwxyz, gemm(dP, x, False, False)), dim=1)
+        return dx, dW, db, None, None, None, None, None
+
+
+def interp_conv(x, W, b, xyz, nn3, B, N, G):
+    return InterpConvFn.apply(x, W, b, xyz, nn3, B, N, G)
+
+
+class LogSoftmaxFn(torch.autograd.Function):
+    """F.log_softmax over the last dim of rows [R,C], C <= 64"""
+
+    @staticmethod
+    def forward(ctx, z):
+        z = _f32c(z)
+        R, C = z.shape
+        out = torch.empty_like(z)
+        check(lib.act_log_softmax_fwd_f32(ptr(z), R, C, ptr(out), stream()), "act_log_softmax_fwd_f32")
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (out,) = ctx.saved_tensors
+        R, C = out.shape
+        dz = torch.empty_like(out)
+        check(lib.act_log_softmax_bwd_f32(ptr(out), ptr(_f32c(g)), R, C, ptr(dz), stream()), "act_log_softmax_bwd_f32")
+        return dz
+
+
+def log_softmax(z):
+    return LogSoftmaxFn.apply(z)
+
+
+class NllWeightedFn(torch.autograd.Function):
+    """F.nll_loss(logp, target, weight) (weighted mean) + the count of rows whose arg-max equals the target (int64, on the device)"""
+
+    @staticmethod
+    def forward(ctx, logp, target, weight):
+        logp = _f32c(logp)
+        R, C = logp.shape
+        dev = logp.device
+        tgt = target.to(torch.int64).contiguous()
+        wt = _f32c(weight) if weight is not None else None
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        wsum = torch.empty(1, dtype=torch.float32, device=dev)
+        correct = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = workspace(dev, lib.act_nll_weighted_workspace(R))
+        check(lib.act_nll_weighted_fwd_f32(ptr(logp), ptr(tgt), ptr(wt), R, C, ptr(loss), ptr(wsum), ptr(correct), ptr(ws), ws.numel() * 4,
+                                           stream()), "act_nll_weighted_fwd_f32")
+        ctx.save_for_backward(tgt, wt, wsum)
+        ctx.shape = (R, C)
+        ctx.mark_non_differentiable(correct)
+        return loss, correct
+
+    @staticmethod
+    def backward(ctx, g, _gc):
+        tgt, wt, wsum = ctx.saved_tensors
+        R, C = ctx.shape
+        dl = torch.empty(R, C, dtype=torch.float32, device=tgt.device)
+        check(lib.act_nll_weighted_bwd_f32(ptr(tgt), ptr(wt), ptr(wsum), ptr(_f32c(g).reshape(-1)), R, C, ptr(dl), stream()),
+              "act_nll_weighted_bwd_f32")
+        return dl, None, None
+
+
+def nll_weighted(logp, target, weight=None):
+    """-> (weighted-mean NLL, 0-d; number of rows with arg-max == target, int64 0-d), both on the device"""
+    loss, correct = NllWeightedFn.apply(logp, target, weight)
+    return loss.reshape(()), correct.reshape(())
+
+
+def confusion(pred, target, C, out=None):
+    """int64 [C,C] counts of (target, arg-max of pred) accumulated into ``out`` (new zeros if None); integer atomics, exact"""
+    pred = _f32c(pred)
+    tgt = target.to(torch.int64).contiguous()
+    if out is None:
+        out = torch.zeros(C, C, dtype=torch.int64, device=pred.device)
+    check(lib.act_confusion_i64(ptr(pred), ptr(tgt), pred.shape[0], C, ptr(out), stream()), "act_confusion_i64")
+    return out
+
+
+class GroupMeanFn(torch.autograd.Function):
+    """x [G*n, C] -> mean over the n rows of every group, [G, C]  (torch.mean(x, 2) of semantic_segmentation/models/pt.py)"""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        x = _f32c(x)
+        R, C = x.shape
+        out = torch.empty(R // n, C, dtype=torch.float32, device=x.device)
+        check(lib.act_group_sum_f32(ptr(x), R // n, n, C, ptr(out), stream()), "act_group_sum_f32")
+        ctx.n = n
+        return out.div_(n)
+
+    @staticmethod
+    def backward(ctx, dout):
+        G, C = dout.shape
+        return (dout / ctx.n).unsqueeze(1).expand(G, ctx.n, C).reshape(G * ctx.n, C), None
+
+
+def group_mean(x, n):
+    return GroupMeanFn.apply(x, n)
+
+
 # ---- the product forms of the block-level Functions live in act_amd.composite (one host call per module); resolved lazily so that
 # either module may be imported first.  ACT_COMPOSITE=0 selects the per-kernel host path above.
 def __getattr__(name):

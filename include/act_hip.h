@@ -541,6 +541,38 @@ size_t act_dgcnn_scratch_floats(const act_dgcnn_t* m);
 int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* idx, float* h, float* scratch, float* workspace,
                            size_t workspace_bytes, act_stream_t stream);
 
+/* ---- dense per-point prediction (semantic segmentation head; csrc/seg.hip) --------------------------------------------------
+ * semantic_segmentation/models/pointnet2_utils.py:262-315 (PointNetFeaturePropagation) and models/pt.py (log_softmax, nll_loss).
+ * Three nearest centres of every point: xyz [B,N,3], centers [B,G,3] (3 <= G <= 512) -> idx int32 [B,N,3] in ascending (distance, index) order
+ * (ties: lower index), weight [B,N,3] = (1/(d+1e-8)) / sum.  d is the DIFFERENCE form (dx*dx+dy*dy)+dz*dz in fp32 without FMA (the reference
+ * uses the expansion form).  adj_off int32 [B,G+1] / adj_ent int32 [B,3N] (both or neither): per cloud, the entries e = 3n+k that
+ * chose centre g, in increasing e, at adj_ent[off[g] .. off[g+1]) -- the inverse adjacency of the interpolation backward (counting sort). */
+int act_three_nn_f32(const float* xyz, const float* centers, int B, int N, int G, int32_t* idx, float* weight, int32_t* adj_off,
+                     int32_t* adj_ent, act_stream_t stream);
+/* Y [B*N,C] = sum_k weight[n,k] * P[b*G + idx[n,k], :]  (+ xyz[n] . wxyz[c,:] if wxyz, wxyz [C,3]; + bias[c] if bias).  C % 4 == 0, P / Y / bias
+ * 16-byte aligned. */
+int act_interp_rows_fwd_f32(const float* P, const int32_t* idx, const float* weight, const float* xyz, const float* wxyz, const float* bias,
+                            int B, int N, int G, int C, float* Y, act_stream_t stream);
+/* dP [B*G,C] = sum over the adjacency of centre g (increasing e) of weight[e] * dY[b*N + e/3, :]: a gather, bit-identical run to run. */
+int act_interp_rows_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
+                            float* dP, act_stream_t stream);
+/* dwxyz [C,3] = dY^T xyz, dbias [C] = column sums of dY (either may be NULL); dY [R,C], xyz [R,3]; per-block partials + one ordered pass. */
+size_t act_interp_xyz_grad_workspace(long long R, int C);
+int act_interp_xyz_grad_f32(const float* dY, const float* xyz, long long R, int C, float* dwxyz, float* dbias, float* workspace,
+                            size_t workspace_bytes, act_stream_t stream);
+/* row log-softmax [R,C] (C <= 64) and its backward dz = dout - exp(logp) * rowsum(dout) */
+int act_log_softmax_fwd_f32(const float* z, long long R, int C, float* out, act_stream_t stream);
+int act_log_softmax_bwd_f32(const float* logp, const float* dout, long long R, int C, float* dz, act_stream_t stream);
+/* F.nll_loss(logp, target, weight) (weighted mean; weight NULL = ones): loss[0], wsum[0] = sum of w[t], correct[0] (int64, may be NULL) = rows whose
+ * arg-max (lowest index on ties) equals the target.  Deterministic: per-block partials, one ordered pass.  Targets outside [0,C) are skipped. */
+size_t act_nll_weighted_workspace(long long R);
+int act_nll_weighted_fwd_f32(const float* logp, const int64_t* target, const float* weight, long long R, int C, float* loss, float* wsum,
+                             int64_t* correct, float* workspace, size_t workspace_bytes, act_stream_t stream);
+int act_nll_weighted_bwd_f32(const int64_t* target, const float* weight, const float* wsum, const float* gloss, long long R, int C, float* dlogp,
+                             act_stream_t stream);
+/* cm int64 [C,C] += counts of (target, arg-max of pred row) (lowest index on ties); rows with a target outside [0,C) are skipped */
+int act_confusion_i64(const float* pred, const int64_t* target, long long R, int C, int64_t* cm, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
