@@ -1554,6 +1554,113 @@ def group_mean(x, n):
     return GroupMeanFn.apply(x, n)
 
 
+# ---- part segmentation (csrc/partseg.hip): category label branch, category-masked evaluation -------------------------------------------
+_C._declare({
+    "act_label_branch_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp],
+    "act_label_branch_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp],
+    "act_part_eval_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp],
+})
+for _n in ("act_label_branch_fwd_f32", "act_label_branch_bwd_f32", "act_part_eval_f32"):
+    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
+
+PART_COUNT_STRIDE = 16          # int32 per shape in the part-evaluation counts: [0,6) intersections, [6,12) unions, [12] category, [13] parts
+
+
+class LabelBranchFn(torch.autograd.Function):
+    """label_conv_cls of part_segmentation/models/pt.py: LeakyReLU(BatchNorm1d(cls [B,16] . W^T)) -> [B,64], one launch each way.  train: batch
+    statistics over the B rows, running stats updated in place (momentum, unbiased variance with count B); eval: running statistics.  ``cls`` is
+    taken as given (any [B,16] rows, not only one-hot) and gets no gradient; the backward gives dW, dgamma, dbeta (fixed-order sums over B,
+    float64 inside the kernels, one rounding per output)."""
+
+    @staticmethod
+    def forward(ctx, cls, W, gamma, beta, running_mean, running_var, training, momentum, eps, slope):
+        cls = _f32c(cls)
+        B = cls.shape[0]
+        if cls.dim() != 2 or cls.shape[1] != 16 or tuple(W.shape) != (64, 16):
+            raise _C.ActHipError(f"label branch: expected cls [B,16] and W [64,16], got {tuple(cls.shape)} / {tuple(W.shape)}")
+        if training and B < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {[B, 16, 1]}")
+        dev = cls.device
+        W = _f32c(W)
+        y = torch.empty(B, 64, dtype=torch.float32, device=dev)
+        check(lib.act_label_branch_fwd_f32(ptr(cls), ptr(W), ptr(gamma), ptr(beta), B, int(training), float(eps), float(momentum), float(slope),
+                                           ptr(running_mean), ptr(running_var), ptr(y), stream()), "act_label_branch_fwd_f32")
+        ctx.save_for_backward(cls, W, gamma, beta)
+        ctx.training, ctx.slope, ctx.eps = training, float(slope), float(eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        cls, W, gamma, beta = ctx.saved_tensors
+        if not ctx.training:
+            raise NotImplementedError("label branch backward in eval mode is off the training path")
+        if ctx.needs_input_grad[0]:
+            raise NotImplementedError("label branch: the category rows are constants (no gradient)")
+        B = cls.shape[0]
+        dW = torch.empty(64, 16, dtype=torch.float32, device=cls.device)
+        dg = torch.empty(64, dtype=torch.float32, device=cls.device)
+        db = torch.empty(64, dtype=torch.float32, device=cls.device)
+        check(lib.act_label_branch_bwd_f32(ptr(cls), ptr(W), ptr(gamma), ptr(beta), ptr(_f32c(dy)), B, ctx.eps, ctx.slope, ptr(dW), ptr(dg), ptr(db),
+                                           stream()), "act_label_branch_bwd_f32")
+        return None, dW, dg, db, None, None, None, None, None, None
+
+
+def label_branch(cls, conv, bn, act, training):
+    """nn.Sequential(Conv1d(16, 64, 1, bias=False), BatchNorm1d(64), LeakyReLU(slope)) on cls [B,16] with the modules' parameters / buffers"""
+    if training and bn.num_batches_tracked is not None and cls.shape[0] >= 2:
+        bn.num_batches_tracked.add_(1)
+    return LabelBranchFn.apply(cls, conv.weight.view(64, 16), bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps,
+                               act.negative_slope)
+
+
+def part_tables(seg_classes, num_part=50, device=None):
+    """{category: [parts]} -> (part -> category int32 [num_part], category -> first part int32 [ncat + 1]) with the categories in sorted
+    order (the order of synsetoffset2category.txt); every category's parts must be one contiguous range"""
+    cats = sorted(seg_classes)
+    p2c = torch.full((num_part,), -1, dtype=torch.int32)
+    first = [0]
+    for ci, c in enumerate(cats):
+        parts = sorted(seg_classes[c])
+        if parts != list(range(first[-1], first[-1] + len(parts))):
+            raise ValueError(f"part ranges must be contiguous in category order: {c} {parts}")
+        p2c[parts] = ci
+        first.append(first[-1] + len(parts))
+    return p2c.to(device), torch.tensor(first, dtype=torch.int32, device=device)
+
+
+_PART_TABLES = {}
+
+
+def partseg_eval(logp, target, counts, seen, correct, shape_offset, pred=None, tables=None):
+    """category-masked evaluation of one batch (main.py:235-299): logp [B,N,P] (or [B*N,P]) log-probs, target [B,N] int.  Writes the per-shape
+    int32 records counts[shape_offset : shape_offset + B] (counts [S,16]: intersections, unions, category, parts), adds the per-part int64
+    seen / correct counts ([P]) in place, and writes the masked arg-max into ``pred`` (int32 [B*N]) when given.  ``tables``: part_tables(...)
+    (default: the ShapeNetPart categories of datasets.ShapeNetPartDataset.seg_classes)."""
+    if target.dim() != 2:
+        raise _C.ActHipError("partseg_eval: target must be [B, N]")
+    B, N = target.shape
+    P = logp.shape[-1]
+    lp = _f32c(logp).reshape(B * N, P)
+    tgt = target.to(torch.int64).contiguous()
+    if tables is None:
+        key = lp.device
+        if key not in _PART_TABLES:
+            from .datasets.ShapeNetPartDataset import seg_classes
+            _PART_TABLES[key] = part_tables(seg_classes, device=lp.device)
+        tables = _PART_TABLES[key]
+    p2c, first = tables
+    if p2c.numel() != P:
+        raise _C.ActHipError(f"partseg_eval: {P} log-prob columns against a {p2c.numel()}-part table")
+    for t, width, dt in ((counts, PART_COUNT_STRIDE, torch.int32), (seen, P, torch.int64), (correct, P, torch.int64)):
+        if t.dtype != dt or not t.is_contiguous() or t.shape[-1] != width or t.device != lp.device:
+            raise _C.ActHipError(f"partseg_eval: bad output buffer {tuple(t.shape)} {t.dtype}")
+    if pred is not None and (pred.dtype != torch.int32 or pred.numel() != B * N or not pred.is_contiguous()):
+        raise _C.ActHipError("partseg_eval: pred must be int32 [B*N]")
+    check(lib.act_part_eval_f32(ptr(lp), ptr(tgt), B, N, P, ptr(p2c), ptr(first), first.numel() - 1, ptr(pred), ptr(counts), int(shape_offset),
+                                counts.shape[0], ptr(seen), ptr(correct), stream()), "act_part_eval_f32")
+    return pred
+
+
 # ---- the product forms of the block-level Functions live in act_amd.composite (one host call per module); resolved lazily so that
 # either module may be imported first.  ACT_COMPOSITE=0 selects the per-kernel host path above.
 def __getattr__(name):

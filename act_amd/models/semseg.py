@@ -67,6 +67,9 @@ class PointNetFeaturePropagation(nn.Module):
 
 
 class get_model(nn.Module):
+    LABEL_DIM = 0               # part segmentation (models/partseg.py) sets 16: the category label branch and its 64 per-cloud columns
+    LOGGER = "SemSeg"
+
     def __init__(self, cls_dim):
         super().__init__()
         self.trans_dim = 384
@@ -83,8 +86,10 @@ class get_model(nn.Module):
         dpr = [x.item() for x in torch.linspace(0, self.drop_path_rate, self.depth)]
         self.blocks = TransformerEncoder(embed_dim=self.trans_dim, depth=self.depth, drop_path_rate=dpr, num_heads=self.num_heads)
         self.norm = nn.LayerNorm(self.trans_dim)
+        if self.LABEL_DIM:                      # the reference registers it here: its state_dict keys sit between norm and propagation_0_cls
+            self.label_conv_cls = nn.Sequential(nn.Conv1d(self.LABEL_DIM, 64, kernel_size=1, bias=False), nn.BatchNorm1d(64), nn.LeakyReLU(0.2))
         self.propagation_0_cls = PointNetFeaturePropagation(in_channel=1152 + 3, mlp=[self.trans_dim * 4, 1024])
-        self.convs1_cls = nn.Conv1d(3328, 512, 1)
+        self.convs1_cls = nn.Conv1d(3328 + (64 if self.LABEL_DIM else 0), 512, 1)
         self.dp1 = nn.Dropout(0.5)
         self.convs2_cls = nn.Conv1d(512, 256, 1)
         self.convs3_cls = nn.Conv1d(256, self.cls_dim, 1)
@@ -111,12 +116,14 @@ class get_model(nn.Module):
                 sd[k[len("base_model."):]] = sd.pop(k)
         return sd
 
-    def _report(self, incompatible, path):
+    def _report(self, incompatible, path, mismatched=()):
+        if mismatched:
+            print_log(f"size mismatch, kept at their initial values: {list(mismatched)}", logger=self.LOGGER)
         if incompatible.missing_keys:
-            print_log(f"missing_keys: {incompatible.missing_keys}", logger="SemSeg")
+            print_log(f"missing_keys: {incompatible.missing_keys}", logger=self.LOGGER)
         if incompatible.unexpected_keys:
-            print_log(f"unexpected_keys: {incompatible.unexpected_keys}", logger="SemSeg")
-        print_log(f"[Transformer] Successful Loading the ckpt from {path}", logger="SemSeg")
+            print_log(f"unexpected_keys: {incompatible.unexpected_keys}", logger=self.LOGGER)
+        print_log(f"[Transformer] Successful Loading the ckpt from {path}", logger=self.LOGGER)
 
     def load_model_from_ckpt(self, bert_ckpt_path, model_key="ACT_encoder"):
         """ACT pretraining checkpoint ({'base_model': state_dict}): strips ``module.``, ``<model_key>.`` and ``base_model.``, loads non-strictly"""
@@ -128,18 +135,26 @@ class get_model(nn.Module):
         return incompatible
 
     def load_model_from_ckpt_withrename(self, bert_ckpt_path):
-        """checkpoint of this model or of its part-segmentation sibling ({'model_state_dict': ...}); keys without ``_cls`` map onto ``*_cls``"""
+        """checkpoint of this model or of its segmentation sibling ({'model_state_dict': ...}); keys without ``_cls`` map onto ``*_cls``.
+        Entries whose shape differs from this model's (the other task's heads: convs1_cls, convs3_cls) are not loaded: they keep their
+        initial values, are printed, and are returned among ``missing_keys``."""
         if bert_ckpt_path is None:
             return None
         ckpt = torch.load(bert_ckpt_path, map_location="cpu")["model_state_dict"]
         model_dict = self.state_dict()
+        mismatched = []
         for k in list(model_dict.keys()):
-            if k in ckpt:
-                model_dict[k] = ckpt[k]
-            elif k.replace("_cls", "") in ckpt:
-                model_dict[k] = ckpt[k.replace("_cls", "")]
+            src = k if k in ckpt else (k.replace("_cls", "") if k.replace("_cls", "") in ckpt else None)
+            if src is None:
+                continue
+            if ckpt[src].shape != model_dict[k].shape:
+                mismatched.append(k)
+            else:
+                model_dict[k] = ckpt[src]
         incompatible = self.load_state_dict(model_dict, strict=False)
-        self._report(incompatible, bert_ckpt_path)
+        self._report(incompatible, bert_ckpt_path, mismatched)
+        if mismatched:
+            incompatible = type(incompatible)(mismatched + list(incompatible.missing_keys), incompatible.unexpected_keys)
         return incompatible
 
     def _dropout(self, x, draws):
@@ -166,15 +181,20 @@ class get_model(nn.Module):
 
     def forward(self, pts, draws=None, pergroup=None):
         """pts [B, 3, N] (the reference's layout) -> log-probabilities [B, N, cls_dim]"""
-        B, _, N = pts.shape
         xyz = pts.transpose(1, 2).contiguous()
         x, center = self.features(xyz, draws)
+        return self.head(xyz, x, center, (), draws, pergroup)
+
+    def head(self, xyz, x, center, extra=(), draws=None, pergroup=None):
+        """xyz [B,N,3], x [B*G,1152], center [B,G,3]; ``extra``: per-cloud blocks appended to the global feature (part segmentation: the
+        label branch's [B,64]) -> log-probabilities [B, N, cls_dim]"""
+        B, N, _ = xyz.shape
         G = center.shape[1]
-        glob = torch.cat((K.group_max(x, G), K.group_mean(x, G)), dim=1)                # [B, 2304]
+        glob = torch.cat((K.group_max(x, G), K.group_mean(x, G)) + tuple(extra), dim=1)  # [B, 2304 (+ 64)]
         f0 = self.propagation_0_cls(xyz, center, x, pergroup=pergroup)                # [B*N, 1024]
         w1 = _w2d(self.convs1_cls)
         nf = f0.shape[1]
-        g = K.linear(glob, w1[:, nf:], self.convs1_cls.bias)                            # per-cloud half, once per cloud
+        g = K.linear(glob, w1[:, nf:], self.convs1_cls.bias)                            # per-cloud columns, once per cloud
         h = K.batch_norm_act(K.linear_group_add(f0, w1[:, :nf], g, N), self.bns1_cls, self.training, relu=True)
         h = self._dropout(h, draws)
         h = K.batch_norm_act(K.linear(h, _w2d(self.convs2_cls), self.convs2_cls.bias), self.bns2_cls, self.training, relu=True)

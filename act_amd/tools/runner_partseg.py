@@ -1,0 +1,203 @@
+"""ShapeNetPart part segmentation: training + category-masked evaluation (reference: part_segmentation/main.py), single GPU.
+
+    python -m act_amd.tools.runner_partseg --root data/ShapeNetPart --ckpts act_pretrain.pth
+    python -m act_amd.tools.runner_partseg --synthetic --max_steps 150
+
+Same arguments and defaults as the reference except ``--ckpts``, which defaults to None (the reference's default names a file of its authors'
+machine), plus ``--synthetic`` (generated shapes, act_amd.datasets.ShapeNetPartDataset.SyntheticShapeNetPart), ``--max_steps`` (stop training after
+that many steps, then evaluate once), ``--log_every``, ``--eval_batches``, ``--seed`` and ``--num_workers``.  ``--normal`` is refused: the reference
+model has no 6-channel input.  Per step, like the reference: isotropic scale U[0.8, 1.25] and shift U[-0.1, 0.1]^3 per cloud (one launch on the
+device), unweighted NLL, ``optimizer.step()``, gradient clipping at 10, a second ``optimizer.step()``, ``zero_grad`` (main.py:196-222); train
+accuracy uses the unmasked arg-max.  No host synchronisation per step: loss and correct counts accumulate on the device and are read once per
+``--log_every`` steps.  Evaluation runs one kernel per batch (kernels.partseg_eval: arg-max over the shape's category range, per-shape part
+intersections / unions, per-part seen / correct) into buffers that hold the whole evaluation and reads them once; every metric of main.py:235-299
+is then formed in float64 on the host.  Categories or parts that never occur in an ``--eval_batches`` subset are left out of their means (the
+reference would print NaN); on the full test set the two agree.  Checkpoint ``best_model.pth`` when the instance mIoU is >= the best:
+``{epoch, train_acc, test_acc, class_avg_iou, inctance_avg_iou, model_state_dict, optimizer_state_dict}`` (the reference's spelling).
+"""
+import argparse
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import builder
+from .. import kernels as K
+from ..datasets.ShapeNetPartDataset import PartNormalDataset, SyntheticShapeNetPart, CATEGORIES, NUM_CATEGORIES, NUM_PARTS, seg_classes
+from ..datasets.data_transforms import PointcloudScaleAndTranslate
+from ..models.partseg import get_model, get_loss, to_categorical
+from .runner_semseg import add_weight_decay, _seed_worker
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser('Model')
+    p.add_argument('--model', type=str, default='pt', help='model name')
+    p.add_argument('--optimizer_part', type=str, default='all', help='training all parameters or optimizing the new layers only')
+    p.add_argument('--batch_size', type=int, default=16, help='batch Size during training')
+    p.add_argument('--epoch', default=300, type=int, help='epoch to run')
+    p.add_argument('--warmup_epoch', default=10, type=int, help='warmup epoch')
+    p.add_argument('--learning_rate', default=0.0002, type=float, help='initial learning rate')
+    p.add_argument('--gpu', type=str, default='0', help='specify GPU devices')
+    p.add_argument('--log_dir', type=str, default='./exp', help='log path')
+    p.add_argument('--npoint', type=int, default=2048, help='point Number')
+    p.add_argument('--normal', action='store_true', default=False, help='use normals')
+    p.add_argument('--ckpts', type=str, default=None, help='ckpts')
+    p.add_argument('--root', type=str, default='../data/ShapeNetPart/', help='data root')
+    # not in the reference
+    p.add_argument('--synthetic', action='store_true', default=False, help='generated shapes instead of the ShapeNetPart files')
+    p.add_argument('--max_steps', type=int, default=0, help='stop training after this many steps (0: run every epoch)')
+    p.add_argument('--log_every', type=int, default=20, help='steps between two reads of the accumulated loss / accuracy')
+    p.add_argument('--eval_batches', type=int, default=0, help='evaluate on at most this many test batches (0: all)')
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--num_workers', type=int, default=4)
+    return p.parse_args(argv)
+
+
+REFERENCE_ARGS = ('model', 'optimizer_part', 'batch_size', 'epoch', 'warmup_epoch', 'learning_rate', 'gpu', 'log_dir', 'npoint', 'normal',
+                  'ckpts', 'root')
+
+
+def part_metrics(counts, seen, correct):
+    """per-shape records (counts int [S,16]: intersections [0,6), unions [6,12), category [12], parts [13]) and per-part seen / correct
+    [50] -> the metrics of main.py:235-299 in float64: accuracy, class_avg_accuracy, class_avg_iou, inctance_avg_iou, per-category mIoU
+    ({name: value} over the categories that occur).  A part absent from both target and prediction of a shape counts IoU 1.0; categories and
+    parts that never occur are left out of their means."""
+    counts = np.asarray(counts, dtype=np.int64)
+    seen = np.asarray(seen, dtype=np.int64)
+    correct = np.asarray(correct, dtype=np.int64)
+    shape_ious = {c: [] for c in CATEGORIES}
+    for rec in counts:
+        cat, n = int(rec[12]), int(rec[13])
+        if cat < 0:
+            continue
+        inter, union = rec[0:n], rec[6:6 + n]
+        ious = [1.0 if union[l] == 0 else inter[l] / float(union[l]) for l in range(n)]
+        shape_ious[CATEGORIES[cat]].append(np.mean(ious))
+    all_ious = [v for c in CATEGORIES for v in shape_ious[c]]
+    per_cat = {c: float(np.mean(shape_ious[c])) for c in CATEGORIES if shape_ious[c]}
+    present = seen > 0
+    return dict(accuracy=float(correct.sum() / float(max(seen.sum(), 1))),
+                class_avg_accuracy=float(np.mean(correct[present] / seen[present].astype(np.float64))) if present.any() else 0.0,
+                class_avg_iou=float(np.mean(list(per_cat.values()))) if per_cat else 0.0,
+                inctance_avg_iou=float(np.mean(all_ious)) if all_ious else 0.0,
+                per_category=per_cat)
+
+
+def datasets(args):
+    if args.synthetic:
+        return (SyntheticShapeNetPart('trainval', args.npoint, seed=args.seed), SyntheticShapeNetPart('test', args.npoint, seed=args.seed))
+    root = os.path.join(args.root, 'shapenetcore_partanno_segmentation_benchmark_v0_normal')
+    return (PartNormalDataset(root, args.npoint, 'trainval', normal_channel=args.normal, rng=np.random.default_rng(args.seed)),
+            PartNormalDataset(root, args.npoint, 'test', normal_channel=args.normal, rng=np.random.default_rng(args.seed + 1)))
+
+
+@torch.no_grad()
+def evaluate(model, loader, device, max_batches=0):
+    """-> metrics dict (part_metrics); one kernel per batch, one host read of the counts at the end"""
+    model.eval()
+    nb = len(loader) if not max_batches else min(max_batches, len(loader))
+    S = min(len(loader.dataset), nb * loader.batch_size)
+    counts = torch.zeros(S, K.PART_COUNT_STRIDE, dtype=torch.int32, device=device)
+    seen = torch.zeros(NUM_PARTS, dtype=torch.int64, device=device)
+    correct = torch.zeros(NUM_PARTS, dtype=torch.int64, device=device)
+    off = 0
+    for i, (pts, label, target) in enumerate(loader):
+        if max_batches and i >= max_batches:
+            break
+        pts = pts.to(device, torch.float32, non_blocking=True)
+        label = label.to(device, torch.int64, non_blocking=True)
+        target = target.to(device, torch.int64, non_blocking=True)
+        logp = model(pts.transpose(2, 1), to_categorical(label, NUM_CATEGORIES))
+        K.partseg_eval(logp, target, counts, seen, correct, off)
+        off += pts.shape[0]
+    return part_metrics(counts[:off].cpu().numpy(), seen.cpu().numpy(), correct.cpu().numpy())
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.normal:
+        raise SystemExit("--normal: the reference's part-segmentation model takes xyz only (it has no 6-channel input); run without --normal")
+    torch.manual_seed(args.seed)
+    device = torch.device('cuda', torch.cuda.current_device())
+    train_set, test_set = datasets(args)
+    g = torch.Generator().manual_seed(args.seed)
+    train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=True,
+                                               generator=g, pin_memory=True, persistent_workers=args.num_workers > 0,
+                                               worker_init_fn=_seed_worker)
+    test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers,
+                                              generator=torch.Generator().manual_seed(args.seed + 1), worker_init_fn=_seed_worker)
+    print(f"The number of training data is: {len(train_set)}", flush=True)
+    print(f"The number of test data is: {len(test_set)}", flush=True)
+
+    model = get_model(NUM_PARTS).to(device)
+    crit = get_loss()
+    if args.ckpts is not None:
+        model.load_model_from_ckpt(args.ckpts)
+    print('# generator parameters:', sum(p.numel() for p in model.parameters()), flush=True)
+    groups = add_weight_decay(model, weight_decay=0.05, optimizer_part=args.optimizer_part)
+    optimizer = builder.FusedAdamW(groups, lr=args.learning_rate, weight_decay=0.05, fused=True)
+    scheduler = builder.CosineLRScheduler(optimizer, t_initial=args.epoch, lr_min=1e-6, warmup_lr_init=1e-6, warmup_t=args.warmup_epoch,
+                                          cycle_limit=1, t_in_epochs=True)
+    augment = PointcloudScaleAndTranslate(scale_low=0.8, scale_high=1.25, translate_range=0.1)
+    ckpt_dir = os.path.join(args.log_dir, 'checkpoints')
+    os.makedirs(ckpt_dir, exist_ok=True)
+    best_inst, step, done = 0.0, 0, False
+    loss_acc = torch.zeros((), dtype=torch.float32, device=device)
+    correct_acc = torch.zeros((), dtype=torch.int64, device=device)
+    ep_correct = torch.zeros((), dtype=torch.int64, device=device)
+    seen, ep_seen, t0 = 0, 0, time.time()
+    model.zero_grad(set_to_none=True)
+    for epoch in range(args.epoch):
+        model.train()
+        ep_correct.zero_()
+        ep_seen = 0
+        for pts, label, target in train_loader:
+            pts = pts.to(device, torch.float32, non_blocking=True).contiguous()
+            label = label.to(device, torch.int64, non_blocking=True)
+            target = target.to(device, torch.int64, non_blocking=True).reshape(-1)
+            B = pts.shape[0]
+            scale = torch.empty(B, 1, device=device).uniform_(0.8, 1.25).expand(B, 3)       # isotropic (provider.random_scale_point_cloud)
+            augment(pts, scale=scale)
+            logp = model(pts.transpose(2, 1), to_categorical(label, NUM_CATEGORIES))
+            loss, correct = crit.with_correct(logp, target)
+            loss.backward()
+            optimizer.step()
+            torch.nn.utils.clip_grad_norm_(model.parameters(), 10, norm_type=2)
+            optimizer.step()
+            model.zero_grad(set_to_none=True)
+            loss_acc += loss.detach()
+            correct_acc += correct
+            ep_correct += correct
+            seen += B * args.npoint
+            ep_seen += B * args.npoint
+            step += 1
+            if step % args.log_every == 0:
+                l, c = loss_acc.item() / args.log_every, correct_acc.item() / seen
+                print(f"epoch {epoch} step {step}: loss {l:.4f} acc {100 * c:.2f}% lr {optimizer.param_groups[0]['lr']:.2e} "
+                      f"({(time.time() - t0) / args.log_every * 1e3:.1f} ms/step)", flush=True)
+                loss_acc.zero_(); correct_acc.zero_(); seen, t0 = 0, time.time()
+            if args.max_steps and step >= args.max_steps:
+                done = True
+                break
+        scheduler.step(epoch)                                             # main.py: after the epoch, with its index
+        train_acc = ep_correct.item() / max(ep_seen, 1)
+        m = evaluate(model, test_loader, device, args.eval_batches)
+        for c in sorted(m['per_category']):
+            print('eval mIoU of %s %f' % (c + ' ' * (14 - len(c)), m['per_category'][c] * 100.0), flush=True)
+        print(f"eval epoch {epoch}: train acc {100 * train_acc:.2f} test accuracy {100 * m['accuracy']:.2f} class avg accuracy "
+              f"{100 * m['class_avg_accuracy']:.2f} class avg mIoU {100 * m['class_avg_iou']:.2f} instance avg mIoU {100 * m['inctance_avg_iou']:.2f}",
+              flush=True)
+        if m['inctance_avg_iou'] >= best_inst:
+            best_inst = m['inctance_avg_iou']
+            torch.save({'epoch': epoch, 'train_acc': train_acc, 'test_acc': m['accuracy'], 'class_avg_iou': m['class_avg_iou'],
+                        'inctance_avg_iou': m['inctance_avg_iou'], 'model_state_dict': model.state_dict(),
+                        'optimizer_state_dict': optimizer.state_dict()}, os.path.join(ckpt_dir, 'best_model.pth'))
+        if done:
+            break
+    print(f"best instance mIoU {100 * best_inst:.2f}", flush=True)
+    return best_inst
+
+
+if __name__ == '__main__':
+    main()

@@ -573,6 +573,25 @@ int act_nll_weighted_bwd_f32(const int64_t* target, const float* weight, const f
 /* cm int64 [C,C] += counts of (target, arg-max of pred row) (lowest index on ties); rows with a target outside [0,C) are skipped */
 int act_confusion_i64(const float* pred, const int64_t* target, long long R, int C, int64_t* cm, act_stream_t stream);
 
+/* ---- part segmentation (ShapeNetPart; csrc/partseg.hip) -------------------------------------------------------------------------
+ * part_segmentation/models/pt.py label_conv_cls = Conv1d(16, 64, bias=False) + BatchNorm1d(64) + LeakyReLU(slope) on the category rows
+ * cls [B,16] (any values, not only one-hot), W [64,16] -> y [B,64].  training: batch statistics over the B rows (B >= 2), running_mean /
+ * running_var updated in place (momentum, unbiased variance with count B); eval: running statistics.  One launch each, float64 inside,
+ * one rounding per output; every reduction over B runs in a fixed order (bit-identical run to run, no float atomics). */
+int act_label_branch_fwd_f32(const float* cls, const float* W, const float* gamma, const float* beta, int B, int training, float eps, float momentum,
+                             float slope, float* running_mean, float* running_var, float* y, act_stream_t stream);
+/* backward of the train-mode branch from dy [B,64] (batch statistics recomputed from cls and W): dW [64,16], dgamma [64], dbeta [64]
+ * (no gradient for cls) */
+int act_label_branch_bwd_f32(const float* cls, const float* W, const float* gamma, const float* beta, const float* dy, int B, float eps, float slope,
+                             float* dW, float* dgamma, float* dbeta, act_stream_t stream);
+/* category-masked evaluation (main.py:235-299), one workgroup per shape: logp [B*N,P] (P <= 64), target int64 [B*N]; the shape's category is
+ * part2cat[target[first point]] (int32 [P]) and its parts are [cat_first[c], cat_first[c+1]) (int32 [ncat+1], at most 6 parts).
+ * pred (int32 [B*N], may be NULL) = arg-max over that range (ties: first index).  counts int32 [num_shapes,16]: row shape_offset + i gets
+ * [0,6) intersections and [6,12) unions of the local parts, [12] the category (-1 when the first target is not a valid part), [13] the
+ * number of parts, [14,16) zero.  seen / correct int64 [P] += per-part counts of target == l and pred == target == l (integer atomics). */
+int act_part_eval_f32(const float* logp, const int64_t* target, int B, int N, int P, const int32_t* part2cat, const int32_t* cat_first, int ncat,
+                      int32_t* pred, int32_t* counts, int shape_offset, int num_shapes, int64_t* seen, int64_t* correct, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
