@@ -46,8 +46,17 @@ SIGNATURES = {
     "act_chamfer_fwd_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "act_chamfer_fwd_ex_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "act_chamfer_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
+    # whole-room sliding-window testing (csrc/wholescene.hip)
+    "act_scene_member_workspace": [_ll, _i, _i],
+    "act_scene_member_count": [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    "act_scene_member_fill": [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+    "act_scene_rows": [_vp, _vp, _vp, _vp, _i, _ll, _i, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, _vp, _vp],
+    "act_scene_gather": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp],
+    "act_scene_vote": [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp],
+    "act_scene_finish": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
 }
-_RESTYPE = {"act_arch": ctypes.c_char_p, "act_prof_kernel_name": ctypes.c_char_p, "act_fps_scratch_floats": ctypes.c_size_t}
+_RESTYPE = {"act_arch": ctypes.c_char_p, "act_prof_kernel_name": ctypes.c_char_p, "act_fps_scratch_floats": ctypes.c_size_t,
+            "act_scene_member_workspace": ctypes.c_size_t}
 
 
 def _declare(extra=None):

@@ -7,6 +7,10 @@ Items are ``(xyz [num_point, 3], labels [num_point])``.  The random stream is an
 
 ``SyntheticS3DIS`` generates rooms on the fly for machines without the data: labels are a deterministic function of local geometry
 (floor, ceiling, walls, columns, a beam, windows and doors in the walls, and box-shaped furniture classes), all 13 ids.
+
+``S3DISWholeScene`` (alias ``ScannetDatasetWholeScene``, reference: dataset.py:150-235) tiles whole rooms with overlapping blocks for
+main_test.py: the per-block thresholds / centres for the device path (``block_table``) and the reference's host ``__getitem__`` restated with an
+injectable ``numpy.random.RandomState``.  ``SyntheticS3DISWholeScene`` writes synthetic rooms as ``Area_5_*.npy`` files and loads them.
 """
 import os
 
@@ -154,3 +158,119 @@ class SyntheticS3DIS(data.Dataset):
 
     def __len__(self):
         return len(self.room_idxs)
+
+
+class S3DISWholeScene:
+    """whole rooms of ``test_area`` (split 'test') or of the other areas (split 'train'), as dataset.py ScannetDatasetWholeScene loads them:
+    ``file_list`` in ``os.listdir`` order, ``scene_points_list`` (xyzrgb, the file's dtype), ``semantic_labels_list``, and ``labelweights``
+    over the split ((max(p) / p)^(1/3), float32; a class absent from the split gets an infinite weight, whose rows never vote)."""
+
+    def __init__(self, root, block_points=4096, split='test', test_area=5, stride=0.5, block_size=1.0, padding=0.001):
+        self.block_points, self.block_size, self.padding, self.root, self.split, self.stride = block_points, block_size, padding, root, split, stride
+        assert split in ['train', 'test']
+        tag = 'Area_%d' % test_area
+        self.file_list = [d for d in os.listdir(root) if (d.find(tag) == -1) == (split == 'train')]
+        self.scene_points_list, self.semantic_labels_list, self.scene_points_num = [], [], []
+        for file in self.file_list:
+            data = np.load(os.path.join(root, file))
+            self.scene_points_list.append(data[:, :6])
+            self.semantic_labels_list.append(data[:, 6])
+            self.scene_points_num.append(data.shape[0])
+        with np.errstate(divide='ignore'):
+            self.labelweights = label_weights(self.semantic_labels_list)
+
+    def __len__(self):
+        return len(self.scene_points_list)
+
+    def scene_name(self, index):
+        return self.file_list[index][:-4]
+
+    def _grid(self, index):
+        points = self.scene_points_list[index]
+        coord_min, coord_max = np.amin(points, axis=0)[:3], np.amax(points, axis=0)[:3]
+        grid_x = int(np.ceil(float(coord_max[0] - coord_min[0] - self.block_size) / self.stride) + 1)
+        grid_y = int(np.ceil(float(coord_max[1] - coord_min[1] - self.block_size) / self.stride) + 1)
+        if grid_x <= 0 or grid_y <= 0:
+            raise ValueError(f"room {self.file_list[index]} is too narrow for a {self.block_size} m block at stride {self.stride} "
+                             f"(extent {float(coord_max[0] - coord_min[0]):.3f} x {float(coord_max[1] - coord_min[1]):.3f}): no block to test")
+        return coord_min, coord_max, grid_x, grid_y
+
+    def _bounds(self, coord_min, coord_max, index_x, index_y):
+        """the reference's block expressions, in the room file's dtype (NumPy 2 scalar promotion: float32 stays float32)"""
+        s_x = coord_min[0] + index_x * self.stride
+        e_x = min(s_x + self.block_size, coord_max[0])
+        s_x = e_x - self.block_size
+        s_y = coord_min[1] + index_y * self.stride
+        e_y = min(s_y + self.block_size, coord_max[1])
+        s_y = e_y - self.block_size
+        return (s_x - self.padding, e_x + self.padding, s_y - self.padding, e_y + self.padding,
+                s_x + self.block_size / 2.0, s_y + self.block_size / 2.0)
+
+    def block_table(self, index):
+        """-> (table float64 [grid_y * grid_x, 6] = lo_x, hi_x, lo_y, hi_y, cx, cy of block index_y * grid_x + index_x, grid_x, grid_y).
+        Every entry is formed in the file's dtype and widened exactly, so float64 comparisons on the device equal the reference's."""
+        coord_min, coord_max, grid_x, grid_y = self._grid(index)
+        table = np.array([[float(v) for v in self._bounds(coord_min, coord_max, ix, iy)] for iy in range(grid_y) for ix in range(grid_x)],
+                         dtype=np.float64)
+        return table, grid_x, grid_y
+
+    def __getitem__(self, index, rng=None):
+        """dataset.py:186-235 with np.random replaced by ``rng`` (a numpy.random.RandomState: ``RandomState(s)`` draws what ``np.random.seed(s)``
+        does) -> (data_room [blocks, block_points, 9], label_room, sample_weight, index_room [blocks, block_points])"""
+        rng = np.random if rng is None else rng
+        points = self.scene_points_list[index]
+        labels = self.semantic_labels_list[index]
+        coord_min, coord_max, grid_x, grid_y = self._grid(index)
+        data_room, label_room, sample_weight, index_room = [], [], [], []
+        for index_y in range(0, grid_y):
+            for index_x in range(0, grid_x):
+                lo_x, hi_x, lo_y, hi_y, cx, cy = self._bounds(coord_min, coord_max, index_x, index_y)
+                point_idxs = np.where((points[:, 0] >= lo_x) & (points[:, 0] <= hi_x) & (points[:, 1] >= lo_y) & (points[:, 1] <= hi_y))[0]
+                if point_idxs.size == 0:
+                    continue
+                num_batch = int(np.ceil(point_idxs.size / self.block_points))
+                point_size = int(num_batch * self.block_points)
+                replace = False if (point_size - point_idxs.size <= point_idxs.size) else True
+                point_idxs_repeat = rng.choice(point_idxs, point_size - point_idxs.size, replace=replace)
+                point_idxs = np.concatenate((point_idxs, point_idxs_repeat))
+                rng.shuffle(point_idxs)
+                data_batch = points[point_idxs, :]
+                normlized_xyz = np.zeros((point_size, 3))
+                normlized_xyz[:, 0] = data_batch[:, 0] / coord_max[0]
+                normlized_xyz[:, 1] = data_batch[:, 1] / coord_max[1]
+                normlized_xyz[:, 2] = data_batch[:, 2] / coord_max[2]
+                data_batch[:, 0] = data_batch[:, 0] - cx
+                data_batch[:, 1] = data_batch[:, 1] - cy
+                data_batch[:, 3:6] /= 255.0
+                data_room.append(np.concatenate((data_batch, normlized_xyz), axis=1))
+                label_batch = labels[point_idxs].astype(int)
+                label_room.append(label_batch)
+                sample_weight.append(self.labelweights[label_batch].astype(np.float64))   # the reference hstacks onto a float64 []
+                index_room.append(point_idxs)
+        data_room = np.concatenate(data_room)
+        return (data_room.reshape((-1, self.block_points, data_room.shape[1])), np.concatenate(label_room).reshape((-1, self.block_points)),
+                np.concatenate(sample_weight).reshape((-1, self.block_points)), np.concatenate(index_room).reshape((-1, self.block_points)))
+
+
+ScannetDatasetWholeScene = S3DISWholeScene
+
+
+def write_synthetic_rooms(root, num_rooms=8, seed=0, points_per_room=60000, test_area=5):
+    """``num_rooms`` synthetic rooms of SyntheticS3DIS's test split (the same generator, held out from its training rooms) written as
+    ``Area_<test_area>_synthetic_<i>.npy`` (xyzrgbl float32) under ``root``; -> the file names"""
+    os.makedirs(root, exist_ok=True)
+    gen = np.random.default_rng(seed + 1000)
+    names = []
+    for i in range(num_rooms):
+        name = 'Area_%d_synthetic_%d.npy' % (test_area, i)
+        np.save(os.path.join(root, name), synthetic_room(gen, points_per_room))
+        names.append(name)
+    return names
+
+
+class SyntheticS3DISWholeScene(S3DISWholeScene):
+    """write_synthetic_rooms into ``root``, then load them as S3DISWholeScene does"""
+
+    def __init__(self, root, block_points=4096, num_rooms=8, seed=0, points_per_room=60000, test_area=5, **kw):
+        write_synthetic_rooms(root, num_rooms, seed, points_per_room, test_area)
+        super().__init__(root, block_points, 'test', test_area, **kw)

@@ -6,6 +6,8 @@ allocator) and launches kernels of libact_hip.so on the current HIP stream.
 import ctypes
 import os
 
+import numpy as np
+
 import torch
 
 from . import _C
@@ -1673,3 +1675,77 @@ def __getattr__(name):
             return getattr(composite, name)
         return {"BlockFn": BlockFnPerKernel, "PrefixBlockFn": PrefixBlockFnPerKernel, "block_forward_prefix": block_forward_prefix_perkernel}[name]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+# ---- whole-room sliding-window testing (csrc/wholescene.hip): membership, keyed row build, gather, vote, finish -------------------------------
+def _i32c(t):
+    return t.to(torch.int32).contiguous()
+
+
+def scene_member_count(xyz, table, gx, gy):
+    """room xyz float64 [P,3], block table float64 [gy*gx,6] -> (counts int32 [gx*gy], offsets int32 [gx*gy+1], workspace) on the device"""
+    xyz, table = xyz.to(torch.float64).contiguous(), table.to(torch.float64).contiguous()
+    P, nblk = xyz.shape[0], gx * gy
+    if table.shape != (nblk, 6):
+        raise _C.ActHipError(f"scene membership: table {tuple(table.shape)} is not [{nblk}, 6]")
+    counts = torch.empty(nblk, dtype=torch.int32, device=xyz.device)
+    offsets = torch.empty(nblk + 1, dtype=torch.int32, device=xyz.device)
+    nbytes = lib.act_scene_member_workspace(P, gx, gy)
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=xyz.device)
+    check(lib.act_scene_member_count(ptr(xyz), P, ptr(table), gx, gy, ptr(counts), ptr(offsets), ptr(ws), ws.numel() * 4, stream()),
+          "act_scene_member_count")
+    return counts, offsets, ws
+
+
+def scene_member_fill(xyz, table, gx, gy, offsets, total, ws):
+    """-> members int32 [total]: block b's points at [offsets[b], offsets[b+1]) in increasing order (``total`` = sum of the counts, from the host)"""
+    xyz, table = xyz.to(torch.float64).contiguous(), table.to(torch.float64).contiguous()
+    members = torch.empty(max(int(total), 1), dtype=torch.int32, device=xyz.device)
+    check(lib.act_scene_member_fill(ptr(xyz), xyz.shape[0], ptr(table), gx, gy, ptr(offsets), ptr(members), ptr(ws), ws.numel() * 4, stream()),
+          "act_scene_member_fill")
+    return members[:int(total)]
+
+
+def scene_members(xyz, table, gx, gy):
+    """np.where of every block at once -> (counts numpy int64 [gx*gy] (the one host read), offsets int32 [gx*gy+1], members int32)"""
+    counts, offsets, ws = scene_member_count(xyz, table, gx, gy)
+    counts_h = counts.cpu().numpy().astype(np.int64)
+    return counts_h, offsets, scene_member_fill(xyz, table, gx, gy, offsets, counts_h.sum(), ws)
+
+
+def scene_rows(members, offsets, block_ids, row_off, R, block_points, seed, room, vote, out=None):
+    """keyed fill + shuffle of one vote -> rows int32 [R]; block_ids int32 [nb] (non-empty blocks), row_off int32 [nb+1] (device tensors)"""
+    nb = block_ids.numel()
+    rows = out if out is not None else torch.empty(R, dtype=torch.int32, device=members.device)
+    check(lib.act_scene_rows(ptr(members), ptr(offsets), ptr(block_ids), ptr(row_off), nb, R, block_points, seed & 0xFFFFFFFF, room & 0xFFFFFFFF,
+                             vote & 0xFFFFFFFF, ptr(rows), stream()), "act_scene_rows")
+    return rows
+
+
+def scene_gather(xyz, table, rows, block_ids, row_off, out=None):
+    """-> float32 [R,3]: (x - cx, y - cy, z) of every row's point with its block's centre (float64, one rounding)"""
+    R = rows.numel()
+    o = out if out is not None else torch.empty(R, 3, dtype=torch.float32, device=rows.device)
+    check(lib.act_scene_gather(ptr(xyz), xyz.shape[0], ptr(table), ptr(rows), ptr(block_ids), ptr(row_off), block_ids.numel(), R, ptr(o), stream()),
+          "act_scene_gather")
+    return o
+
+
+def scene_vote(logp, rows, label, labelweights, votes):
+    """votes int32 [P,C] += one vote per row of logp [n, C] (rows int32 [n]) at its arg-max, where the point's label weight is non-zero and
+    finite (main_test.py add_vote)"""
+    logp = _f32c(logp)
+    C = logp.shape[-1]
+    n = logp.numel() // C
+    check(lib.act_scene_vote(ptr(logp), ptr(rows), n, votes.shape[0], C, ptr(label), ptr(labelweights), ptr(votes), stream()), "act_scene_vote")
+    return votes
+
+
+def scene_finish(votes, label, cm=None):
+    """-> (pred int32 [P] = arg-max of the votes (ties: lowest class; none: 0), cm int64 [C,C] += (label, pred) counts)"""
+    P, C = votes.shape
+    if cm is None:
+        cm = torch.zeros(C, C, dtype=torch.int64, device=votes.device)
+    pred = torch.empty(P, dtype=torch.int32, device=votes.device)
+    check(lib.act_scene_finish(ptr(votes), ptr(label), P, C, ptr(pred), ptr(cm), stream()), "act_scene_finish")
+    return pred, cm

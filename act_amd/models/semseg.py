@@ -52,7 +52,7 @@ class PointNetFeaturePropagation(nn.Module):
         B, N, _ = xyz.shape
         G = center.shape[1]
         if nn3 is None:
-            nn3 = K.three_nn(xyz, center)
+            nn3 = K.three_nn(xyz, center, want_adj=torch.is_grad_enabled())    # the inverse adjacency serves the backward only
         pergroup = FP_PERGROUP if pergroup is None else pergroup
         xyz2 = xyz.reshape(B * N, 3).contiguous()
         c0 = self.mlp_convs[0]

@@ -592,6 +592,33 @@ int act_label_branch_bwd_f32(const float* cls, const float* W, const float* gamm
 int act_part_eval_f32(const float* logp, const int64_t* target, int B, int N, int P, const int32_t* part2cat, const int32_t* cat_first, int ncat,
                       int32_t* pred, int32_t* counts, int shape_offset, int num_shapes, int64_t* seen, int64_t* correct, act_stream_t stream);
 
+/* ---- whole-room sliding-window testing (S3DIS; csrc/wholescene.hip) ---------------------------------------------------------------
+ * semantic_segmentation/main_test.py with dataset.py ScannetDatasetWholeScene.  xyz float64 [P,3] (the room, promoted exactly from a float32
+ * file); table float64 [gy*gx, 6] = lo_x, hi_x, lo_y, hi_y, cx, cy of block iy*gx + ix, computed on the host in the file's dtype.
+ * Membership: point p is in block b iff lo_x <= x <= hi_x && lo_y <= y <= hi_y (the reference's np.where), lists in increasing point order.
+ * member_count: counts int32 [gx*gy], offsets int32 [gx*gy + 1] (exclusive scan); ws of act_scene_member_workspace bytes, kept for
+ * member_fill, which writes members int32 [offsets[gx*gy]] (block b at [offsets[b], offsets[b+1])).  P <= 2^27, gx*gy <= 2^20. */
+size_t act_scene_member_workspace(long long P, int gx, int gy);
+int act_scene_member_count(const double* xyz, long long P, const double* table, int gx, int gy, int32_t* counts, int32_t* offsets, void* ws,
+                           size_t ws_bytes, act_stream_t stream);
+int act_scene_member_fill(const double* xyz, long long P, const double* table, int gx, int gy, const int32_t* offsets, int32_t* members, void* ws,
+                          size_t ws_bytes, act_stream_t stream);
+/* keyed row-index build of one vote: rows int32 [R]; nb non-empty blocks block_ids[s] (grid index, count > 0), block s at rows
+ * [row_off[s], row_off[s+1]) (point_size = ceil(count / block_points) * block_points).  Fill (point_size - count draws from the members,
+ * without replacement when that is <= count) and shuffle are counter-based functions of (seed, room, vote, block) (csrc/wholescene.hip). */
+int act_scene_rows(const int32_t* members, const int32_t* member_off, const int32_t* block_ids, const int32_t* row_off, int nb, long long R,
+                   int block_points, unsigned seed, unsigned room, unsigned vote, int32_t* rows, act_stream_t stream);
+/* out float32 [R,3] = (x - cx, y - cy, z) of point rows[r] with its block's centre, in float64 and rounded once (rows outside [0,P): NaN) */
+int act_scene_gather(const double* xyz, long long P, const double* table, const int32_t* rows, const int32_t* block_ids, const int32_t* row_off,
+                     int nb, long long R, float* out, act_stream_t stream);
+/* votes int32 [P,C] += 1 at (rows[r], arg-max of logp[r, :]) for r < n (ties: the first maximum; a NaN wins) when labelweights[label[point]]
+ * is non-zero and not infinite (main_test.py add_vote); rows outside [0,P) and labels outside [0,C) do not vote.  C <= 64. */
+int act_scene_vote(const float* logp, const int32_t* rows, long long n, long long P, int C, const int32_t* label, const float* labelweights,
+                   int32_t* votes, act_stream_t stream);
+/* pred int32 [P] = arg-max of votes[p, :] (ties: lowest class; no votes: 0); cm int64 [C,C] (may be NULL) += (label, pred) counts, labels
+ * outside [0,C) skipped.  C <= 64. */
+int act_scene_finish(const int32_t* votes, const int32_t* label, long long P, int C, int32_t* pred, int64_t* cm, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
