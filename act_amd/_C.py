@@ -54,6 +54,8 @@ SIGNATURES = {
     "act_scene_gather": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp],
     "act_scene_vote": [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp],
     "act_scene_finish": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
+    # Stage-I reconstruction evaluation (csrc/recon_eval.hip)
+    "act_recon_eval_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _vp],
 }
 _RESTYPE = {"act_arch": ctypes.c_char_p, "act_prof_kernel_name": ctypes.c_char_p, "act_fps_scratch_floats": ctypes.c_size_t,
             "act_scene_member_workspace": ctypes.c_size_t}

@@ -53,6 +53,7 @@ class ShapeNet(data.Dataset):
         if self.synthetic:
             self.num = int(config.get("NUM_SAMPLES", 4096))
             self.seed = 1234 + (0 if self.subset == "train" else 1)
+            self.num_taxonomies = int(config.get("NUM_TAXONOMIES", 0))          # opt-in: spread the samples over that many taxonomy ids
             return
         self.data_root, self.pc_path = config.DATA_PATH, config.PC_PATH
         list_file = os.path.join(self.data_root, f"{self.subset}.txt")
@@ -75,7 +76,8 @@ class ShapeNet(data.Dataset):
         if self.synthetic:
             g = np.random.RandomState((self.seed * 1000003 + idx) & 0x7FFFFFFF)
             pts = pc_norm(g.standard_normal((self.sample_points_num, 3))).astype(np.float32)
-            return "synthetic", f"{idx:06d}", torch.from_numpy(pts)
+            taxonomy = f"synthetic{idx % self.num_taxonomies:02d}" if self.num_taxonomies > 0 else "synthetic"
+            return taxonomy, f"{idx:06d}", torch.from_numpy(pts)
         sample = self.file_list[idx]
         pc = read_points(os.path.join(self.pc_path, sample["file_path"])).astype(np.float32)
         pc = pc[np.random.permutation(pc.shape[0])[:self.sample_points_num]]           # random subset without replacement

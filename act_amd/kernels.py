@@ -1749,3 +1749,27 @@ def scene_finish(votes, label, cm=None):
     pred = torch.empty(P, dtype=torch.int32, device=votes.device)
     check(lib.act_scene_finish(ptr(votes), ptr(label), P, C, ptr(pred), ptr(cm), stream()), "act_scene_finish")
     return pred, cm
+
+
+# ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip): four Chamfer losses, CDL1 / CDL2 with ignore_zeros, F-Score counts, one row per cloud ----
+RECON_FIELDS = 12
+(RECON_SPARSE_L1, RECON_SPARSE_L2, RECON_DENSE_L1, RECON_DENSE_L2, RECON_CDL1, RECON_CDL2, RECON_PRECISION_HITS, RECON_RECALL_HITS, RECON_FSCORE,
+ RECON_NZ_DENSE, RECON_NZ_GT) = range(11)
+
+
+def recon_eval(coarse, dense, gt, out, row0, th=0.01):
+    """coarse [B,nc,3], dense [B,nd,3], gt [B,N,3] float32 -> rows out[row0 : row0 + B] of the float64 [rows, RECON_FIELDS] device buffer ``out``
+    (field order: the RECON_* indices; values unscaled, see include/act_hip.h).  One launch; nothing outside those rows is written."""
+    for t in (coarse, dense, gt):
+        if not t.is_cuda:
+            raise _C.ActHipError("act_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != gt.shape[0]:
+            raise _C.ActHipError(f"recon_eval: expected float32 [B, n, 3] clouds of one batch size, got {tuple(t.shape)} {t.dtype}")
+    if not out.is_cuda or out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != RECON_FIELDS or not out.is_contiguous() \
+            or out.device != gt.device:
+        raise _C.ActHipError(f"recon_eval: out must be a contiguous float64 [rows, {RECON_FIELDS}] tensor on the clouds' device")
+    coarse, dense, gt = coarse.contiguous(), dense.contiguous(), gt.contiguous()
+    B = gt.shape[0]
+    check(lib.act_recon_eval_f32(ptr(coarse), ptr(dense), ptr(gt), B, coarse.shape[1], dense.shape[1], gt.shape[1], float(th), ptr(out), int(row0),
+                                 out.shape[0], stream()), "act_recon_eval_f32")
+    return out

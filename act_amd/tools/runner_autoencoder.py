@@ -2,11 +2,17 @@
 
 temperature: cosine 1 -> 0.0625 over ``temp.ntime`` iterations (:42-53); KL weight: 0 for the first 10k iterations, then
 cosine ``kldweight.start`` -> ``kldweight.target`` (:18-40); loss = recon (CD-L1 coarse + fine) + kld_weight * KL.
-Validation reports whole-cloud Chamfer L1/L2 x1000 (the reference additionally prints per-taxonomy tables and F-score,
-which need open3d and the ShapeNet taxonomy files: out of scope)."""
+``validate`` (the periodic validation of ``run_net``) reports whole-batch Chamfer L1/L2 x1000.
+
+Evaluation of a trained tokenizer (reference :219-420, ``main_autoencoder.py --val / --test``): ``evaluate`` / ``validate_net`` / ``test_net``
+below give the reference's full report -- the four per-sample losses, F-Score@0.01 / CDL1 / CDL2 per taxonomy and their macro average --
+from one ``kernels.recon_eval`` launch per batch and a single device->host read, without open3d."""
+import json
 import math
+import os
 import time
 
+import numpy as np
 import torch
 
 from . import builder
@@ -165,3 +171,214 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
         if max_steps is not None and steps >= max_steps:
             break
     return log
+
+
+# ---- evaluation of a trained tokenizer (reference :219-420) ------------------------------------------------------------------------------
+LOSS_NAMES = ['SparseLossL1', 'SparseLossL2', 'DenseLossL1', 'DenseLossL2']
+SYNSET_DICT = './data/shapenet_synset_dict.json'
+USEFUL_CATE = ["02691156", "02818832", "04379243", "04099429", "03948459", "03790512", "03642806", "03467517", "03261776", "03001627",
+               "02958343", "03759954"]
+
+
+def _tax(t):
+    return t if isinstance(t, str) else (t.item() if hasattr(t, "item") else t)
+
+
+def aggregate_rows(rows, taxonomy_ids):
+    """host part of the evaluation, float64: ``rows`` [n, RECON_FIELDS] as ``kernels.recon_eval`` wrote them, one taxonomy id per row ->
+    dict(losses = mean over samples of the four losses x1000, per_taxonomy = {id: (count, [F-Score, CDL1, CDL2])} in order of first
+    appearance, overall = mean over taxonomies of the per-taxonomy means (:282-283))"""
+    from .. import kernels as K
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, K.RECON_FIELDS)
+    if len(taxonomy_ids) != rows.shape[0]:
+        raise ValueError(f"{rows.shape[0]} rows for {len(taxonomy_ids)} taxonomy ids")
+    losses = [float(v) for v in rows[:, [K.RECON_SPARSE_L1, K.RECON_SPARSE_L2, K.RECON_DENSE_L1, K.RECON_DENSE_L2]].mean(axis=0) * 1000] \
+        if rows.shape[0] else [0.0] * 4
+    met = rows[:, [K.RECON_FSCORE, K.RECON_CDL1, K.RECON_CDL2]] * np.array([1.0, 1000.0, 1000.0])
+    members = {}
+    for i, t in enumerate(taxonomy_ids):
+        members.setdefault(t, []).append(i)
+    per = {t: (len(ix), [float(v) for v in met[ix].mean(axis=0)]) for t, ix in members.items()}
+    overall = [float(v) for v in np.mean([v for _, v in per.values()], axis=0)] if per else [0.0] * 3
+    return dict(losses=losses, per_taxonomy=per, overall=overall)
+
+
+def results_table(per_taxonomy, overall, names=None, synset=None):
+    """the reference's TEST RESULTS table (:292-314) as plain text: Taxonomy | #Sample | metrics | Category, a footing row 'Overall'"""
+    from ..utils.metrics import Metrics as FullMetrics
+    synset = synset or {}
+    table = [['Taxonomy', '#Sample'] + list(names or FullMetrics.names()) + ['Category']]
+    for t, (count, vals) in per_taxonomy.items():
+        table.append([str(t), str(count)] + ['%.3f' % v for v in vals] + [str(synset.get(t, t))])
+    table.append(['Overall', '--'] + ['%.3f' % v for v in overall] + ['--'])
+    width = [max(len(r[c]) for r in table) for c in range(len(table[0]))]
+    rule = '+' + '+'.join('-' * (w + 2) for w in width) + '+'
+    line = lambda r: '| ' + ' | '.join(v.ljust(w) for v, w in zip(r, width)) + ' |'
+    out = [rule, line(table[0]), rule] + [line(r) for r in table[1:-1]] + [rule, line(table[-1]), rule]
+    return '\n'.join(out)
+
+
+def _synset_names():
+    if os.path.exists(SYNSET_DICT):
+        with open(SYNSET_DICT) as f:
+            return json.load(f)
+    return {}
+
+
+def gumbel_noise(module, sample_ids, seed, device):
+    """[B, num_group, num_tokens] gumbel noise, sample i from its own generator state (seed, i): the draw of a cloud does not depend on the
+    batch it is evaluated in, and two passes agree bit for bit"""
+    gen = torch.Generator(device=device)
+    u = torch.empty(len(sample_ids), module.num_group, module.num_tokens, dtype=torch.float32, device=device)
+    for r, i in enumerate(sample_ids):
+        gen.manual_seed(((int(seed) & 0x7FFFFFFF) << 32) | (int(i) & 0xFFFFFFFF))          # distinct for every (seed, i) below 2^31 / 2^32
+        u[r].exponential_(generator=gen)
+    return -u.log()
+
+
+@torch.no_grad()
+def eval_batch(module, points, out, row0, seed=0, th=0.01):
+    """the per-batch part of ``evaluate`` (no host synchronisation): eval-mode forward with ``hard=True`` on device-resident ``points``
+    [B,N,3], rows [row0, row0 + B) of ``out`` from one ``kernels.recon_eval`` launch.  Returns the model's output tuple."""
+    from .. import kernels as K
+    from ..utils.draws import Draws
+    B = points.shape[0]
+    noise = gumbel_noise(module, range(row0, row0 + B), seed, points.device)
+    ret = module(points, temperature=1., hard=True, draws=Draws({"gumbel": noise}))
+    K.recon_eval(ret[0], ret[1], points, out, row0, th)
+    return ret
+
+
+@torch.no_grad()
+def evaluate(base_model, test_dataloader, epoch, args, config, logger=None, val_writer=None, batch_size=None, seed=0, max_batches=None):
+    """the reference's ``validate`` (:219-323) with batched forwards: the model runs in eval mode with ``hard=True`` (every layer is per-sample
+    there), the gumbel noise of sample i is a function of (seed, i), each batch is one ``kernels.recon_eval`` launch into a
+    [len(dataset), RECON_FIELDS] device buffer, and that buffer is read ONCE after the last batch; the averages are taken in float64 on the
+    host.  ``batch_size``: None keeps the loader's, else the loader's dataset is walked in that batch size.
+
+    Returns ``utils.metrics.Metrics(config.consider_metric, overall)``, overall = mean over taxonomies of the per-taxonomy means.  The details
+    ride on the returned object as attributes: ``per_taxonomy`` {id: (count, [F-Score, CDL1, CDL2])}, ``losses`` (the four mean losses x1000),
+    ``rows`` (float64 ndarray [samples, RECON_FIELDS]) and ``taxonomy_ids`` / ``model_ids`` (one per row)."""
+    from .. import kernels as K
+    from ..utils.metrics import Metrics as FullMetrics
+    print_log(f"[VALIDATION] Start validating epoch {epoch}", logger=logger)
+    base_model.eval()
+    module = builder._unwrap(base_model)
+    device = next(module.parameters()).device
+    if batch_size is not None and batch_size != test_dataloader.batch_size:
+        test_dataloader = torch.utils.data.DataLoader(test_dataloader.dataset, batch_size=int(batch_size), shuffle=False, drop_last=False,
+                                                      num_workers=int(getattr(args, "num_workers", 0)), pin_memory=True)
+    section = config.dataset.get('test', None) or config.dataset.val
+    if section._base_.NAME != 'ShapeNet':
+        raise NotImplementedError(f'Train phase do not support {section._base_.NAME}')
+    n_samples = len(test_dataloader.dataset)
+    out = torch.zeros(n_samples, K.RECON_FIELDS, dtype=torch.float64, device=device)
+    taxonomy_ids, model_ids, row0 = [], [], 0
+    for idx, (tax, mids, data) in enumerate(test_dataloader):
+        points = data.to(device, non_blocking=True)
+        eval_batch(module, points, out, row0, seed)
+        taxonomy_ids += [_tax(t) for t in tax]
+        model_ids += [_tax(m) for m in mids]
+        row0 += points.shape[0]
+        if max_batches is not None and idx + 1 >= max_batches:
+            break
+    rows = out[:row0].cpu().numpy()                                   # the one device -> host read
+    agg = aggregate_rows(rows, taxonomy_ids)
+    for i in range(1999, row0, 2000):
+        r = rows[i]
+        print_log('Test[%d/%d] Taxonomy = %s Sample = %s Losses = %s Metrics = %s' %
+                  (i + 1, n_samples, taxonomy_ids[i], model_ids[i], ['%.4f' % (l * 1000) for l in r[:4]],
+                   ['%.4f' % m for m in (r[K.RECON_FSCORE], r[K.RECON_CDL1] * 1000, r[K.RECON_CDL2] * 1000)]), logger=logger)
+    print_log('[Validation] EPOCH: %d  Metrics = %s' % (epoch, ['%.4f' % m for m in agg["overall"]]), logger=logger)
+    print_log('============================ TEST RESULTS ============================', logger=logger)
+    print_log('\n' + results_table(agg["per_taxonomy"], agg["overall"], FullMetrics.names(), _synset_names()), logger=logger)
+    if val_writer is not None:
+        val_writer.add_scalar('Loss/Epoch/Sparse', agg["losses"][0], epoch)
+        val_writer.add_scalar('Loss/Epoch/Dense', agg["losses"][2], epoch)
+        for name, v in zip(FullMetrics.names(), agg["overall"]):
+            val_writer.add_scalar('Metric/%s' % name, v, epoch)
+    m = FullMetrics(config.consider_metric, list(agg["overall"]))
+    m.per_taxonomy, m.losses, m.rows, m.taxonomy_ids, m.model_ids = agg["per_taxonomy"], agg["losses"], rows, taxonomy_ids, model_ids
+    return m
+
+
+def _load_for_test(args, config, logger):
+    print_log('Tester start ... ', logger=logger)
+    if args.distributed:
+        raise NotImplementedError()
+    _, test_dataloader = builder.dataset_builder(args, config.dataset.test)
+    base_model = builder.model_builder(config.model)
+    builder.load_model(base_model, args.ckpts, logger=logger)
+    if args.use_gpu:
+        device = torch.device("cuda", args.local_rank % max(1, torch.cuda.device_count()))
+        torch.cuda.set_device(device)
+        base_model.to(device)
+    return base_model, test_dataloader
+
+
+def validate_net(args, config):
+    """evaluate the checkpoint ``args.ckpts`` on ``config.dataset.test`` (reference :325-344); returns what ``evaluate`` returns"""
+    logger = get_logger(args.log_name)
+    base_model, test_dataloader = _load_for_test(args, config, logger)
+    return evaluate(base_model, test_dataloader, 0, args, config, logger=logger)
+
+
+def _plot(path, gt, dense):
+    """gt | reconstruction scatter plot; returns False when matplotlib is not installed"""
+    try:
+        from matplotlib.figure import Figure
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+    except ImportError:
+        return False
+    fig = Figure(figsize=(8, 4))
+    FigureCanvasAgg(fig)
+    for k, (pts, title) in enumerate(((gt, 'gt'), (dense, 'dense'))):
+        ax = fig.add_subplot(1, 2, k + 1, projection='3d')
+        ax.scatter(pts[:, 0], pts[:, 2], pts[:, 1], s=1, c=pts[:, 0], cmap='jet')
+        ax.set_axis_off()
+        ax.set_title(title)
+    fig.savefig(path)
+    return True
+
+
+@torch.no_grad()
+def test(base_model, test_dataloader, args, config, logger=None, target='./vis', seed=0):
+    """reference :363-420: for the clouds of ``USEFUL_CATE``, write ``<target>/<taxonomy>_<idx>/gt.txt`` and ``dense_points.txt``
+    (np.savetxt, delimiter ';') and ``plot.png`` when matplotlib imports; idx is the sample's index in the loader's order, and the walk
+    stops after the first written sample with idx > 1000.  Returns the directories written."""
+    from ..utils.draws import Draws
+    base_model.eval()
+    module = builder._unwrap(base_model)
+    device = next(module.parameters()).device
+    if config.dataset.test._base_.NAME != 'ShapeNet':
+        raise NotImplementedError(f'Train phase do not support {config.dataset.test._base_.NAME}')
+    written, row0 = [], 0
+    for tax, _, data in test_dataloader:
+        B = data.shape[0]
+        tax = [_tax(t) for t in tax]
+        if any(t in USEFUL_CATE for t in tax):
+            points = data.to(device)
+            noise = gumbel_noise(module, range(row0, row0 + B), seed, device)
+            dense = module(points, temperature=1., hard=True, draws=Draws({"gumbel": noise}))[1].cpu().numpy()
+            gt = points.cpu().numpy()
+            for r in range(B):
+                if tax[r] not in USEFUL_CATE:
+                    continue
+                idx = row0 + r
+                data_path = os.path.join(target, f'{tax[r]}_{idx}')
+                os.makedirs(data_path, exist_ok=True)
+                np.savetxt(os.path.join(data_path, 'gt.txt'), gt[r], delimiter=';')
+                np.savetxt(os.path.join(data_path, 'dense_points.txt'), dense[r], delimiter=';')
+                _plot(os.path.join(data_path, 'plot.png'), gt[r], dense[r])
+                written.append(data_path)
+                if idx > 1000:
+                    return written
+        row0 += B
+    return written
+
+
+def test_net(args, config, target='./vis'):
+    """write the reconstructions of the checkpoint ``args.ckpts`` for the reference's category list (reference :346-361)"""
+    logger = get_logger(args.log_name)
+    base_model, test_dataloader = _load_for_test(args, config, logger)
+    return test(base_model, test_dataloader, args, config, logger=logger, target=target)

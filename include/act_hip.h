@@ -619,6 +619,23 @@ int act_scene_vote(const float* logp, const int32_t* rows, long long n, long lon
  * outside [0,C) skipped.  C <= 64. */
 int act_scene_finish(const int32_t* votes, const int32_t* label, long long P, int C, int32_t* pred, int64_t* cm, act_stream_t stream);
 
+/* ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip) ------------------------------------------------------------------------
+ * tools/runner_autoencoder.py:219-323 (validate) with utils/metrics.py, one launch per batch, one workgroup per cloud: coarse [B,nc,3],
+ * dense [B,nd,3], gt [B,N,3] -> row row0 + b of out (float64 [num_rows, ACT_RECON_FIELDS]):
+ *   [0] sparse L1  [1] sparse L2   ChamferDistanceL1 / L2 (coarse, gt) of that one cloud: L1 = (mean sqrt d1 + mean sqrt d2) / 2, L2 = mean d1 + mean d2
+ *   [2] dense L1   [3] dense L2    the same for dense
+ *   [4] CDL1       [5] CDL2        (dense, gt) with ignore_zeros at batch size 1: points whose fp32 (x + y) + z == 0 are neither queries nor
+ *                                  candidates, the means divide by the counts that remain; NaN when either cloud has no point left
+ *   [6] precision hits  [7] recall hits   dense points whose nearest gt point / gt points whose nearest dense point is closer than th (all points)
+ *   [8] F-Score = 2 r p / (r + p), 0 when r + p == 0     [9] non-zero dense points  [10] non-zero gt points  [11] 0
+ * Values are NOT scaled by 1000.  Squared distances are fp32 with every product and sum rounded (the per-point minima are those of
+ * act_chamfer_fwd_f32, lowest index on ties); sums are float64 in a fixed order (bit-identical run to run, no atomics); the threshold is
+ * applied to the float64 distance between the query and the selected neighbour.  Clouds that fit in LDS are staged once; larger ones are
+ * tiled.  B == 0 is a no-op; rows outside [row0, row0 + B) are not touched. */
+#define ACT_RECON_FIELDS 12
+int act_recon_eval_f32(const float* coarse, const float* dense, const float* gt, int B, int nc, int nd, int N, float th, double* out, int row0,
+                       int num_rows, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
