@@ -9,11 +9,10 @@ import os
 
 import torch
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ACT_LIB_PATH") or os.path.join(_HERE, "lib", "libact_hip.so")      # (ACT_LIB_PATH: A/B builds of the same ABI)
-
-_vp, _i, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-_f = ctypes.c_float
 
 
 def _load():
@@ -26,52 +25,11 @@ def _load():
 
 lib = _load()
 
-# name -> argtypes   (every function returns int unless listed in _RESTYPE)
-SIGNATURES = {
-    "act_version": [],
-    "act_arch": [],
-    "act_prof_enable": [_i],
-    "act_prof_reset": [],
-    "act_prof_num_kernels": [],
-    "act_prof_kernel_name": [_i],
-    "act_prof_read": [_i, _vp, _vp, _vp, _vp],
-    "act_fps_scratch_floats": [_i, _i],
-    "act_fps_f32": [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
-    "act_fps_chain_probe": [_i, _i, _vp, _vp, _vp, _vp],
-    "act_knn_group_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp],
-    "act_gather_points_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_gather_points_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_scale_translate_f32": [_vp, _vp, _vp, _i, _i, _vp],
-    "act_rotate_points_f32": [_vp, _vp, _i, _i, _vp],
-    "act_chamfer_fwd_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "act_chamfer_fwd_ex_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "act_chamfer_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    # whole-room sliding-window testing (csrc/wholescene.hip)
-    "act_scene_member_workspace": [_ll, _i, _i],
-    "act_scene_member_count": [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp],
-    "act_scene_member_fill": [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp],
-    "act_scene_rows": [_vp, _vp, _vp, _vp, _i, _ll, _i, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, _vp, _vp],
-    "act_scene_gather": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp],
-    "act_scene_vote": [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp],
-    "act_scene_finish": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
-    # Stage-I reconstruction evaluation (csrc/recon_eval.hip)
-    "act_recon_eval_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _vp],
-}
-_RESTYPE = {"act_arch": ctypes.c_char_p, "act_prof_kernel_name": ctypes.c_char_p, "act_fps_scratch_floats": ctypes.c_size_t,
-            "act_scene_member_workspace": ctypes.c_size_t}
-
-
-def _declare(extra=None):
-    sigs = dict(SIGNATURES)
-    if extra:
-        sigs.update(extra)
-    for name, args in sigs.items():
-        fn = getattr(lib, name)          # AttributeError here == symbol missing from the build
-        fn.argtypes = args
-        fn.restype = _RESTYPE.get(name, _i)
-
-
-_declare()
+# the whole header, declared once: name -> (restype, argtypes)   (AttributeError here == symbol missing from the build)
+SIGNATURES = _abi.SIGNATURES
+for _name, (_restype, _argtypes) in SIGNATURES.items():
+    _fn = getattr(lib, _name)
+    _fn.restype, _fn.argtypes = _restype, _argtypes
 
 
 class ActHipError(RuntimeError):

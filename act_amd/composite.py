@@ -7,8 +7,8 @@ scratch slab per backward, fills a small parameter struct with device pointers a
 
 GEMM launch configurations: the C side looks every GEMM up in a table keyed by (layout, M, N, K).  Before the first execution of a
 composite with given dimensions the shapes it will launch are collected (act_composite_collect_begin/_end: the call runs without
-launching anything), tuned exactly like the single-GEMM path (shipped table, else first-use timing) and registered, so results never
-depend on the call history.
+launching anything), decided by the function the single-GEMM path asks (kernels.gemm_config: shipped table, else first-use timing) and
+registered, so results never depend on the call history.
 """
 import ctypes
 import os
@@ -18,105 +18,13 @@ import torch
 
 from . import _C
 from . import kernels as K
+from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3
+from ._abi import GemmFx          # noqa: F401  (tests and benchmarks build it as CP.GemmFx)
 
-_vp, _i, _f, _sz, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64
 lib, check = _C.lib, _C.check
+_vp, _i = ctypes.c_void_p, ctypes.c_int
 
 ENABLED = os.environ.get("ACT_COMPOSITE", "1") != "0"       # 0: the one-call-per-kernel host path (A/B measurements, bit-identity test)
-
-
-class BlockParams(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b",
-                                   "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
-
-
-class BlockDims(ctypes.Structure):
-    _fields_ = [("B", _i), ("S", _i), ("D", _i), ("heads", _i), ("hidden", _i), ("eps", _f)]
-
-
-class BlockStack(ctypes.Structure):
-    _fields_ = [("depth", _i), ("blocks", _vp), ("gate1", _vp), ("gate2", _vp)]
-
-
-class PrefixVit(ctypes.Structure):
-    _fields_ = ([(n, _i) for n in ("B", "P", "G", "D", "heads", "hidden", "depth", "tokens_dims", "pos_hidden")] +
-                [("eps", _f), ("drop_p", _f), ("seed_base", _u64), ("seed_dev", _vp)] +
-                [(n, _vp) for n in ("pos_w0", "pos_b0", "pos_w1", "pos_b1", "pre_w", "pre_b", "post_w", "post_b", "norm_w", "norm_b")] +
-                [("prompt_tok", ctypes.POINTER(_vp)), ("prompt_pos", ctypes.POINTER(_vp)), ("blocks", ctypes.POINTER(BlockParams))])
-
-
-class VitBf16x3(ctypes.Structure):
-    _fields_ = [("w_planes", _vp), ("a_planes", _vp), ("a_planes_elems", _sz)]
-
-
-class PointnetParams(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ("c1_w", "c1_b", "bn1_w", "bn1_b", "c2_w", "c2_b", "c3_w", "c3_b", "bn2_w", "bn2_b", "c4_w", "c4_b",
-                                   "bn1_mean", "bn1_var", "bn2_mean", "bn2_var")]
-
-
-class PointnetGrads(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ("c1_w", "c1_b", "bn1_w", "bn1_b", "c2_w", "c2_b", "c3_w", "c3_b", "bn2_w", "bn2_b", "c4_w", "c4_b")]
-
-
-class PointnetDims(ctypes.Structure):
-    _fields_ = [("BG", _i), ("n", _i), ("C", _i), ("eps1", _f), ("eps2", _f), ("momentum1", _f), ("momentum2", _f)]
-
-
-class Dgcnn(ctypes.Structure):
-    _fields_ = ([(n, _i) for n in ("B", "G", "k", "Cin", "Cout", "groups")] + [("eps", _f), ("slope", _f)] +
-                [(n, _vp) for n in ("w_in", "b_in", "w5")] + [("stacked", _vp * 4), ("gn_w", _vp * 4), ("gn_b", _vp * 4)])
-
-
-class GemmFx(ctypes.Structure):
-    _fields_ = ([(n, _vp) for n in ("a_scale", "a_shift", "b_scale", "b_shift", "tile_stats", "gmax", "garg")] + [("group", _i), ("store_c", _i)]
-                + [(n, _vp) for n in ("sa_src", "sa_arg", "ep_src", "ep_arg", "row_groups")])
-
-
-_P = ctypes.POINTER
-_SIGS = {
-    "act_sgemm_fx_tile_stats_floats": [_i, _i],
-    "act_sgemm_fx_f32": [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _P(K.GemmEpilogue), _P(GemmFx), _vp, _sz, _vp],
-    "act_bn_tiles_finalize_f32": [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "act_gemm_tune_set": [_i] * 7,
-    "act_gemm_tune_get": [_i] * 5 + [_P(_i), _P(_i)],
-    "act_gemm_tune_clear": [],
-    "act_gemm_fx_asm": [_i],
-    "act_composite_collect_begin": [],
-    "act_composite_collect_end": [_P(_i), _i],
-    "act_composite_shutdown": [],
-    "act_scale_rows_f32": [_vp, _vp, _i, _i, _i, _vp, _vp],
-    "act_bn_eval_affine_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
-    "act_block_saved_floats": [_P(BlockDims)],
-    "act_block_bwd_scratch_floats": [_P(BlockDims)],
-    "act_block_fwd_f32": [_P(BlockDims), _P(BlockParams), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_block_bwd_f32": [_P(BlockDims), _P(BlockParams), _vp, _vp, _vp, _vp, _vp, _P(BlockParams), _vp, _vp, _sz, _vp, _sz, _vp, _vp],
-    "act_block_stack_saved_floats": [_P(BlockDims), _i, _i],
-    "act_block_stack_bwd_scratch_floats": [_P(BlockDims), _i],
-    "act_block_stack_fwd_f32": [_P(BlockDims), _P(BlockStack), _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_block_stack_bwd_f32": [_P(BlockDims), _P(BlockStack), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp],
-    "act_add_f32": [_vp, _vp, _vp, ctypes.c_longlong, _vp],
-    "act_prefix_block_saved_floats": [_P(BlockDims), _i],
-    "act_prefix_block_bwd_scratch_floats": [_P(BlockDims), _i],
-    "act_prefix_block_fwd_f32": [_P(BlockDims), _i, _P(BlockParams), _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_prefix_block_fwd_bf16x3_f32": [_P(BlockDims), _i, _P(BlockParams), _P(VitBf16x3), _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_prefix_block_bwd_bf16x3_f32": [_P(BlockDims), _i, _P(BlockParams), _P(VitBf16x3), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_prefix_block_bwd_f32": [_P(BlockDims), _i, _P(BlockParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_prefix_vit_scratch_floats": [_P(PrefixVit)],
-    "act_prefix_vit_fwd_f32": [_P(PrefixVit), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_prefix_vit_fwd_bf16x3_f32": [_P(PrefixVit), _P(VitBf16x3), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_pointnet_saved_floats": [_P(PointnetDims)],
-    "act_pointnet_bwd_scratch_floats": [_P(PointnetDims)],
-    "act_pointnet_fwd_f32": [_P(PointnetDims), _P(PointnetParams), _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_pointnet_fwd_groups_f32": [_P(PointnetDims), _P(PointnetParams), _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp],
-    "act_pointnet_bwd_f32": [_P(PointnetDims), _P(PointnetParams), _vp, _vp, _vp, _P(PointnetGrads), _vp, _vp, _sz, _vp],
-    "act_dgcnn_scratch_floats": [_P(Dgcnn)],
-    "act_dgcnn_features_f32": [_P(Dgcnn), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-}
-_C._declare(_SIGS)
-for _n in _SIGS:
-    _C.SIGNATURES.setdefault(_n, getattr(lib, _n).argtypes)
-    if _n.endswith("_floats"):
-        getattr(lib, _n).restype = _sz
 
 
 def _p(t):
@@ -129,44 +37,16 @@ def _p(t):
     return t.data_ptr()
 
 
-def _ws_of(device, stream_handle):
-    """split-K / reduction scratch of one stream (kernels of different streams run concurrently)"""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, stream_handle)
-    w = K._WS.get(key)
-    if w is None:
-        w = K._WS[key] = torch.empty(K._WS_BYTES // 4, dtype=torch.float32, device=device)
-    return w
-
-
 # ---- tuning bridge ------------------------------------------------------------------------------------------------------
-for (_ak, _bk, _M, _N, _K), (_tile, _sp) in K._GEMM_TABLE.items():
-    lib.act_gemm_tune_set(_ak, _bk, _M, _N, _K, _tile, _sp)
+K.publish_table()
 _TUNED = set()
 _SHAPE_BUF = (_i * (5 * 256))()
 
 
 def _tune_shape(ak, bk, M, N, Kd, device):
-    """the decision K._gemm_config would take for this product, registered with the C-side table; False when the shape could not be tuned
-    right now (stream capture in progress) and has to be looked at again"""
-    if lib.act_gemm_tune_get(ak, bk, M, N, Kd, None, None) == 0:
-        return True
-    if not K.AUTOTUNE or M * N * Kd < (1 << 24) or (not ak and not bk and min(M, N) <= 8):
-        return True                                             # built-in cost model / skinny streaming kernel (tile 0)
-    key = (int(ak), int(bk), M, N, Kd, device.index)
-    cfg = K._GEMM_CACHE.get(key)                                # (0, 0) -- the cost model's pick -- is a valid cached decision: no `or`
-    if cfg is None:
-        cfg = K._GEMM_TABLE.get(key[:5])
-    if cfg is None:
-        if torch.cuda.is_current_stream_capturing():
-            return False
-        a = torch.randn((M, Kd) if ak else (Kd, M), dtype=torch.float32, device=device)
-        b = torch.randn((N, Kd) if bk else (Kd, N), dtype=torch.float32, device=device)
-        cfg = K.first_use_config(a, b, ak, bk, M, N, Kd, K.workspace(device))
-        K._NEW_TUNED[key[:5]] = cfg
-    K._GEMM_CACHE[key] = cfg
-    lib.act_gemm_tune_set(ak, bk, M, N, Kd, int(cfg[0]), int(cfg[1]))
-    return True
+    """K.gemm_config's decision for this product in the C-side table (unless the table already has one); False when the shape could not be
+    decided right now (stream capture in progress) and has to be looked at again"""
+    return lib.act_gemm_tune_get(ak, bk, M, N, Kd, None, None) == 0 or K.gemm_config(ak, bk, M, N, Kd, device, publish=True) is not None
 
 
 def ensure_tuned(key, call, device):
@@ -186,17 +66,11 @@ def ensure_tuned(key, call, device):
         _TUNED.add(key)
 
 
-def register_tuned(ak, bk, M, N, Kd, cfg):
-    """called by the single-GEMM autotuner (kernels._gemm_config) so both host paths launch the same configuration"""
-    lib.act_gemm_tune_set(int(ak), int(bk), M, N, Kd, int(cfg[0]), int(cfg[1]))
-
-
 def reset_tuning():
     """forget every first-use decision (tests that need identical configurations across processes)"""
     _TUNED.clear()
     lib.act_gemm_tune_clear()
-    for (ak, bk, M, N, Kd), (tile, sp) in K._GEMM_TABLE.items():
-        lib.act_gemm_tune_set(ak, bk, M, N, Kd, tile, sp)
+    K.publish_table()
 
 
 def shutdown():
@@ -275,7 +149,7 @@ class BlockFn(torch.autograd.Function):
         side, sws = None, None
         if tw == 2 and K.OVERLAP_DW:
             side = K.side_stream(dev, 1).cuda_stream
-            sws = _ws_of(dev, side)
+            sws = K.workspace(dev, stream_handle=side)
         args = (ctypes.byref(dims), ctypes.byref(prm), _p(gate1), _p(gate2), _p(saved), _p(dout), _p(dx), gp, _p(scratch),
                 _p(ws), ws.numel() * 4, _p(sws), (sws.numel() * 4 if sws is not None else 0))
         ensure_tuned(("blk_bwd", B, S, D, heads, hidden, bool(tw)), lambda: lib.act_block_bwd_f32(*args, _C.stream(), side), dev)
@@ -398,7 +272,7 @@ class BlockStackFn(torch.autograd.Function):
         side, sws = None, None
         if tw == 2 and K.OVERLAP_DW:
             side = K.side_stream(dev, 1).cuda_stream
-            sws = _ws_of(dev, side)
+            sws = K.workspace(dev, stream_handle=side)
         args = (ctypes.byref(dims), ctypes.byref(st), saved.data_ptr(), dout.data_ptr(), dx.data_ptr(), dpos.data_ptr() if dpos is not None else None,
                 dpos_in.data_ptr() if (dpos_in is not None and dpos is not None) else None,
                 ctypes.cast(garr, _vp) if garr is not None else None, scratch.data_ptr(), ws.data_ptr(), ws.numel() * 4,
@@ -622,7 +496,7 @@ def prefix_vit_forward(tok, tokens, center, drop_p, seed_base, seed_dev):
         toks = (_vp * depth)(*[ptr[nb] if i == 0 else ptr[nb + 2] + (i - 1) * row for i in range(depth)])
         poss = (_vp * depth)(*[ptr[nb + 1] if i == 0 else ptr[nb + 3] + (i - 1) * row for i in range(depth)])
         blks = (_vp * (_NPB * depth))(*[ptr[10 + i] for i in range(_NPB * depth)])
-        m.prompt_tok, m.prompt_pos, m.blocks = toks, poss, ctypes.cast(blks, _P(BlockParams))
+        m.prompt_tok, m.prompt_pos, m.blocks = toks, poss, ctypes.cast(blks, ctypes.POINTER(BlockParams))
         n_scratch = int(lib.act_prefix_vit_scratch_floats(ctypes.byref(m)))
         cache = _VIT_STRUCT[tok] = (sig, m, n_scratch, (toks, poss, blks, ptr))
     _, m, n_scratch, _ = cache

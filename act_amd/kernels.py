@@ -11,65 +11,21 @@ import numpy as np
 import torch
 
 from . import _C
-
-_vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+from ._abi import GemmEpilogue, GemmTnProblem          # (declared with the rest of the C ABI; built here and by tests / benchmarks as K.*)
 
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_MUL_GELU_GRAD, EPI_MUL_RELU_MASK = 0, 1, 2, 3, 4
 
-
-class GemmEpilogue(ctypes.Structure):
-    _fields_ = [("alpha", _f), ("act", _i), ("accumulate", _i), ("rows_per_scale", _i), ("ldr", _i), ("ldaux", _i),
-                ("res_row_div", _i), ("bias", _vp), ("rowscale", _vp), ("res", _vp), ("aux", _vp)]
-
-
-_C._declare({
-    "act_sgemm_f32": [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(GemmEpilogue), _vp, _sz, _vp],
-    "act_sgemm_ex_f32": [_i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(GemmEpilogue), _vp, _sz, _i, _i, _vp],
-    "act_layernorm_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
-    "act_layernorm_bwd_workspace": [_i, _i],
-    "act_layernorm_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _i, _vp],
-    "act_colsum_workspace": [_i, _i],
-    "act_colsum_f32": [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp],
-    "act_attention_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "act_attention_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    "act_cosine_loss_fwd_f32": [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp],
-    "act_cosine_loss_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp],
-    "act_regression_loss_fwd_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "act_regression_loss_bwd_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "act_softmax_xent_fwd_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
-    "act_softmax_xent_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
-})
-_C.lib.act_layernorm_bwd_workspace.restype = _sz
-_C.lib.act_colsum_workspace.restype = _sz
-for _n in ("act_sgemm_f32", "act_sgemm_ex_f32", "act_layernorm_fwd_f32", "act_layernorm_bwd_workspace", "act_layernorm_bwd_f32",
-           "act_colsum_workspace", "act_colsum_f32", "act_attention_fwd_f32", "act_attention_bwd_f32",
-           "act_cosine_loss_fwd_f32", "act_cosine_loss_bwd_f32", "act_softmax_xent_fwd_f32", "act_softmax_xent_bwd_f32",
-           "act_regression_loss_fwd_f32", "act_regression_loss_bwd_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
 lib, ptr, stream, check = _C.lib, _C.ptr, _C.stream, _C.check
 
-
-class GemmTnProblem(ctypes.Structure):                 # act_gemm_tn_problem_t
-    _fields_ = [("A", _vp), ("lda", _i), ("B", _vp), ("ldb", _i), ("C", _vp), ("ldc", _i), ("M", _i), ("N", _i), ("bias_out", _vp)]
-
-
-_C._declare({"act_sgemm_tn_grouped_workspace": [ctypes.POINTER(GemmTnProblem), _i, _i, _i],
-             "act_sgemm_tn_grouped_splits": [ctypes.POINTER(GemmTnProblem), _i, _i],
-             "act_sgemm_tn_grouped_f32": [ctypes.POINTER(GemmTnProblem), _i, _i, _i, _vp, _sz, _vp]})
-_C.lib.act_sgemm_tn_grouped_workspace.restype = _sz
-for _n in ("act_sgemm_tn_grouped_workspace", "act_sgemm_tn_grouped_splits", "act_sgemm_tn_grouped_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-# ---- persistent scratch (split-K partials, LN / colsum partial rows): one buffer per device ----------
+# ---- persistent scratch (split-K partials, LN / colsum partial rows): one buffer per device and stream ----------
 _WS = {}
 _WS_BYTES = 160 << 20       # split-K / grouped-GEMM partials: 7 K ranges of the two d=768 MLP weight gradients need 132 MB (round 3; 64 MB before)
 
 
-def workspace(device, nbytes=_WS_BYTES):
-    """scratch buffer of the CURRENT stream on ``device`` (kernels of different streams may run concurrently)."""
+def workspace(device, nbytes=_WS_BYTES, stream_handle=None):
+    """scratch buffer of one stream on ``device`` -- the CURRENT one unless a raw handle is given (kernels of different streams may run concurrently)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, _C.stream_handle(idx))
+    key = (idx, _C.stream_handle(idx) if stream_handle is None else stream_handle)
     w = _WS.get(key)
     if w is None or w.numel() * 4 < nbytes:
         w = torch.empty(max(nbytes, _WS_BYTES) // 4, dtype=torch.float32, device=device)
@@ -161,7 +117,9 @@ def gemm(a, b, a_kmajor=True, b_kmajor=True, bias=None, act=EPI_NONE, aux=None, 
                      ldr=(res.stride(0) if res is not None else 0), ldaux=(aux.stride(0) if aux is not None else 0),
                      res_row_div=int(res_row_div), bias=ptr(bias), rowscale=ptr(rowscale), res=ptr(res), aux=ptr(aux))
     ws = workspace(a.device)
-    tile, splits = cfg if cfg is not None else _gemm_config(a, b, a_kmajor, b_kmajor, M, N, K, ws)
+    if cfg is None:
+        cfg = gemm_config(a_kmajor, b_kmajor, M, N, K, a.device, a, b, ws)
+    tile, splits = cfg if cfg is not None else (0, 0)         # undecided during stream capture: the cost model now, the decision on a later eager call
     check(lib.act_sgemm_ex_f32(int(a_kmajor), int(b_kmajor), M, N, K, _C.ptr_rows(a), a.stride(0), _C.ptr_rows(b), b.stride(0), ptr(out),
                                out.stride(0), ctypes.byref(e), ptr(ws), ws.numel() * 4, tile, splits, stream()), "act_sgemm_f32")
     return out
@@ -200,19 +158,6 @@ def gemm_tn_grouped(pairs, want_bias=True, splits=0):
 
 
 # ---- OPT-IN split-bf16 products (csrc/gemm_bf16x3.hip): frozen teacher only, never the default -------------------------------------------------
-_C._declare({"act_split_bf16x2_f32": [_vp, _i, _i, _i, _vp, _vp, _vp],
-             "act_sgemm_nt_bf16x3_supported": [_i, _i, _i],
-             "act_sgemm_nt_bf16x3_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(GemmEpilogue), _vp],
-             "act_sgemm_nt_bf16x3_planes_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, ctypes.POINTER(GemmEpilogue), _vp],
-             # producers that emit planes (used from C by the teacher composite; declared here so the binding covers the whole header)
-             "act_layernorm_fwd_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
-             "act_prompt_layernorm_fwd_planes_f32": [_vp, _vp, _i, _i, _i, _f, ctypes.c_uint64, _vp, _vp, _vp, _f, _vp, _vp, _vp],
-             "act_attention_fwd_prefix_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]})
-for _n in ("act_split_bf16x2_f32", "act_sgemm_nt_bf16x3_supported", "act_sgemm_nt_bf16x3_f32", "act_sgemm_nt_bf16x3_planes_f32",
-           "act_layernorm_fwd_planes_f32", "act_prompt_layernorm_fwd_planes_f32", "act_attention_fwd_prefix_planes_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-
 def split_bf16x2(x, out=None):
     """fp32 [R, K] -> bf16 planes [2, R, K]: hi = bf16(x), lo = bf16(x - hi) (round to nearest even) -- the operand form of gemm_nt_bf16x3."""
     x = _f32rows(x, "x")
@@ -333,62 +278,67 @@ def first_use_config(a, b, ak, bk, M, N, K, ws):
     return best if t < float("inf") else (0, 0)
 
 
-def gemm_tune(a, b, ak, bk, M, N, K, ws, reps=3, rounds=1, trace=None, cands=None):
-    """time every (tile id, split-K) candidate for this product (``cands``: only these) -> (best config, best ms per launch); ``trace`` (a list)
-    receives every (tile, splits, ms) measured."""
-    given = cands
+def gemm_candidates(ak, bk, M, N, K, ws_bytes, max_split=0):
+    """every (tile id, split-K) configuration gemm_tune tries for this product, in trial order (a tie in the timing goes to the earlier one).
+    A function of these integers only: no tensor, no device (tests/test_gemm_candidates.py pins the lists).
+    ws_bytes bounds the split-K partial sums; max_split > 0 caps split-K where K <= 8192 (ACT_GEMM_MAX_SPLIT)."""
+    k32 = K % 32 == 0
+
+    def fits(s):
+        return s * M * N * 4 <= ws_bytes
+
+    def capped(sp):
+        return [s for s in sp if s <= max_split] if max_split > 0 and K <= 8192 else sp
+
+    def quad_splits(nbq):
+        """split-K counts of a quad-fragment tile whose grid has nbq workgroups"""
+        sp = [1]
+        if K >= 1024 and nbq < 2048:
+            sp += [s for s in (2, 3, 4, 6, 8, 12, 16, 24, 32) if K // s >= 256 and fits(s) and nbq * s <= 8192]
+        if K >= 65536 and nbq <= 64:                                  # weight gradients over a few hundred thousand rows on a handful of tiles
+            sp += [s for s in (48, 64, 96, 128, 192, 256) if fits(s) and nbq * s <= 1024]
+        if K >= 512 and nbq < 128:                                    # a handful of tiles: K ranges down to 128 rows, up to one round of 512 workgroups
+            sp += [s for s in (5, 7, 9, 10, 12, 14, 16) if s not in sp and K // s >= 128 and fits(s) and nbq * s <= 512]
+        return capped(sp)
+
     cands = []
     for tile, (bm, bn) in ((1, (128, 128)), (2, (128, 64)), (3, (64, 64))):
         nb = -(-M // bm) * -(-N // bn)
         if nb > 16384 and tile > 1:
             continue
-        sp_list = [1]
+        sp = [1]
         if K >= 1024 and nb < 2048:
-            sp_list += [s for s in (2, 3, 4, 6, 8, 12, 16, 24, 32) if K // s >= 256 and s * M * N * 4 <= ws.numel() * 4 and nb * s <= 8192]
+            sp += [s for s in (2, 3, 4, 6, 8, 12, 16, 24, 32) if K // s >= 256 and fits(s) and nb * s <= 8192]
         # prune hopeless configurations (a long serial K loop on a handful of workgroups takes tens of ms per trial)
-        sp_list = [s for s in sp_list if not (K // s > 8192 and nb * s < 256) or s == sp_list[-1]]
-        if _MAX_SPLIT > 0 and K <= 8192:
-            sp_list = [s for s in sp_list if s <= _MAX_SPLIT]
-        cands += [(tile, s) for s in sp_list]
-        if M % bm == 0 and N % bn == 0 and K % 32 == 0:
-            cands += [(tile + 3, s) for s in sp_list if s <= 4 and K % 32 == 0]       # software-pipelined main loop
-        if (M % bm == 0 or ak) and N % bn == 0 and K % 32 == 0:                              # the 16x16x4 kernels take an M tail (K-major A)
-            cands += [(tile + 6, s) for s in sp_list if K % 32 == 0]                  # v_mfma_f32_16x16x4_f32 main loop
-            if ak and bk:
-                cands += [(tile + 9, s) for s in sp_list if K % 32 == 0]              # NT: K-contiguous LDS image, b128 fragments
-                cands += [(29 + tile, s) for s in sp_list if K % 32 == 0]             # NT: the hand-scheduled main loop (30: 128x128, 31: 128x64, 32: 64x64)
-                if tile in (1, 2) and M % bm == 0:                                            # ... with 32-deep K tiles (20: 128x128, 21: 128x64): full 128-byte rows per load
-                    cands += [(19 + tile, s) for s in sp_list if K % 32 == 0]
-                if tile == 1 and M % bm == 0 and K >= 1536:                                   # ... with the software-pipelined main loop (17: 128x128; 18 = 128x64
-                    cands += [(17, s) for s in sp_list if K % 32 == 0]                 # exists but never won a shape): pays on long K only
-        if not bk and N % 128 == 0 and K % 32 == 0 and ((tile == 1 and (ak or M % 128 == 0)) or (tile == 2 and ak)):
-            qsp = [1]
-            nbq = -(-M // (128 if tile == 1 else 64)) * (N // 128)
-            if K >= 1024 and nbq < 2048:
-                qsp += [s for s in (2, 3, 4, 6, 8, 12, 16, 24, 32) if K // s >= 256 and s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 8192]
-            if K >= 65536 and nbq <= 64:                              # weight gradients over a few hundred thousand rows on a handful of tiles
-                qsp += [s for s in (48, 64, 96, 128, 192, 256) if s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 1024]
-            if K >= 512 and nbq < 128:                                # a handful of tiles: K ranges down to 128 rows, up to one round of 512 workgroups
-                qsp += [s for s in (5, 7, 9, 10, 12, 14, 16) if s not in qsp and K // s >= 128 and s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 512]
-            if _MAX_SPLIT > 0 and K <= 8192:
-                qsp = [s for s in qsp if s <= _MAX_SPLIT]
-            cands += [(12 + tile, s) for s in qsp if K % 32 == 0]                     # NN / TN: quad fragments (13: 128x128, 14: 64x128)
-            cands += [(32 + tile, s) for s in qsp if K % 32 == 0]                     # ... on the hand-scheduled main loop (33: 128x128, 34: 64x128)
-        if ak and not bk and N % 64 == 0 and K % 32 == 0 and tile in (2, 3):                  # NN, 64-column quad tiles (4 x 1 waves): 16 = 128x64, 15 = 64x64
-            qsp = [1]
-            nbq = -(-M // (128 if tile == 2 else 64)) * (N // 64)
-            if K >= 1024 and nbq < 2048:
-                qsp += [s for s in (2, 3, 4, 6, 8, 12, 16, 24, 32) if K // s >= 256 and s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 8192]
-            if K >= 65536 and nbq <= 64:                              # weight gradients over a few hundred thousand rows on a handful of tiles
-                qsp += [s for s in (48, 64, 96, 128, 192, 256) if s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 1024]
-            if K >= 512 and nbq < 128:                                # a handful of tiles: K ranges down to 128 rows, up to one round of 512 workgroups
-                qsp += [s for s in (5, 7, 9, 10, 12, 14, 16) if s not in qsp and K // s >= 128 and s * M * N * 4 <= ws.numel() * 4 and nbq * s <= 512]
-            if _MAX_SPLIT > 0 and K <= 8192:
-                qsp = [s for s in qsp if s <= _MAX_SPLIT]
-            cands += [(16 if tile == 2 else 15, s) for s in qsp if K % 32 == 0]
-            cands += [(36 if tile == 2 else 35, s) for s in qsp if K % 32 == 0]       # ... hand-scheduled (36: 128x64, 35: 64x64)
-    if given is not None:
-        cands = list(given)
+        sp = capped([s for s in sp if not (K // s > 8192 and nb * s < 256) or s == sp[-1]])
+        cands += [(tile, s) for s in sp]
+        if k32 and N % bn == 0:
+            if M % bm == 0:
+                cands += [(tile + 3, s) for s in sp if s <= 4]                        # software-pipelined main loop
+            if M % bm == 0 or ak:                                                     # the 16x16x4 kernels take an M tail (K-major A)
+                cands += [(tile + 6, s) for s in sp]                                  # v_mfma_f32_16x16x4_f32 main loop
+                if ak and bk:
+                    cands += [(tile + 9, s) for s in sp]                              # NT: K-contiguous LDS image, b128 fragments
+                    cands += [(29 + tile, s) for s in sp]                             # NT: the hand-scheduled main loop (30: 128x128, 31: 128x64, 32: 64x64)
+                    if tile in (1, 2) and M % bm == 0:                                # ... with 32-deep K tiles (20: 128x128, 21: 128x64): full 128-byte rows per load
+                        cands += [(19 + tile, s) for s in sp]
+                    if tile == 1 and M % bm == 0 and K >= 1536:                       # ... with the software-pipelined main loop (17: 128x128; 18 = 128x64
+                        cands += [(17, s) for s in sp]                                # exists but never won a shape): pays on long K only
+        if k32 and not bk and N % 128 == 0 and ((tile == 1 and (ak or M % 128 == 0)) or (tile == 2 and ak)):
+            qsp = quad_splits(-(-M // (128 if tile == 1 else 64)) * (N // 128))
+            cands += [(12 + tile, s) for s in qsp]                                    # NN / TN: quad fragments (13: 128x128, 14: 64x128)
+            cands += [(32 + tile, s) for s in qsp]                                    # ... on the hand-scheduled main loop (33: 128x128, 34: 64x128)
+        if k32 and ak and not bk and N % 64 == 0 and tile in (2, 3):                  # NN, 64-column quad tiles (4 x 1 waves): 16 = 128x64, 15 = 64x64
+            qsp = quad_splits(-(-M // (128 if tile == 2 else 64)) * (N // 64))
+            cands += [(16 if tile == 2 else 15, s) for s in qsp]
+            cands += [(36 if tile == 2 else 35, s) for s in qsp]                      # ... hand-scheduled (36: 128x64, 35: 64x64)
+    return cands
+
+
+def gemm_tune(a, b, ak, bk, M, N, K, ws, reps=3, rounds=1, trace=None, cands=None):
+    """time every (tile id, split-K) candidate for this product (``cands``: only these, else gemm_candidates) -> (best config, best ms per launch);
+    ``trace`` (a list) receives every (tile, splits, ms) measured."""
+    cands = list(cands) if cands is not None else gemm_candidates(ak, bk, M, N, K, ws.numel() * 4, _MAX_SPLIT)
     scratch = torch.empty(M, N, dtype=torch.float32, device=a.device)
     e = GemmEpilogue(alpha=1.0)
     best, best_t = (0, 0), float("inf")
@@ -414,26 +364,46 @@ def gemm_tune(a, b, ak, bk, M, N, K, ws, reps=3, rounds=1, trace=None, cands=Non
     return best, best_t
 
 
-def _gemm_config(a, b, ak, bk, M, N, K, ws):
+def gemm_config(ak, bk, M, N, K, device, a=None, b=None, ws=None, publish=False):
+    """THE launch-configuration decision for the product (a_kmajor, b_kmajor, M, N, K) on ``device``: (tile id, split-K), (0, 0) = the library's
+    built-in cost model; None = cannot be decided now (the shape needs timing and the stream is being captured) -- nothing is recorded then.
+    Order: size cut-off, skinny-TN exemption, cache, shipped table, first-use timing -- on the operands ``a`` / ``b`` where the caller has them
+    (gemm), else on random ones (composite.ensure_tuned, which knows shapes only).  A freshly timed shape is recorded in _NEW_TUNED and published to
+    the C-side table the composite entry points read; ``publish``: hand the decision to that table in any case (it may have been cleared since)."""
     if not AUTOTUNE or M * N * K < (1 << 24):
         return 0, 0                                            # tiny products: built-in cost model
     if not ak and not bk and min(M, N) <= 8:
         return 0, 0                                            # skinny weight gradients: streaming-reduction kernel (gemm.hip)
-    key = (int(ak), int(bk), M, N, K, a.device.index)
+    key = (int(ak), int(bk), M, N, K, device.index)
     cfg = _GEMM_CACHE.get(key)
-    if cfg is not None:
+    if cfg is not None and not publish:
         return cfg
-    cfg = _GEMM_TABLE.get(key[:5])
-    if cfg is not None:
+    if cfg is None:
+        cfg = _GEMM_TABLE.get(key[:5])
+        if cfg is None:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            if a is None:
+                a = torch.randn((M, K) if ak else (K, M), dtype=torch.float32, device=device)
+                b = torch.randn((N, K) if bk else (K, N), dtype=torch.float32, device=device)
+            cfg = _NEW_TUNED[key[:5]] = first_use_config(a, b, ak, bk, M, N, K, ws if ws is not None else workspace(device))
+            publish = True
         _GEMM_CACHE[key] = cfg
-        return cfg
-    if torch.cuda.is_current_stream_capturing():
-        return 0, 0
-    best = first_use_config(a, b, ak, bk, M, N, K, ws)
-    _GEMM_CACHE[key] = best
-    _NEW_TUNED[key[:5]] = best
-    lib.act_gemm_tune_set(int(ak), int(bk), M, N, K, int(best[0]), int(best[1]))      # the composite entry points launch the same configuration
-    return best
+    if publish:
+        lib.act_gemm_tune_set(key[0], key[1], M, N, K, int(cfg[0]), int(cfg[1]))
+    return cfg
+
+
+def _gemm_config(a, b, ak, bk, M, N, K, ws):
+    """gemm_config for a product whose operands exist; during stream capture an undecided shape runs on the cost model and is decided later"""
+    cfg = gemm_config(ak, bk, M, N, K, a.device, a, b, ws)
+    return cfg if cfg is not None else (0, 0)
+
+
+def publish_table():
+    """the shipped table -> the C-side table (composite entry points)"""
+    for (ak, bk, M, N, K), (tile, sp) in _GEMM_TABLE.items():
+        lib.act_gemm_tune_set(ak, bk, M, N, K, tile, sp)
 
 
 def layernorm_fwd(x, pos, gamma, beta, eps, want_xin=True, want_stats=True):
@@ -847,34 +817,6 @@ def softmax_xent(logits, labels):
 
 
 # ---- mini-PointNet / FoldingNet row kernels (csrc/pointnet.hip) --------------------------------------------------
-_C._declare({
-    "act_colstats_workspace": [_i, _i],
-    "act_bn_stats_f32": [_vp, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_affine_act_f32": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "act_bn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_group_max_f32": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "act_group_max_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_group_sum_f32": [_vp, _i, _i, _i, _vp, _vp],
-    "act_group_max_bwd_matmul_f32": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp],
-    "act_group_max_bwd_wgrad_workspace": [_i, _i, _i, _i],
-    "act_group_live_i32": [_vp, _i, _i, _vp, _vp],
-    "act_group_max_bwd_matmul_live_f32": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp],
-    "act_bn_bwd_groups_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_group_max_bwd_wgrad_f32": [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp],
-    "act_col_mean_var_f32": [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_bn_bwd_sums_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_bn_bwd_apply_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp, _vp],
-})
-_C.lib.act_layernorm_bwd_workspace.restype = _sz
-_C.lib.act_colsum_workspace.restype = _sz
-_C.lib.act_colstats_workspace.restype = _sz
-_C.lib.act_group_max_bwd_wgrad_workspace.restype = _sz
-for _n in ("act_colstats_workspace", "act_bn_stats_f32", "act_affine_act_f32", "act_bn_bwd_f32", "act_group_max_f32",
-           "act_group_max_bwd_f32", "act_group_max_bwd_matmul_f32", "act_group_max_bwd_wgrad_workspace", "act_group_max_bwd_wgrad_f32", "act_group_live_i32",
-           "act_group_max_bwd_matmul_live_f32", "act_bn_bwd_groups_f32", "act_group_sum_f32", "act_col_mean_var_f32", "act_bn_bwd_sums_f32", "act_bn_bwd_apply_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-
 class BNActFn(torch.autograd.Function):
     """BatchNorm1d over the rows of x [R,C] (+ optional ReLU).  train: batch statistics (biased variance), running stats
     updated in place (momentum, unbiased variance) like nn.BatchNorm1d; eval: running statistics."""
@@ -1059,25 +1001,6 @@ def linear_group_add(x, w, g, n):
 
 
 # ---- DGCNN / tokenizer glue (csrc/dgcnn.hip) -------------------------------------------------------------------------
-_u64 = ctypes.c_uint64
-_C._declare({
-    "act_edge_gn_lrelu_max_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _i, _i, _vp],
-    "act_gn_gumbel_argmax_gather_f32": [_vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _u64, _vp, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp],
-    "act_edge_gn_lrelu_max_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _vp],
-    "act_edge_bwd_lds": [_i],
-    "act_gumbel_softmax_fwd_f32": [_vp, _i, _i, _vp, _u64, _f, _vp, _vp],
-    "act_gumbel_softmax_bwd_f32": [_vp, _vp, _i, _i, _f, _vp, _vp],
-    "act_kl_uniform_fwd_f32": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "act_kl_uniform_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-})
-_C.lib.act_layernorm_bwd_workspace.restype = _sz
-_C.lib.act_colsum_workspace.restype = _sz
-_C.lib.act_colstats_workspace.restype = _sz
-for _n in ("act_edge_gn_lrelu_max_f32", "act_gn_gumbel_argmax_gather_f32", "act_edge_gn_lrelu_max_bwd_f32", "act_edge_bwd_lds",
-           "act_gumbel_softmax_fwd_f32", "act_gumbel_softmax_bwd_f32", "act_kl_uniform_fwd_f32", "act_kl_uniform_bwd_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-
 def edge_gn_lrelu_max(yz, zoff, idx, B, G, k, C, gn, out=None, ooff=0, slope=0.2):
     """inference-only tail of a DGCNN layer (see csrc/dgcnn.hip); yz [B*G, ld], -> out[:, ooff:ooff+C]."""
     yz = _f32c(yz)
@@ -1199,15 +1122,6 @@ def gn_gumbel_argmax_gather(h, B, G, gn, codebook, noise=None, seed=0, tau=1.0, 
     return out, index, logits
 
 
-_C._declare({"act_attention_fwd_prefix_f32": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp],
-             "act_attention_bwd_prefix_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]})
-_C.lib.act_layernorm_bwd_workspace.restype = _sz
-_C.lib.act_colsum_workspace.restype = _sz
-_C.lib.act_colstats_workspace.restype = _sz
-_C.SIGNATURES.setdefault("act_attention_fwd_prefix_f32", _C.lib.act_attention_fwd_prefix_f32.argtypes)
-_C.SIGNATURES.setdefault("act_attention_bwd_prefix_f32", _C.lib.act_attention_bwd_prefix_f32.argtypes)
-
-
 def attention_fwd_prefix(kv0, S0, qkv1, Sq, B, H, hd, want_lse=False):
     """queries = the Sq rows of qkv1 [B*Sq, 3*H*hd]; keys/values = S0 rows of kv0 [B*S0, 2*H*hd] then the rows of qkv1."""
     out = torch.empty(B * Sq, H * hd, dtype=torch.float32, device=qkv1.device)
@@ -1269,16 +1183,6 @@ class PrefixBlockFnPerKernel(torch.autograd.Function):
         return (dxin, dxin, dprm) + (None,) * 17
 
 
-_C._declare({"act_prompt_layernorm_fwd_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp]})
-_C.SIGNATURES.setdefault("act_prompt_layernorm_fwd_f32", _C.lib.act_prompt_layernorm_fwd_f32.argtypes)
-
-
-_C._declare({"act_prompt_rows_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp],
-             "act_prompt_rows_bwd_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp]})
-for _n in ("act_prompt_rows_fwd_f32", "act_prompt_rows_bwd_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-
 class PromptRowsFn(torch.autograd.Function):
     """prompt rows of a trained prompt layer: y[b*P+p, :] = dropout(tok[p, :]) + ppos[p, :] (models/dvae.py:485-498, 556-566), one launch per
     direction.  mask: 0/1 keep mask [B, P, D] (injected / recorded draws) or None -> in-kernel Philox(seed), regenerated in the backward."""
@@ -1337,27 +1241,6 @@ def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, b
 
 
 # ---- dense per-point prediction (csrc/seg.hip): three-NN feature propagation, log-softmax, weighted NLL, confusion matrix -------------------
-_C._declare({
-    "act_three_nn_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "act_interp_rows_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_interp_rows_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_interp_xyz_grad_workspace": [ctypes.c_longlong, _i],
-    "act_interp_xyz_grad_f32": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _sz, _vp],
-    "act_log_softmax_fwd_f32": [_vp, ctypes.c_longlong, _i, _vp, _vp],
-    "act_log_softmax_bwd_f32": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
-    "act_nll_weighted_workspace": [ctypes.c_longlong],
-    "act_nll_weighted_fwd_f32": [_vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp, _vp, _vp, _sz, _vp],
-    "act_nll_weighted_bwd_f32": [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
-    "act_confusion_i64": [_vp, _vp, ctypes.c_longlong, _i, _vp, _vp],
-})
-_C.lib.act_interp_xyz_grad_workspace.restype = _sz
-_C.lib.act_nll_weighted_workspace.restype = _sz
-for _n in ("act_three_nn_f32", "act_interp_rows_fwd_f32", "act_interp_rows_bwd_f32", "act_interp_xyz_grad_workspace", "act_interp_xyz_grad_f32",
-           "act_log_softmax_fwd_f32", "act_log_softmax_bwd_f32", "act_nll_weighted_workspace", "act_nll_weighted_fwd_f32", "act_nll_weighted_bwd_f32",
-           "act_confusion_i64"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
-
 def three_nn(xyz, centers, want_adj=True):
     """xyz [B,N,3], centers [B,G,3] -> (idx int32 [B,N,3], weight [B,N,3], adj_off int32 [B,G+1] | None, adj_ent int32 [B,3N] | None):
     the three nearest centres of every point in ascending (difference-form distance, index) order, their normalised inverse-distance
@@ -1557,14 +1440,6 @@ def group_mean(x, n):
 
 
 # ---- part segmentation (csrc/partseg.hip): category label branch, category-masked evaluation -------------------------------------------
-_C._declare({
-    "act_label_branch_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp],
-    "act_label_branch_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp],
-    "act_part_eval_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp],
-})
-for _n in ("act_label_branch_fwd_f32", "act_label_branch_bwd_f32", "act_part_eval_f32"):
-    _C.SIGNATURES.setdefault(_n, getattr(_C.lib, _n).argtypes)
-
 PART_COUNT_STRIDE = 16          # int32 per shape in the part-evaluation counts: [0,6) intersections, [6,12) unions, [12] category, [13] parts
 
 
