@@ -231,6 +231,14 @@ _TABLE = {
     "act_scene_finish": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
     # Stage-I reconstruction evaluation (csrc/recon_eval.hip)
     "act_recon_eval_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _vp],
+    # linear-SVM validation of pretrained features (csrc/svm.hip)
+    "act_svm_scores_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    "act_svm_hinge_workspace": (_sz, [_i, _i]),
+    "act_svm_hinge_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_svm_tprod_workspace": (_sz, [_i, _i, _i]),
+    "act_svm_tprod_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_svm_newton_workspace": (_sz, [_i, _i, _i]),
+    "act_svm_newton_f32": [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -1648,3 +1648,81 @@ def recon_eval(coarse, dense, gt, out, row0, th=0.01):
     check(lib.act_recon_eval_f32(ptr(coarse), ptr(dense), ptr(gt), B, coarse.shape[1], dense.shape[1], gt.shape[1], float(th), ptr(out), int(row0),
                                  out.shape[0], stream()), "act_recon_eval_f32")
     return out
+
+
+# ---- linear-SVM validation of pretrained features (csrc/svm.hip): scores, hinge, transposed product, one batched Newton iteration ----------------
+SVM_MAX_CLASSES = 64
+
+
+def _svm_rows(x, name):
+    if not x.is_cuda:
+        raise _C.ActHipError("act_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise _C.ActHipError(f"{name}: expected a float32 matrix, got {tuple(x.shape)} {x.dtype}")
+    return x.contiguous()
+
+
+def _svm_ids(t, n, name):
+    if not t.is_cuda:
+        raise _C.ActHipError("act_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if t.dim() != 1 or t.numel() != n or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise _C.ActHipError(f"{name}: expected {n} integers, got {tuple(t.shape)} {t.dtype}")
+    return t.to(torch.int64).contiguous()
+
+
+def _svm_workspace(device, nbytes):
+    """the stream's scratch buffer; its base address is 256-byte aligned (caching allocator)"""
+    return workspace(device, max(int(nbytes), 4))
+
+
+def svm_scores(x, w, b=None, mask=None, out=None):
+    """x [N,D] . w [K,D]^T (+ b [K]) -> [N,K]; ``mask`` [N,K]: zero where mask == 0 (K <= 64)"""
+    x, w = _svm_rows(x, "svm_scores x"), _svm_rows(w, "svm_scores w")
+    (N, D), K = x.shape, w.shape[0]
+    if w.shape[1] != D or (b is not None and (b.dtype != torch.float32 or b.numel() != K)) or \
+            (mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (N, K))):
+        raise _C.ActHipError("svm_scores: operand shapes do not agree")
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    check(lib.act_svm_scores_f32(ptr(x), ptr(w), ptr(b.contiguous() if b is not None else None), ptr(mask.contiguous() if mask is not None else None),
+                                 N, D, K, ptr(out), stream()), "act_svm_scores_f32")
+    return out
+
+
+def svm_hinge(scores, labels, classes):
+    """scores fp32 [N,K], labels int [N], classes int [K] -> (R [N,K] = y max(0, 1 - y m), float64 [K] sums of h^2), y = +1 where label == class"""
+    m = _svm_rows(scores, "svm_hinge scores")
+    N, K = m.shape
+    labels, classes = _svm_ids(labels, N, "svm_hinge labels"), _svm_ids(classes, K, "svm_hinge classes")
+    R = torch.empty_like(m)
+    sums = torch.empty(K, dtype=torch.float64, device=m.device)
+    ws = _svm_workspace(m.device, lib.act_svm_hinge_workspace(N, K))
+    check(lib.act_svm_hinge_f32(ptr(m), ptr(labels), ptr(classes), N, K, ptr(R), ptr(sums), ptr(ws), ws.numel() * 4, stream()), "act_svm_hinge_f32")
+    return R, sums
+
+
+def svm_tprod(p, x):
+    """p [N,K], x [N,D] -> (p^T . x [K,D], column sums of p [K])"""
+    p, x = _svm_rows(p, "svm_tprod p"), _svm_rows(x, "svm_tprod x")
+    (N, K), D = p.shape, x.shape[1]
+    if x.shape[0] != N:
+        raise _C.ActHipError("svm_tprod: row counts differ")
+    out = torch.empty(K, D, dtype=torch.float32, device=x.device)
+    colsum = torch.empty(K, dtype=torch.float32, device=x.device)
+    ws = _svm_workspace(x.device, lib.act_svm_tprod_workspace(N, D, K))
+    check(lib.act_svm_tprod_f32(ptr(p), ptr(x), N, D, K, ptr(out), ptr(colsum), ptr(ws), ws.numel() * 4, stream()), "act_svm_tprod_f32")
+    return out, colsum
+
+
+def svm_state(K, device):
+    """fresh solver state: (istate int32 [3,K]: flag, Newton steps, CG iterations; dstate float64 [2,K]: objective, gradient norm)"""
+    return torch.zeros(3, K, dtype=torch.int32, device=device), torch.zeros(2, K, dtype=torch.float64, device=device)
+
+
+def svm_newton(x, labels, classes, W, b, istate, dstate, C=1.0, tol=1e-4, max_cg=60):
+    """one Newton iteration of every class, in place on W [K,D], b [K] and the state of svm_state (see include/act_hip.h); no host read"""
+    N, D = x.shape
+    K = W.shape[0]
+    ws = _svm_workspace(x.device, lib.act_svm_newton_workspace(N, D, K))
+    check(lib.act_svm_newton_f32(ptr(x), ptr(labels), ptr(classes), N, D, K, float(C), float(tol), int(max_cg), ptr(W), ptr(b), ptr(istate),
+                                 ptr(dstate), ptr(ws), ws.numel() * 4, stream()), "act_svm_newton_f32")

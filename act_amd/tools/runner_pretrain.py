@@ -6,7 +6,9 @@ Differences forced by the hardware-first design, none of them visible in the con
     reference's non-SyncBN default) and without find_unused_parameters: the never-used heads
     (lm_head / cls_head) are kept in the state_dict but frozen, so gradients are a single bucketed RCCL
     all-reduce overlapped with backward;
-  * the logged loss is all-reduced every step but read back only every ``log_every`` steps.
+  * the logged loss is all-reduced every step but read back only every ``log_every`` steps;
+  * the linear-SVM validation (reference :47-51, :228-287, which its run_net never calls) is solved on the device (utils/svm.py) and is
+    opt-in: ``svm_val: True`` in the config, a ``dataset.extra_train`` section and a positive ``--val_freq``.
 """
 import time
 import os
@@ -33,6 +35,45 @@ class Acc_Metric:
 
     def state_dict(self):
         return {'acc': self.acc}
+
+
+def evaluate_svm(train_features, train_labels, test_features, test_labels):
+    """accuracy (percent) on the test features of a LinearSVC fitted to the train features (reference :47-51), on device tensors: the solve
+    and the prediction stay on the device, the accuracy is the one value read back"""
+    from ..utils.svm import LinearSVC
+    clf = LinearSVC().fit(train_features, train_labels)
+    pred = clf.predict(test_features)
+    return float((pred == test_labels.to(pred.dtype)).sum() * 100. / pred.shape[0])
+
+
+def extract_features(base_model, dataloader, npoints):
+    """(features [n, C], labels [n]) of a ModelNet-style loader, concatenated on the device: misc.fps to ``npoints``, ``forward(noaug=True)``"""
+    feats, labels = [], []
+    for _, _, data in dataloader:
+        points = misc.fps(data[0].cuda(non_blocking=True), npoints)
+        assert points.size(1) == npoints
+        feats.append(base_model(points, noaug=True).detach())
+        labels.append(data[1].cuda(non_blocking=True).view(-1))
+    return torch.cat(feats, dim=0), torch.cat(labels, dim=0)
+
+
+def validate(base_model, extra_train_dataloader, test_dataloader, epoch, val_writer, args, config, logger=None):
+    """Point-BERT's linear-SVM protocol (reference :228-287): features of the extra_train and val splits, a linear SVM on the first, accuracy
+    on the second.  Under ``args.distributed`` the features are all-gathered and every rank solves the same problem."""
+    print_log(f"[VALIDATION] Start validating epoch {epoch}", logger=logger)
+    base_model.eval()
+    npoints = config.dataset.train.others.npoints
+    with torch.no_grad():
+        train_features, train_label = extract_features(base_model, extra_train_dataloader, npoints)
+        test_features, test_label = extract_features(base_model, test_dataloader, npoints)
+        if args.distributed:
+            train_features, train_label, test_features, test_label = (dist_utils.gather_tensor(t, args) for t in
+                                                                      (train_features, train_label, test_features, test_label))
+        svm_acc = evaluate_svm(train_features.float(), train_label, test_features.float(), test_label)
+        print_log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, svm_acc), logger=logger)
+    if val_writer is not None:
+        val_writer.add_scalar('Metric/ACC', svm_acc, epoch)
+    return Acc_Metric(svm_acc)
 
 
 def freeze_unused_heads(model):
@@ -121,6 +162,9 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
     logger = get_logger(args.log_name)
     (train_sampler, train_dataloader), (_, test_dataloader) = builder.dataset_builder(args, config.dataset.train), \
         builder.dataset_builder(args, config.dataset.val)
+    # linear-SVM validation is opt-in: without all three of these the loop, its random draws and its checkpoints are what they are without it
+    svm_val = bool(config.dataset.get('extra_train')) and getattr(args, 'val_freq', 0) > 0 and bool(config.get('svm_val', False))
+    extra_train_dataloader = builder.dataset_builder(args, config.dataset.extra_train)[1] if svm_val else None
     base_model = builder.model_builder(config.model)
     freeze_unused_heads(base_model)
     device = torch.device("cuda", args.local_rank % max(1, torch.cuda.device_count()))
@@ -219,6 +263,11 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
         print_log('[Training] EPOCH: %d EpochTime = %.3f (s) Losses = %s lr = %.6f' %
                   (epoch, time.time() - epoch_start_time, ['%.4f' % l for l in losses.avg()], optimizer.param_groups[0]['lr']),
                   logger=logger)
+        if svm_val and epoch % args.val_freq == 0:
+            metrics = validate(base_model, extra_train_dataloader, test_dataloader, epoch, val_writer, args, config, logger=logger)
+            if metrics.better_than(best_metrics):
+                best_metrics = metrics
+                builder.save_checkpoint(base_model, optimizer, epoch, metrics, best_metrics, 'ckpt-best', args, logger=logger)
         builder.save_checkpoint(base_model, optimizer, epoch, metrics, best_metrics, 'ckpt-last', args, logger=logger)
         if epoch % 25 == 0 and epoch >= 250:
             builder.save_checkpoint(base_model, optimizer, epoch, metrics, best_metrics, f'ckpt-epoch-{epoch:03d}', args, logger=logger)

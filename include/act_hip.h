@@ -636,6 +636,35 @@ int act_scene_finish(const int32_t* votes, const int32_t* label, long long P, in
 int act_recon_eval_f32(const float* coarse, const float* dense, const float* gt, int B, int nc, int nd, int N, float th, double* out, int row0,
                        int num_rows, act_stream_t stream);
 
+/* ---- linear-SVM validation of pretrained features (csrc/svm.hip) ---------------------------------------------------------------------
+ * tools/runner_pretrain.py:47-51, 228-287: sklearn.svm.LinearSVC() on extracted features, i.e. liblinear's L2-regularised L2-loss SVC,
+ * one-vs-rest, with the bias regularised (its appended constant feature) but kept as a separate scalar per class:
+ *   f_c(w, b) = 1/2 (|w|^2 + b^2) + C sum_i max(0, 1 - y_ic (x_i . w + b))^2,   y_ic = +1 if labels[i] == classes[c] else -1.
+ * X fp32 [N,D], labels int64 [N], classes int64 [K], K <= 64.  Every reduction has a fixed order (float64 where it runs over the N rows) and
+ * there are no atomics: all outputs are bit-identical run to run.  X is read with 16-byte loads when D % 4 == 0 and X is 16-byte aligned.
+ *
+ * scores: out [N,K] = X . W^T + b (b [K], may be NULL); mask ([N,K], may be NULL): out = 0 where mask == 0. */
+int act_svm_scores_f32(const float* X, const float* W, const float* b, const float* mask, int N, int D, int K, float* out, act_stream_t stream);
+/* hinge: from scores M [N,K], R [N,K] = y max(0, 1 - y m) (its non-zero pattern is the active set) and sums float64 [K] = sum_i h^2 */
+size_t act_svm_hinge_workspace(int N, int K);
+int act_svm_hinge_f32(const float* M, const int64_t* labels, const int64_t* classes, int N, int K, float* R, double* sums, void* workspace,
+                      size_t workspace_bytes, act_stream_t stream);
+/* transposed product: out [K,D] = P[N,K]^T . X[N,D], colsum [K] (may be NULL) = column sums of P; fp32 partial products over 256 rows, summed
+ * in float64 and rounded once */
+size_t act_svm_tprod_workspace(int N, int D, int K);
+int act_svm_tprod_f32(const float* P, const float* X, int N, int D, int K, float* out, float* colsum, void* workspace, size_t workspace_bytes,
+                      act_stream_t stream);
+/* ONE Newton iteration of all K classes, in place on W [K,D], b [K]: gradient, up to max_cg conjugate-gradient iterations on the generalised
+ * Hessian I + 2C X_A^T X_A (per class, until |r| <= 0.05 |g|), then the largest step 2^-t (t < 16) that passes the Armijo test on the true
+ * objective.  istate int32 [3,K]: row 0 = 0 running / 1 converged (|grad f_c| <= tol) / 2 no progress (no step accepted, or an accepted
+ * decrease below fp32 epsilon times the objective: the resolution of an objective built on fp32 scores), row 1 Newton steps taken, row 2 CG
+ * iterations.  dstate float64 [2,K]: row 0 objective and row 1 gradient norm at the iteration's START.  Start from istate = 0; a class whose
+ * row-0 flag is set is frozen.  The caller repeats the call until every flag is set;
+ * nothing is read back or synchronised here. */
+size_t act_svm_newton_workspace(int N, int D, int K);
+int act_svm_newton_f32(const float* X, const int64_t* labels, const int64_t* classes, int N, int D, int K, float C, float tol, int max_cg,
+                       float* W, float* b, int32_t* istate, double* dstate, void* workspace, size_t workspace_bytes, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
