@@ -191,6 +191,10 @@ _TABLE = {
     "act_add_f32": [_vp, _vp, _vp, _ll, _vp],
     "act_prefix_block_saved_floats": (_sz, [_dims, _i]),
     "act_prefix_block_fwd_f32": [_dims, _i, _blk, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_prefix_block_fwd_kv_f32": [_dims, _i, _blk, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_prompt_kv_sparse": [_i],
+    "act_prompt_kv_workspace": (_sz, [_i, _i, _i, _i]),
+    "act_prompt_kv_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp],
     "act_prefix_block_bwd_scratch_floats": (_sz, [_dims, _i]),
     "act_prefix_block_bwd_f32": [_dims, _i, _blk, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_prefix_vit_scratch_floats": (_sz, [_P(PrefixVit)]),

@@ -427,9 +427,10 @@ class PrefixBlockFn(torch.autograd.Function):
         return (dx, dx, dprm) + (None,) * 17
 
 
-def block_forward_prefix(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, n1p=None):
+def block_forward_prefix(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, n1p=None, kvp=None):
     """Inference-only prefix block (one host call): exactly the patch-token rows of
-    blk(cat(prompt, x) + cat(prompt_pos, pos)) of models/dvae.py:549-571.  prm2d [B*P, D] = prompt + prompt_pos, or n1p = its LayerNorm."""
+    blk(cat(prompt, x) + cat(prompt_pos, pos)) of models/dvae.py:549-571.  prm2d [B*P, D] = prompt + prompt_pos, or n1p = its LayerNorm, or
+    kvp [B*P, 2D] = its keys / values (K.prompt_kv)."""
     D = x2d.shape[1]
     dev = x2d.device
     dims, n_saved, _ = _prefix_dims(B, G, D, heads, w1.shape[0], eps, P)
@@ -440,6 +441,11 @@ def block_forward_prefix(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj
     tmp = torch.empty(n_saved, dtype=torch.float32, device=dev)
     out = torch.empty(B * G, D, dtype=torch.float32, device=dev)
     ws = K.workspace(dev)
+    if kvp is not None:
+        kargs = (ctypes.byref(dims), P, ctypes.byref(prm), _p(x2d), _p(pos2d), _p(K._f32c(kvp)), _p(tmp), _p(out), _p(ws), ws.numel() * 4)
+        ensure_tuned(("pfx_fwd_kv", B, G, D, heads, w1.shape[0], P), lambda: lib.act_prefix_block_fwd_kv_f32(*kargs, _C.stream()), dev)
+        check(lib.act_prefix_block_fwd_kv_f32(*kargs, _C.stream()), "act_prefix_block_fwd_kv_f32")
+        return out
     args = (ctypes.byref(dims), P, ctypes.byref(prm), _p(x2d), _p(pos2d), _p(prm2d), _p(n1p), 0, _p(tmp), _p(out), _p(ws), ws.numel() * 4)
     ensure_tuned(("pfx_fwd", B, G, D, heads, w1.shape[0], P), lambda: lib.act_prefix_block_fwd_f32(*args, _C.stream()), dev)
     check(lib.act_prefix_block_fwd_f32(*args, _C.stream()), "act_prefix_block_fwd_f32")

@@ -12,7 +12,7 @@ enum ActKernelId {
     KID_GEMM_NT, KID_GEMM_NN, KID_GEMM_TN, KID_LAYERNORM_FWD, KID_LAYERNORM_BWD, KID_ATTN_FWD, KID_ATTN_BWD,
     KID_COLSUM, KID_GELU_BWD, KID_COSINE_FWD, KID_COSINE_BWD, KID_BN_STATS, KID_BN_APPLY, KID_BN_BWD,
     KID_MAXPOOL, KID_MAXPOOL_BWD, KID_GN_LRELU_MAX, KID_GRAPH_FEATURE, KID_GUMBEL_ARGMAX, KID_ROW_GATHER,
-    KID_ROW_SCATTER, KID_ADAMW, KID_ELTWISE, KID_GEMM_BF16X3, KID_COUNT
+    KID_ROW_SCATTER, KID_ADAMW, KID_ELTWISE, KID_GEMM_BF16X3, KID_PROMPT_KV, KID_COUNT
 };
 
 void act_prof_begin(int kid, hipStream_t s, double flops, double bytes);
@@ -29,6 +29,15 @@ struct ActProfScope {
     }
     ~ActProfScope() { if (on) act_prof_end(kid, s); }
 };
+
+// ---- sparse prompt keys / values (prompt_kv.hip): the pieces act_prompt_kv_fwd_f32 (composite.hip) puts around the base product ------------
+struct ActPromptKvWs { float *arows, *base, *rstd, *dmu; int* steps; unsigned short* lst; size_t floats; };
+bool act_prompt_kv_shape_ok(int B, int P, int D, int N);                                   // D % 4 == 0 and the weight tile fits LDS
+void act_prompt_kv_carve(float* ws, int B, int P, int D, int N, ActPromptKvWs& w);         // ws == null: sizes only (w.floats)
+int act_prompt_kv_rows(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                       const float* gamma, const float* beta, float eps, const ActPromptKvWs& w, hipStream_t s);
+int act_prompt_kv_correct(const float* tok, int B, int P, int D, int N, float drop_p, const float* gamma, const float* W, const float* bias,
+                          const ActPromptKvWs& w, float* kvp, hipStream_t s);
 
 #define ACT_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 

@@ -8,6 +8,7 @@
 // `side_stream` that `stream` waits for before the function returns.  Buffers handed to the side stream are caller-owned slabs
 // that outlive the call on `stream` order, so the caller's allocator never sees a cross-stream hazard.
 #include "common.h"
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -141,7 +142,7 @@ inline bool x3_fits(const act_block_dims_t& d, int P, size_t a_elems) {
 }
 
 int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t& w, const float* x, const float* pos, const float* n1p,
-                      bool keep, PrefixSaved& sv, float* out, float* ws, size_t wsb, hipStream_t s, const X3Block* x3 = nullptr) {
+                      bool keep, PrefixSaved& sv, float* out, float* ws, size_t wsb, hipStream_t s, const X3Block* x3 = nullptr, bool kvp_ready = false) {
     const int B = d.B, G = d.S, D = d.D, H = d.heads, hd = D / H, Hd = d.hidden, TG = B * G, TP = B * P;
     // C = epi(A . W^T): on the f32-input MFMA kernels -- or, for the frozen teacher with the split-bf16 switch on and a shape the kernel takes, A is split into
     // (hi, lo) bf16 planes and multiplied with the weight's planes (W_hi = the sub-block of the plane image; lo plane `wplane` elements behind it)
@@ -169,6 +170,8 @@ int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t
     act_gemm_epilogue_t e = epi0();
     e.bias = w.qkv_b ? w.qkv_b + D : nullptr;                                                   // K,V rows of the qkv Linear
     // (n1p_is_planes: the caller's prompt LayerNorm already left the rows as planes in the activation region)
+    // (kvp_ready: sv.kvp already holds them -- act_prompt_kv_fwd_f32, or the caller's own)
+    if (!kvp_ready)
     CK(linear(TP, 2 * D, D, n1p, w.qkv_w + (size_t)D * D, x3 ? x3->qkv + (size_t)D * D : nullptr, (size_t)3 * D * D, sv.kvp, e,
               (x3_ok && x3->n1p_is_planes) ? tmp_planes : nullptr));
     const bool ln1_planes = x3_ok && x3->qkv && act_sgemm_nt_bf16x3_supported(TG, 3 * D, D);          // LayerNorm-1 hands n1x on as planes (xin stays fp32: residual)
@@ -420,6 +423,41 @@ int act_prefix_block_fwd_f32(const act_block_dims_t* d, int P, const act_block_p
     return prefix_block_core(*d, P, *w, x, pos, n1p, keep, sv, out, ws, wsb, s);
 }
 
+// the same block with the prompts' keys / values given (inference only, nothing kept): kvp [B*P, 2D] from act_prompt_kv_fwd_f32
+int act_prefix_block_fwd_kv_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* x, const float* pos, const float* kvp,
+                                float* saved, float* out, float* ws, size_t wsb, act_stream_t stream) {
+    if (!w || !x || !saved || !out || !kvp) return ACT_E_NULLPTR;
+    if (bad_dims(d) || P <= 0) return ACT_E_BADARG;
+    PrefixSaved sv; carve_prefix(saved, *d, P, sv);
+    sv.kvp = const_cast<float*>(kvp);                                  // read only (kvp_ready)
+    return prefix_block_core(*d, P, *w, x, pos, nullptr, false, sv, out, ws, wsb, (hipStream_t)stream, nullptr, true);
+}
+
+// ============================================================================================== prompt keys / values, dropped terms sparse (prompt_kv.hip)
+static std::atomic<int> g_prompt_kv_sparse{[] { const char* e = getenv("ACT_PROMPT_KV_SPARSE"); return !(e && e[0] == '0') ? 1 : 0; }()};
+int act_prompt_kv_sparse(int on) { return on < 0 ? g_prompt_kv_sparse.load() : g_prompt_kv_sparse.exchange(on ? 1 : 0); }
+size_t act_prompt_kv_workspace(int B, int P, int D, int N) {
+    if (!act_prompt_kv_shape_ok(B, P, D, N)) return 0;
+    ActPromptKvWs w; act_prompt_kv_carve(nullptr, B, P, D, N, w);
+    return w.floats * sizeof(float);
+}
+int act_prompt_kv_fwd_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                          const float* gamma, const float* beta, float eps, const float* W, const float* bias, float* kvp, float* scratch,
+                          size_t scratch_bytes, float* ws, size_t wsb, act_stream_t stream) {
+    if (!tok || !ppos || !gamma || !beta || !W || !kvp) return ACT_E_NULLPTR;
+    if (B < 0 || P <= 0 || D <= 0 || N <= 0 || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
+    if (!g_prompt_kv_sparse.load() || !act_prompt_kv_shape_ok(B ? B : 1, P, D, N) || (reinterpret_cast<uintptr_t>(W) & 15)) return ACT_E_UNSUPPORTED;
+    if (B == 0) return 0;
+    ActPromptKvWs pw; act_prompt_kv_carve(scratch, B, P, D, N, pw);
+    if (!scratch) return ACT_E_NULLPTR;
+    if (scratch_bytes < pw.floats * sizeof(float) || (reinterpret_cast<uintptr_t>(scratch) & 15)) return ACT_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    RUN(act_prompt_kv_rows(tok, ppos, B, P, D, drop_p, seed, seed_dev, gamma, beta, eps, pw, s));
+    CK(gemm_nt(P + 2, N, D, pw.arows, D, W, D, pw.base, N, epi0(), ws, wsb, s));             // base [P], g, c (without the bias)
+    RUN(act_prompt_kv_correct(tok, B, P, D, N, drop_p, gamma, W, bias, pw, kvp, s));
+    return 0;
+}
+
 // OPT-IN: the same forward with the block's four (frozen) weights given as (hi, lo) bf16 planes: every product whose shape the split-bf16 kernel takes runs there
 // (w_planes[0..3] = hi planes of qkv_w, proj_w, fc1_w, fc2_w, lo plane behind each; a_planes as in act_vit_bf16x3_t).  The backward is unchanged (f32).
 int act_prefix_block_fwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const act_vit_bf16x3_t* x3, const float* x, const float* pos,
@@ -507,13 +545,15 @@ int act_prefix_block_bwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_
 
 // ============================================================================================== frozen prompt-tuned Transformer (teacher)
 static size_t carve_vit(float* base, const act_prefix_vit_t& m, float*& pos_h, float*& pos, float*& xa, float*& xb, float*& n1p, float*& blk,
-                        float*& feat) {
+                        float*& feat, float** pkv = nullptr) {
     const size_t TG = (size_t)m.B * m.G, TP = (size_t)m.B * m.P, D = m.D;
     act_block_dims_t d{m.B, m.G, m.D, m.heads, m.hidden, m.eps};
     PrefixSaved sv;
     Carver c(base);
     pos_h = c.take(TG * m.pos_hidden); pos = c.take(TG * D); xa = c.take(TG * D); xb = c.take(TG * D); n1p = c.take(TP * D); feat = c.take(TG * D);
     blk = c.take(carve_prefix(nullptr, d, m.P, sv));
+    float* kv_scratch = c.take(act_prompt_kv_workspace(m.B, m.P, m.D, 2 * m.D) / sizeof(float));      // 0 floats for a shape the sparse form does not take
+    if (pkv) *pkv = kv_scratch;
     return c.used;
 }
 static bool bad_vit(const act_prefix_vit_t* m) {
@@ -543,8 +583,9 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
     if (!tokens || !center || !out || !scratch || !m->blocks || !m->prompt_tok || !m->prompt_pos) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
     const int TG = m->B * m->G, D = m->D;
-    float *pos_h, *pos, *xa, *xb, *n1p, *blk, *feat;
-    carve_vit(scratch, *m, pos_h, pos, xa, xb, n1p, blk, feat);
+    float *pos_h, *pos, *xa, *xb, *n1p, *blk, *feat, *pkv;
+    carve_vit(scratch, *m, pos_h, pos, xa, xb, n1p, blk, feat, &pkv);
+    const size_t pkv_bytes = act_prompt_kv_workspace(m->B, m->P, m->D, 2 * m->D);
     const act_block_dims_t d{m->B, m->G, m->D, m->heads, m->hidden, m->eps};
     PrefixSaved sv; carve_prefix(blk, d, m->P, sv);
     // pos = visual_pos_embed(center): Linear(3, pos_hidden) - GELU - Linear(pos_hidden, D)   (models/dvae.py:413-417)
@@ -558,6 +599,17 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
     for (int i = 0; i < m->depth; ++i) {
         const act_block_params_t& w = m->blocks[i];
         const uint64_t seed = (m->seed_base + 7919ull * (uint64_t)(i + 1)) & ((1ull << 62) - 1);
+        if (!x3) {              // f32 path: base product once, the dropped terms walked sparsely (the split-bf16 opt-in keeps its planes)
+            const int rc = act_prompt_kv_fwd_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
+                                                 m->eps, w.qkv_w + (size_t)D * D, w.qkv_b ? w.qkv_b + D : nullptr, sv.kvp, pkv, pkv_bytes, ws, wsb, stream);
+            if (rc == 0) {
+                (void)collecting(1, 1, m->B * m->P, 2 * D, D);          // the dense product stays tuned: the switch can be turned at run time
+                CK(prefix_block_core(d, m->P, w, cur, pos, nullptr, false, sv, nxt, ws, wsb, s, nullptr, true));
+                float* t = cur; cur = nxt; nxt = t;
+                continue;
+            }
+            if (rc != ACT_E_UNSUPPORTED) return rc;                    // switched off / a shape it does not take: the dense sequence below
+        }
         X3Block xb{};
         if (x3) xb = X3Block{x3->w_planes[4 * i], x3->w_planes[4 * i + 1], x3->w_planes[4 * i + 2], x3->w_planes[4 * i + 3], x3->a_planes, x3->a_planes_elems, false};
         if (x3 && xb.qkv && x3_fits(d, m->P, x3->a_planes_elems) && act_sgemm_nt_bf16x3_supported(m->B * m->P, 2 * D, D)) {

@@ -1221,16 +1221,45 @@ def prompt_layernorm(tok, ppos, B, drop_p, seed, gamma, beta, eps, seed_dev=None
     return y
 
 
-def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, n1p=None):
+_E_UNSUPPORTED = -3
+
+
+def prompt_kv(tok, ppos, B, drop_p, seed, gamma, beta, eps, w, bias=None, seed_dev=None):
+    """LN(dropout(tok) + ppos) . w^T + bias for the B x P prompt rows of one layer of the frozen teacher, [B*P, N]: rows and mask of prompt_layernorm;
+    w [N, D] = the K,V rows of the qkv Linear.  One small product for the cloud-independent part + a sparse walk over the dropped channels
+    (csrc/prompt_kv.hip); a shape that entry does not take, or ACT_PROMPT_KV_SPARSE=0, runs prompt_layernorm + the dense product."""
+    P, D = tok.shape
+    N = w.shape[0]
+    dev = tok.device
+    tok, ppos, w = _f32c(tok), _f32c(ppos), _f32c(w)
+    nbytes = int(lib.act_prompt_kv_workspace(B, P, D, N))
+    if nbytes:
+        gemm_config(True, True, P + 2, N, D, dev, publish=True)                  # the base product's configuration, as the composite path decides it
+        kvp = torch.empty(B * P, N, dtype=torch.float32, device=dev)
+        scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        ws = workspace(dev)
+        rc = lib.act_prompt_kv_fwd_f32(ptr(tok), ptr(ppos), B, P, D, N, float(drop_p), int(seed), ptr(seed_dev), ptr(gamma), ptr(beta), float(eps),
+                                       ptr(w), ptr(bias), ptr(kvp), ptr(scratch), nbytes, ptr(ws), ws.numel() * 4, stream())
+        if rc == 0:
+            return kvp
+        if rc != _E_UNSUPPORTED:
+            check(rc, "act_prompt_kv_fwd_f32")
+    n1p = prompt_layernorm(tok, ppos, B, drop_p, seed, gamma, beta, eps, seed_dev=seed_dev)
+    return gemm(n1p, w, True, True, bias=bias)
+
+
+def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, n1p=None,
+                                   kvp=None):
     """Inference-only pre-LN block on G 'patch' tokens per cloud with P extra 'prompt' tokens that act as keys/values only
     (their outputs are discarded by the caller): x2d [B*G, D] (+ pos2d), prm2d [B*P, D] = prompt + prompt_pos (or n1p = its
-    LayerNorm, already computed by prompt_layernorm).
+    LayerNorm, already computed by prompt_layernorm; or kvp [B*P, 2D] = its keys / values, already computed by prompt_kv).
     Exactly the patch-token rows of  blk(cat(prompt, x) + cat(prompt_pos, pos))  of models/dvae.py:549-571."""
     D = x2d.shape[1]
     hd = D // heads
-    if n1p is None:
-        n1p, _, _, _ = layernorm_fwd(prm2d, None, n1w, n1b, eps, want_stats=False)
-    kvp = gemm(n1p, wqkv[D:], True, True, bias=(bqkv[D:] if bqkv is not None else None))          # K,V of the prompts
+    if kvp is None:
+        if n1p is None:
+            n1p, _, _, _ = layernorm_fwd(prm2d, None, n1w, n1b, eps, want_stats=False)
+        kvp = gemm(n1p, wqkv[D:], True, True, bias=(bqkv[D:] if bqkv is not None else None))          # K,V of the prompts
     n1x, xin, _, _ = layernorm_fwd(x2d, pos2d, n1w, n1b, eps, want_stats=False)
     qkvx = gemm(n1x, wqkv, True, True, bias=bqkv)
     att = attention_fwd_prefix(kvp, P, qkvx, G, B, heads, hd)

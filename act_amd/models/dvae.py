@@ -493,15 +493,15 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
             ppos = self.visual_prompt_pos[0] if i == 0 else self.deep_prompt_pos[i - 1]
             blk = blocks[i]
             a, m = blk.attn, blk.mlp
-            prm = n1p = None
-            if fused:       # dropout (in-kernel Philox) + prompt position + LayerNorm in one launch
-                n1p = K.prompt_layernorm(tok, ppos, B, drop_p, (base + 7919 * (i + 1)) & (2 ** 62 - 1), blk.norm1.weight, blk.norm1.bias,
-                                         blk.eps, seed_dev=ctr)
+            prm = kvp = None
+            if fused:       # dropout (in-kernel Philox) + prompt position + LayerNorm + the K,V rows of the qkv Linear: the entry the composite stack calls
+                kvp = K.prompt_kv(tok, ppos, B, drop_p, (base + 7919 * (i + 1)) & (2 ** 62 - 1), blk.norm1.weight, blk.norm1.bias, blk.eps,
+                                  a.qkv.weight[D:], a.qkv.bias[D:] if a.qkv.bias is not None else None, seed_dev=ctr)
             else:           # injected / recorded dropout masks (parity tests)
                 prm = (self._drop(tok.unsqueeze(0).expand(B, -1, -1), draws, f"prompt.{i}") + ppos).reshape(B * Pn, D)
             x = K.block_forward_prefix(x, pos, prm, B, Pn, G, blk.norm1.weight, blk.norm1.bias, a.qkv.weight, a.qkv.bias,
                                        a.proj.weight, a.proj.bias, blk.norm2.weight, blk.norm2.bias, m.fc1.weight, m.fc1.bias,
-                                       m.fc2.weight, m.fc2.bias, blk.num_heads, blk.eps, n1p=n1p)
+                                       m.fc2.weight, m.fc2.bias, blk.num_heads, blk.eps, kvp=kvp)
         nrm = self.visual_embed[1]
         feature = K.layer_norm(x, nrm.weight, nrm.bias, nrm.eps)
         return K.linear(feature, self.proj_post.weight, self.proj_post.bias).reshape(B, G, -1)

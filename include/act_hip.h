@@ -19,6 +19,7 @@ typedef void* act_stream_t;            /* hipStream_t */
 
 #define ACT_E_BADARG   (-1)            /* shape / size outside what the kernel supports */
 #define ACT_E_NULLPTR  (-2)
+#define ACT_E_UNSUPPORTED (-3)         /* the entry does not take this shape (or is switched off): run the dense sequence instead */
 
 /* ---- library ------------------------------------------------------------------------------ */
 int         act_version(void);
@@ -457,6 +458,20 @@ size_t act_prefix_block_saved_floats(const act_block_dims_t* d, int P);
 int act_prefix_block_fwd_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* x, const float* pos,
                              const float* prm, const float* n1p, int keep_for_backward, float* saved, float* out,
                              float* workspace, size_t workspace_bytes, act_stream_t stream);
+/* The same block, inference only, with the prompts' keys / values kvp [B*P, 2D] given (act_prompt_kv_fwd_f32) instead of prm / n1p. */
+int act_prefix_block_fwd_kv_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* x, const float* pos,
+                                const float* kvp, float* saved, float* out, float* workspace, size_t workspace_bytes, act_stream_t stream);
+/* Keys / values of the frozen teacher's prompt rows without the dense product: kvp [B*P, N] = LN(dropout(tok[p]) + ppos[p]) . W^T + bias with the
+ * rows, the Philox keying and the mask of act_prompt_layernorm_fwd_f32; W [N, D] (16-byte aligned), bias [N] nullable.  The cloud-independent part
+ * (undropped rows, centred on their mean) is ONE (P+2) x N x D product per call; the dropped channels of every row are then walked against a weight
+ * tile held in LDS, in increasing channel order (no atomics: bit-identical runs).  scratch: act_prompt_kv_workspace bytes, 16-byte aligned;
+ * workspace: the GEMM's.  ACT_E_UNSUPPORTED (nothing launched) for D % 4 != 0, a D whose tile does not fit LDS (D > 1240), or when switched off
+ * (ACT_PROMPT_KV_SPARSE=0 / act_prompt_kv_sparse(0)): the caller runs act_prompt_layernorm_fwd_f32 + the dense product. */
+int act_prompt_kv_sparse(int on /* < 0: query */);      /* -> previous setting */
+size_t act_prompt_kv_workspace(int B, int P, int D, int N);      /* bytes; 0 for an unsupported shape */
+int act_prompt_kv_fwd_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed,
+                          const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, const float* W, const float* bias,
+                          float* kvp, float* scratch, size_t scratch_bytes, float* workspace, size_t workspace_bytes, act_stream_t stream);
 size_t act_prefix_block_bwd_scratch_floats(const act_block_dims_t* d, int P);
 int act_prefix_block_bwd_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* prm, const float* saved,
                              const float* dout, float* dx, float* dprm, float* scratch, float* workspace, size_t workspace_bytes,
