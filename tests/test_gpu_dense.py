@@ -537,12 +537,21 @@ def test_attention_prefix_and_teacher_block_prefix(K):
     assert _rel(out, ref) <= 2e-5
 
 
+# Every (JT, QT) the forward instantiates is run by a row here or in test_attention_forward / test_attention_backward (packed, S > 16):
+#   (1,1) (3,96,32)  (1,2) (2,64,64)  (1,3) (1,100,70)  (1,4) S >= 128 packed, (1,64,512), (1,128,200)  (2,1) (1,32,32)  (2,2) S = 33 / 64 packed, (2,20,33), (2,0,40)
+#   (3,2) (2,32,33)  (4,4) S = 100 / 103 packed  and  (3,1) (3,3) (4,3) (4,2) by the last four rows         [rows as (B, S0, Sq)]
 @pytest.mark.parametrize("B,S0,Sq,H,hd", [(2, 20, 33, 3, 64), (2, 64, 64, 12, 64), (3, 8, 16, 2, 32), (1, 100, 70, 2, 64),
                                            (2, 0, 40, 2, 64), (1, 130, 129, 1, 32),
                                            # the register-resident kernels (S0 % 32 == 0, Sq >= 32): shifted tail tiles on either side, both head dims
                                            (2, 64, 40, 2, 64), (2, 32, 33, 2, 64), (1, 64, 104, 3, 32), (1, 64, 512, 2, 64), (3, 96, 32, 1, 64), (5, 0, 63, 2, 32),
                                            # single-pass backward (round 6): two pairs per workgroup with an odd pair count, one key tile, several key blocks with a ragged last one
-                                           (3, 0, 64, 1, 64), (1, 32, 32, 3, 64), (3, 0, 32, 1, 32), (1, 128, 200, 1, 64), (2, 64, 64, 6, 32)])
+                                           (3, 0, 64, 1, 64), (1, 32, 32, 3, 64), (3, 0, 32, 1, 32), (1, 128, 200, 1, 64), (2, 64, 64, 6, 32),
+                                           # forward instantiations (JT, QT) no other row reaches; all five satisfy Sq >= 32 and S0 % 32 == 0, so the backward
+                                           # half runs the single-pass kernel.  Sk = 96 with one query tile: at head_dim 64 four pairs of 96 keys exceed the LDS
+                                           # of a CU (this shape failed to launch) and run as (2,1), at head_dim 32 it is (3,1), no prefetch path; (3,3): Sk = 80,
+                                           # ragged last key and query tile; (4,3): Sk = 112 at head_dim 32, the key chunk straddles the two key segments;
+                                           # (4,2): head_dim 32 only (two pairs of 128 keys pass the 80 KB LDS rule there), Sk = 112
+                                           (2, 64, 32, 2, 64), (2, 64, 32, 2, 32), (2, 0, 80, 2, 64), (1, 32, 80, 2, 32), (1, 64, 48, 2, 32)])
 def test_attention_prefix_backward(K, B, S0, Sq, H, hd):
     """dQ / dK / dV of the own rows and dK / dV of the prefix rows against a float64 reference."""
     kv0 = _rnd(f"pb.kv{S0}{Sq}", B * max(S0, 1), 2 * H * hd)[:B * S0]; qkv = _rnd(f"pb.qkv{S0}{Sq}", B * Sq, 3 * H * hd)
