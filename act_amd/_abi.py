@@ -243,6 +243,18 @@ _TABLE = {
     "act_svm_tprod_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "act_svm_newton_workspace": (_sz, [_i, _i, _i]),
     "act_svm_newton_f32": [_vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    # exact t-SNE of classifier features (csrc/tsne.hip)
+    "act_tsne_knn_workspace": (_sz, [_i, _i]),
+    "act_tsne_knn_cosine_f32": [_vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_tsne_conditional_p_f32": [_vp, _i, _i, _f, _vp, _vp, _vp],
+    "act_tsne_symmetrize_workspace": (_sz, [_i, _i]),
+    "act_tsne_symmetrize_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp, _sz, _vp],
+    "act_tsne_step_workspace": (_sz, [_i]),
+    "act_tsne_step_f32": [_vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_tsne_steps_f32": [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_tsne_kl_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp],
+    "act_tsne_pca_workspace": (_sz, [_i, _i]),
+    "act_tsne_pca_init_f32": [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -1755,3 +1755,126 @@ def svm_newton(x, labels, classes, W, b, istate, dstate, C=1.0, tol=1e-4, max_cg
     ws = _svm_workspace(x.device, lib.act_svm_newton_workspace(N, D, K))
     check(lib.act_svm_newton_f32(ptr(x), ptr(labels), ptr(classes), N, D, K, float(C), float(tol), int(max_cg), ptr(W), ptr(b), ptr(istate),
                                  ptr(dstate), ptr(ws), ws.numel() * 4, stream()), "act_svm_newton_f32")
+
+
+# ---- exact t-SNE of classifier features (csrc/tsne.hip): kNN graph, perplexity search, CSR symmetrisation, steps, KL, PCA initialisation ----------
+TSNE_MAX_NEIGHBORS = 1024
+TSNE_MAX_PCA_DIM = 1024
+
+
+def _tsne_i32(t, shape, name):
+    if not t.is_cuda:
+        raise _C.ActHipError("act_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if t.dtype != torch.int32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise _C.ActHipError(f"{name}: expected int32 {shape if shape is not None else ''}, got {tuple(t.shape)} {t.dtype}")
+    return t.contiguous()
+
+
+def _tsne_state(t, N, name):
+    """Y / update / gains: updated in place, so no copy is made for the caller"""
+    if not t.is_cuda:
+        raise _C.ActHipError("act_amd kernels run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if t.dtype != torch.float32 or tuple(t.shape) != (N, 2) or not t.is_contiguous():
+        raise _C.ActHipError(f"{name}: expected a contiguous float32 [{N}, 2], got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def tsne_knn_cosine(x, k):
+    """x [N,D] -> (idx int32 [N,k], dist [N,k]): the k nearest other rows under 1 - cos, ascending, ties towards the lower index; a zero row
+    has distance 1 to every row"""
+    x = _svm_rows(x, "tsne_knn_cosine x")
+    N, D = x.shape
+    k = int(k)
+    if not 1 <= k <= min(N - 1, TSNE_MAX_NEIGHBORS):
+        raise _C.ActHipError(f"tsne_knn_cosine: k = {k} outside 1 .. min(N - 1, {TSNE_MAX_NEIGHBORS}) for N = {N}")
+    idx = torch.empty(N, k, dtype=torch.int32, device=x.device)
+    dist = torch.empty(N, k, dtype=torch.float32, device=x.device)
+    ws = _svm_workspace(x.device, lib.act_tsne_knn_workspace(N, D))
+    check(lib.act_tsne_knn_cosine_f32(ptr(x), N, D, k, ptr(idx), ptr(dist), ptr(ws), ws.numel() * 4, stream()), "act_tsne_knn_cosine_f32")
+    return idx, dist
+
+
+def tsne_conditional_p(dist, perplexity, want_beta=False):
+    """dist [N,k] -> p [N,k], every row summing to 1 with entropy log(perplexity) (bisection on beta in float64)"""
+    dist = _svm_rows(dist, "tsne_conditional_p dist")
+    N, k = dist.shape
+    p = torch.empty_like(dist)
+    beta = torch.empty(N, dtype=torch.float32, device=dist.device) if want_beta else None
+    check(lib.act_tsne_conditional_p_f32(ptr(dist), N, k, float(perplexity), ptr(p), ptr(beta), stream()), "act_tsne_conditional_p_f32")
+    return (p, beta) if want_beta else p
+
+
+def tsne_symmetrize(idx, p):
+    """idx int32 [N,k], p [N,k] -> CSR (indptr int32 [N+1], indices int32 [nnz], values [nnz]) of (P + P^T) / 2N, columns ascending within a row.
+    One host read: the number of entries"""
+    p = _svm_rows(p, "tsne_symmetrize p")
+    N, k = p.shape
+    idx = _tsne_i32(idx, (N, k), "tsne_symmetrize idx")
+    cap = 2 * N * k
+    indptr = torch.empty(N + 1, dtype=torch.int32, device=p.device)
+    indices = torch.empty(cap, dtype=torch.int32, device=p.device)
+    values = torch.empty(cap, dtype=torch.float32, device=p.device)
+    ws = _svm_workspace(p.device, lib.act_tsne_symmetrize_workspace(N, k))
+    check(lib.act_tsne_symmetrize_f32(ptr(idx), ptr(p), N, k, ptr(indptr), ptr(indices), ptr(values), cap, ptr(ws), ws.numel() * 4, stream()),
+          "act_tsne_symmetrize_f32")
+    nnz = int(indptr[N])
+    return indptr, indices[:nnz].clone(), values[:nnz].clone()
+
+
+def _tsne_csr(csr, N, name):
+    indptr, indices, values = csr
+    indptr = _tsne_i32(indptr, (N + 1,), name + " indptr")
+    indices = _tsne_i32(indices, None, name + " indices")
+    if values.dtype != torch.float32 or values.shape != indices.shape or not values.is_cuda:
+        raise _C.ActHipError(f"{name}: values must be float32 {tuple(indices.shape)} on the device")
+    return indptr, indices, values.contiguous()
+
+
+def tsne_steps(csr, Y, update, gains, n, exaggeration, momentum, lr):
+    """n optimisation steps inside one C call, in place on Y, update, gains [N,2]; nothing is read back"""
+    N = Y.shape[0]
+    indptr, indices, values = _tsne_csr(csr, N, "tsne_steps")
+    for t, nm in ((Y, "Y"), (update, "update"), (gains, "gains")):
+        _tsne_state(t, N, "tsne_steps " + nm)
+    ws = _svm_workspace(Y.device, lib.act_tsne_step_workspace(N))
+    check(lib.act_tsne_steps_f32(ptr(indptr), ptr(indices), ptr(values), N, int(n), float(exaggeration), float(momentum), float(lr), ptr(Y),
+                                 ptr(update), ptr(gains), ptr(ws), ws.numel() * 4, stream()), "act_tsne_steps_f32")
+    return Y
+
+
+def tsne_step(csr, Y, update, gains, exaggeration, momentum, lr):
+    """one optimisation step (exact all-pairs repulsion, attraction along the CSR rows, gains, momentum, centring), in place"""
+    N = Y.shape[0]
+    indptr, indices, values = _tsne_csr(csr, N, "tsne_step")
+    for t, nm in ((Y, "Y"), (update, "update"), (gains, "gains")):
+        _tsne_state(t, N, "tsne_step " + nm)
+    ws = _svm_workspace(Y.device, lib.act_tsne_step_workspace(N))
+    check(lib.act_tsne_step_f32(ptr(indptr), ptr(indices), ptr(values), N, float(exaggeration), float(momentum), float(lr), ptr(Y), ptr(update),
+                                ptr(gains), ptr(ws), ws.numel() * 4, stream()), "act_tsne_step_f32")
+    return Y
+
+
+def tsne_kl(csr, Y, out=None):
+    """KL(P || Q) of the embedding Y [N,2] -> one device double (read it when the number is wanted)"""
+    N = Y.shape[0]
+    indptr, indices, values = _tsne_csr(csr, N, "tsne_kl")
+    _tsne_state(Y, N, "tsne_kl Y")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=Y.device)
+    ws = _svm_workspace(Y.device, lib.act_tsne_step_workspace(N))
+    check(lib.act_tsne_kl_f32(ptr(indptr), ptr(indices), ptr(values), ptr(Y), N, ptr(out), ptr(ws), ws.numel() * 4, stream()), "act_tsne_kl_f32")
+    return out
+
+
+def tsne_pca_init(x, want_info=False):
+    """x [N,D] -> Y0 [N,2]: projection on the two leading principal axes, column 0 scaled to standard deviation 1e-4.  info float64 [4]: the two
+    eigenvalues of the centred Gram matrix, the sweeps of the orthogonal iteration, its last subspace change"""
+    x = _svm_rows(x, "tsne_pca_init x")
+    N, D = x.shape
+    if not 2 <= D <= TSNE_MAX_PCA_DIM or N < 2:
+        raise _C.ActHipError(f"tsne_pca_init: needs N >= 2 and 2 <= D <= {TSNE_MAX_PCA_DIM}, got {tuple(x.shape)}")
+    Y = torch.empty(N, 2, dtype=torch.float32, device=x.device)
+    info = torch.empty(4, dtype=torch.float64, device=x.device)
+    ws = _svm_workspace(x.device, lib.act_tsne_pca_workspace(N, D))
+    check(lib.act_tsne_pca_init_f32(ptr(x), N, D, ptr(Y), ptr(info), ptr(ws), ws.numel() * 4, stream()), "act_tsne_pca_init_f32")
+    return (Y, info) if want_info else Y

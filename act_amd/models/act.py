@@ -392,6 +392,15 @@ class PointTransformer(nn.Module):
         return K.linear(x, h[8].weight, h[8].bias)
 
     def forward(self, pts, draws=None):
+        return self._head(self._concat_f(pts, draws), draws)
+
+    def forward_features(self, pts):
+        """-> (logits, concat_f): the classifier's output and the [B, 2 embed_dim] feature cat(cls, max over tokens) its head reads, from one
+        forward (what the reference's t-SNE runner asks of ``model(points, True)``)"""
+        f = self._concat_f(pts, None)
+        return self._head(f, None), f
+
+    def _concat_f(self, pts, draws):
         neighborhood, center = self.group_divider(pts)
         tokens = self.encoder(neighborhood)                                                 # B G C
         if not isinstance(self.reduce_dim, nn.Identity):
@@ -410,7 +419,7 @@ class PointTransformer(nn.Module):
             a = torch.sigmoid(self.side_alpha)
             patch = a * patch + (1 - a) * side
         pooled = K.group_max(patch.reshape(B * G, C), G)                                    # max over the G tokens of a cloud
-        return self._head(torch.cat((x[:, 0], pooled), dim=-1), draws)
+        return torch.cat((x[:, 0], pooled), dim=-1)
 
 
 @MODELS.register_module()

@@ -680,6 +680,47 @@ size_t act_svm_newton_workspace(int N, int D, int K);
 int act_svm_newton_f32(const float* X, const int64_t* labels, const int64_t* classes, int N, int D, int K, float C, float tol, int max_cg,
                        float* W, float* b, int32_t* istate, double* dstate, void* workspace, size_t workspace_bytes, act_stream_t stream);
 
+/* ---- exact t-SNE of classifier features (csrc/tsne.hip) ------------------------------------------------------------------------------
+ * tools/runner_tsne.py: openTSNE's TSNE(perplexity=25, metric="cosine") on the concat_f features.  Here: the exact objective (no Barnes-Hut,
+ * no interpolation), every stage on the device.  Every reduction has a fixed order (float64 wherever many terms meet); the only atomics are
+ * integer counters whose order a sort removes: all outputs are bit-identical run to run.  Workspaces are 16-byte aligned.
+ *
+ * kNN graph under the cosine distance 1 - x^_i . x^_j (x^ = x / |x|; a row of zero norm has x^ = 0, i.e. distance 1 to every row): for every
+ * row of X fp32 [N,D] its k nearest OTHER rows, idx int32 [N,k] and dist fp32 [N,k] in ascending distance, ties towards the lower index.
+ * 1 <= k <= min(N - 1, 1024).  Distances are formed in slabs of 512 rows: no N x N matrix exists. */
+size_t act_tsne_knn_workspace(int N, int D);
+int act_tsne_knn_cosine_f32(const float* X, int N, int D, int k, int32_t* idx, float* dist, void* workspace, size_t workspace_bytes,
+                            act_stream_t stream);
+/* conditional p fp32 [N,k] from dist fp32 [N,k]: per row the beta at which the entropy of p_j ~ exp(-beta (d_j - d_min)) equals
+ * log(perplexity), by bisection in float64 (beta doubles while the upper bound is open, halves while the lower one is), until
+ * |H - log perplexity| < 1e-5 or 100 steps; every row sums to 1.  beta fp32 [N] may be NULL. */
+int act_tsne_conditional_p_f32(const float* dist, int N, int k, float perplexity, float* p, float* beta, act_stream_t stream);
+/* P = (P_cond + P_cond^T) / 2N as CSR: indptr int32 [N + 1], indices (ascending within a row) and values with room for `capacity` >= 2 N k
+ * entries; indptr[N] entries are written.  count -> scan -> fill through the sorted inverse adjacency. */
+size_t act_tsne_symmetrize_workspace(int N, int k);
+int act_tsne_symmetrize_f32(const int32_t* idx, const float* p, int N, int k, int32_t* indptr, int32_t* indices, float* values,
+                            long long capacity, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* one optimisation step, in place on Y, update and gains (fp32 [N,2] each), nothing read back:
+ *   w_ij = 1 / (1 + |y_i - y_j|^2),  Z = sum_{i != j} w_ij,  g_i = exaggeration sum_j P_ij w_ij (y_i - y_j) - (1/Z) sum_j w_ij^2 (y_i - y_j)
+ *   gain += 0.2 where sign(g) != sign(update) else gain *= 0.8, floor 0.01;  update = momentum update - lr gain g;  Y += update;  Y -= mean(Y).
+ * The repulsive term and Z are the exact sweep over all pairs.  act_tsne_steps_f32 runs n_steps such steps in one call (the same launches:
+ * bit-identical to n_steps single calls). */
+size_t act_tsne_step_workspace(int N);
+int act_tsne_step_f32(const int32_t* indptr, const int32_t* indices, const float* values, int N, float exaggeration, float momentum, float lr,
+                      float* Y, float* update, float* gains, void* workspace, size_t workspace_bytes, act_stream_t stream);
+int act_tsne_steps_f32(const int32_t* indptr, const int32_t* indices, const float* values, int N, int n_steps, float exaggeration,
+                       float momentum, float lr, float* Y, float* update, float* gains, void* workspace, size_t workspace_bytes,
+                       act_stream_t stream);
+/* out[0] (one device double) = KL(P || Q) = sum_ij P_ij log(P_ij / (w_ij / Z)), accumulated in float64; workspace: act_tsne_step_workspace */
+int act_tsne_kl_f32(const int32_t* indptr, const int32_t* indices, const float* values, const float* Y, int N, double* out, void* workspace,
+                    size_t workspace_bytes, act_stream_t stream);
+/* PCA initialisation Y fp32 [N,2]: centred features, covariance by the TN GEMM, its two leading eigenvectors by orthogonal iteration in float64
+ * (one workgroup; until the subspace moves by less than 1e-10 or 500 sweeps) and a Rayleigh-Ritz rotation, each signed so that its
+ * largest-magnitude entry is positive; the projection is scaled so that column 0 has standard deviation 1e-4.  2 <= D <= 1024.
+ * info float64 [4]: the two eigenvalues of X_c^T X_c, the sweeps run, the last subspace change. */
+size_t act_tsne_pca_workspace(int N, int D);
+int act_tsne_pca_init_f32(const float* X, int N, int D, float* Y, double* info, void* workspace, size_t workspace_bytes, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
