@@ -255,6 +255,11 @@ _TABLE = {
     "act_tsne_kl_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp],
     "act_tsne_pca_workspace": (_sz, [_i, _i]),
     "act_tsne_pca_init_f32": [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    # frozen post-LayerNorm language teacher (csrc/bert.hip)
+    "act_dropout_add_layernorm_fwd_f32": [_vp, _vp, _vp, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp],
+    "act_dropout_add_layernorm_bwd_f32": [_vp, _vp, _vp, _i, _i, _f, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "act_attention_dropout_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _u64, _vp, _vp],
+    "act_attention_dropout_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _u64, _vp, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

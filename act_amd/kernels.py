@@ -1878,3 +1878,110 @@ def tsne_pca_init(x, want_info=False):
     ws = _svm_workspace(x.device, lib.act_tsne_pca_workspace(N, D))
     check(lib.act_tsne_pca_init_f32(ptr(x), N, D, ptr(Y), ptr(info), ptr(ws), ws.numel() * 4, stream()), "act_tsne_pca_init_f32")
     return (Y, info) if want_info else Y
+
+
+# ---- frozen post-LayerNorm language teacher (csrc/bert.hip) ---------------------------------------------------------------------------
+def dropout_add_layernorm_fwd(t, res, gamma, beta, eps, p=0.0, seed=0, mask=None, seed_dev=None, want_rstd=True):
+    """y = LN(keep o t / (1-p) + res) * gamma + beta on rows [T, D]; keep: ``mask`` (0/1 floats [T, D]) or in-kernel Philox(seed, seed_dev)."""
+    t, res = _f32c(t), _f32c(res)
+    T, D = t.shape
+    mask = _f32c(mask).reshape(T, D) if (mask is not None and p > 0) else None
+    y = torch.empty_like(t)
+    rstd = torch.empty(T, dtype=torch.float32, device=t.device) if want_rstd else None
+    check(lib.act_dropout_add_layernorm_fwd_f32(ptr(t), ptr(res), ptr(mask), T, D, float(p), int(seed), ptr(seed_dev), ptr(gamma), ptr(beta),
+                                                float(eps), ptr(y), ptr(rstd), stream()), "act_dropout_add_layernorm_fwd_f32")
+    return y, rstd
+
+
+def dropout_add_layernorm_bwd(dy, y, gamma, beta, rstd, p=0.0, seed=0, mask=None, seed_dev=None):
+    """-> (dt, dres) of dropout_add_layernorm_fwd; the mask is regenerated from its key (or the given one), the normalised row from y."""
+    dy = _f32c(dy)
+    T, D = dy.shape
+    mask = _f32c(mask).reshape(T, D) if (mask is not None and p > 0) else None
+    dt, dres = torch.empty_like(dy), torch.empty_like(dy)
+    check(lib.act_dropout_add_layernorm_bwd_f32(ptr(dy), ptr(y), ptr(mask), T, D, float(p), int(seed), ptr(seed_dev), ptr(gamma), ptr(beta),
+                                                ptr(rstd), ptr(dt), ptr(dres), stream()), "act_dropout_add_layernorm_bwd_f32")
+    return dt, dres
+
+
+def _attn_mask_u8(mask, B, S, H):
+    if mask is None:
+        return None
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, H, S, S):
+        raise _C.ActHipError(f"attention dropout mask: expected uint8 [{B}, {H}, {S}, {S}], got {mask.dtype} {tuple(mask.shape)}")
+    return mask.contiguous()
+
+
+def attention_dropout_fwd(qkv, B, S, H, hd, p, seed=0, mask=None, seed_dev=None, want_lse=True):
+    """out = (softmax(q k^t hd^-1/2) o keep / (1-p)) v on packed qkv [B,S,3,H,hd]; keep: ``mask`` (uint8 [B,H,S,S]) or in-kernel Philox."""
+    out = torch.empty(B * S, H * hd, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device) if want_lse else None
+    check(lib.act_attention_dropout_fwd_f32(ptr(qkv), ptr(_attn_mask_u8(mask, B, S, H)), ptr(out), ptr(lse), B, S, H, hd, float(hd) ** -0.5, float(p),
+                                            int(seed), ptr(seed_dev), stream()), "act_attention_dropout_fwd_f32")
+    return out, lse
+
+
+def attention_dropout_bwd(qkv, out, dout, lse, B, S, H, hd, p, seed=0, mask=None, seed_dev=None):
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, S, dtype=torch.float32, device=qkv.device)
+    check(lib.act_attention_dropout_bwd_f32(ptr(qkv), ptr(_attn_mask_u8(mask, B, S, H)), ptr(out), ptr(_f32c(dout)), ptr(lse), ptr(delta), ptr(dqkv),
+                                            B, S, H, hd, float(hd) ** -0.5, float(p), int(seed), ptr(seed_dev), stream()),
+          "act_attention_dropout_bwd_f32")
+    return dqkv
+
+
+class BertLayerFn(torch.autograd.Function):
+    """One FROZEN post-LayerNorm (BERT) layer on x [B,S,D] (reference models/dvae.py:753-754 through transformers' BertLayer):
+
+        qkv = x Wqkv + b ; ctx = (dropout_pa(softmax(q k^t hd^-1/2))) v ; a = LN(dropout_ph(ctx Wo + bo) + x) ; y = LN(dropout_ph(gelu(a Wi + bi) Wo2 + bo2) + a)
+
+    seeds = (attention, hidden1, hidden2) Philox seeds, masks = the same three as injected keep masks (uint8 [B,H,S,S], floats [B,S,D] twice) or None
+    each; seed_dev: the device-resident counter of the no_grad teacher path.  Kept for the backward: qkv, ctx, lse, a, the GELU input, y (the
+    normalised rows come back from a and y), the two rstd vectors and the seeds (injected masks as given) -- no mask is stored.  The backward produces the
+    input gradient only: the weights are frozen.  Under no_grad nothing is kept.  At p_attn == 0 the attention is act_attention_fwd_f32 / _bwd_f32."""
+
+    @staticmethod
+    def forward(ctx, x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps, p_attn, p_hidden, seeds, masks, seed_dev):
+        B, S, D = x.shape
+        hd = D // heads
+        x2 = _f32c(x).reshape(B * S, D)
+        need_grad = ctx.needs_input_grad[0]
+        m_attn, m_h1, m_h2 = masks if masks is not None else (None, None, None)
+        qkv = gemm(x2, wqkv, True, True, bias=bqkv)
+        if p_attn > 0:
+            att, lse = attention_dropout_fwd(qkv, B, S, heads, hd, p_attn, seeds[0], m_attn, seed_dev, want_lse=need_grad)
+        else:
+            att, lse = attention_fwd(qkv, B, S, heads, hd, want_lse=need_grad)
+        t1 = gemm(att, wo, True, True, bias=bo)
+        a, rstd1 = dropout_add_layernorm_fwd(t1, x2, g1, b1, eps, p_hidden, seeds[1], m_h1, seed_dev, want_rstd=need_grad)
+        hpre = torch.empty(B * S, wi.shape[0], dtype=torch.float32, device=x.device) if need_grad else None
+        h = gemm(a, wi, True, True, bias=bi, act=EPI_GELU, aux=hpre)
+        t2 = gemm(h, wo2, True, True, bias=bo2)
+        y, rstd2 = dropout_add_layernorm_fwd(t2, a, g2, b2, eps, p_hidden, seeds[2], m_h2, seed_dev, want_rstd=need_grad)
+        if need_grad:
+            ctx.save_for_backward(qkv, att, lse, a, hpre, y, rstd1, rstd2, wqkv, wo, g1, b1, wi, wo2, g2, b2, m_attn,
+                                  m_h1 if p_hidden > 0 else None, m_h2 if p_hidden > 0 else None, seed_dev)
+            ctx.cfg = (B, S, D, heads, hd, float(p_attn), float(p_hidden), tuple(int(s) for s in seeds))
+        return y.reshape(B, S, D)
+
+    @staticmethod
+    def backward(ctx, dy):
+        qkv, att, lse, a, hpre, y, rstd1, rstd2, wqkv, wo, g1, b1, wi, wo2, g2, b2, m_attn, m_h1, m_h2, seed_dev = ctx.saved_tensors
+        B, S, D, heads, hd, p_attn, p_hidden, seeds = ctx.cfg
+        dy2 = _f32c(dy).reshape(B * S, D)
+        dt2, dres2 = dropout_add_layernorm_bwd(dy2, y, g2, b2, rstd2, p_hidden, seeds[2], m_h2, seed_dev)
+        dh = gemm(dt2, wo2, True, False, act=EPI_MUL_GELU_GRAD, aux=hpre)
+        da = gemm(dh, wi, True, False, res=dres2)                       # + the residual branch of the second LayerNorm
+        dt1, dres1 = dropout_add_layernorm_bwd(da, a, g1, b1, rstd1, p_hidden, seeds[1], m_h1, seed_dev)
+        datt = gemm(dt1, wo, True, False)
+        if p_attn > 0:
+            dqkv = attention_dropout_bwd(qkv, att, datt, lse, B, S, heads, hd, p_attn, seeds[0], m_attn, seed_dev)
+        else:
+            dqkv = attention_bwd(qkv, att, datt, lse, B, S, heads, hd)
+        dx = gemm(dqkv, wqkv, True, False, res=dres1)
+        return (dx.reshape(B, S, D),) + (None,) * 19
+
+
+def bert_layer(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps=1e-12, p_attn=0.0, p_hidden=0.0, seeds=(0, 0, 0), masks=None,
+               seed_dev=None):
+    return BertLayerFn.apply(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps, p_attn, p_hidden, seeds, masks, seed_dev)

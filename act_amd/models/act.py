@@ -13,7 +13,9 @@ from .. import kernels as K
 from ..utils.draws import Draws
 from ..utils.logger import print_log
 from .build import MODELS
-from .dvae import Group, Encoder, ACTPromptedDiscreteVAEwithVIT, trunc_normal_
+from .dvae import Group, Encoder, ACTPromptedDiscreteVAEwithVIT, ACTPromptedDiscreteVAEwithBERT, trunc_normal_
+
+_TEACHERS = {c.__name__: c for c in (ACTPromptedDiscreteVAEwithVIT, ACTPromptedDiscreteVAEwithBERT)}
 
 
 import os
@@ -469,7 +471,11 @@ class ACT_PointDistillation(nn.Module):
             raise NotImplementedError(f"loss: {self.loss_type!r} -- the reference knows 'cosine' (the ACT recipe), 'l2', 'smoothl1', 'ntxent' and 'barlow'")
 
     def build_tokenizer(self, cfg):
-        self.dvae_tokenizer = ACTPromptedDiscreteVAEwithVIT(cfg)
+        # optional dvae_config.NAME (absent from the reference YAML): which registered prompt-tuned tokenizer teaches -- the image one unless told otherwise
+        name = cfg.get("NAME", None) or "ACTPromptedDiscreteVAEwithVIT"
+        if name not in _TEACHERS:
+            raise KeyError(f"dvae_config.NAME: {name!r} -- the teachers are {sorted(_TEACHERS)}")
+        self.dvae_tokenizer = _TEACHERS[name](cfg)
         dvae_ckpt = cfg.get("ckpt", None)
         if dvae_ckpt and str(dvae_ckpt).lower() not in ("none", "random", ""):
             ckpt = torch.load(dvae_ckpt, map_location='cpu')

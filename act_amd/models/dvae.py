@@ -552,3 +552,206 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
         nrm = self.visual_embed[1]
         feature = K.layer_norm(hidden[:, Pn:].contiguous(), nrm.weight, nrm.bias, nrm.eps)
         return K.linear(feature, self.proj_post.weight, self.proj_post.bias)
+
+
+class _BertLayerParams(nn.Module):
+    """parameter container of one transformers ``BertLayer``, its key names and order (attention.self.{query,key,value}, attention.output.{dense,
+    LayerNorm}, intermediate.dense, output.{dense,LayerNorm}); the arithmetic is K.bert_layer."""
+
+    def __init__(self, dim, heads, intermediate, eps=1e-12, p_attn=0.1, p_hidden=0.1):
+        super().__init__()
+        self.num_heads, self.eps, self.p_attn, self.p_hidden = heads, eps, p_attn, p_hidden
+        self.attention = nn.Module()
+        setattr(self.attention, "self", nn.Module())
+        att = getattr(self.attention, "self")
+        att.query, att.key, att.value = nn.Linear(dim, dim), nn.Linear(dim, dim), nn.Linear(dim, dim)
+        self.attention.output = nn.Module()
+        self.attention.output.dense = nn.Linear(dim, dim)
+        self.attention.output.LayerNorm = nn.LayerNorm(dim, eps=eps)
+        self.intermediate = nn.Module()
+        self.intermediate.dense = nn.Linear(dim, intermediate)
+        self.output = nn.Module()
+        self.output.dense = nn.Linear(intermediate, dim)
+        self.output.LayerNorm = nn.LayerNorm(dim, eps=eps)
+
+    def qkv(self):
+        """the concatenated [3D, D] weight and [3D] bias of the packed q/k/v product, built once and rebuilt only when a weight changes"""
+        att = getattr(self.attention, "self")
+        ps = (att.query.weight, att.key.weight, att.value.weight, att.query.bias, att.key.bias, att.value.bias)
+        key = tuple((p.data_ptr(), p._version, p.device) for p in ps)
+        cache = self.__dict__.get("_act_qkv")
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                cache = (key, torch.cat(ps[:3], dim=0).contiguous(), torch.cat(ps[3:], dim=0).contiguous())
+            self.__dict__["_act_qkv"] = cache
+        return cache[1], cache[2]
+
+    def forward(self, x, p_attn, p_hidden, seeds, masks, seed_dev):
+        wqkv, bqkv = self.qkv()
+        ao, o = self.attention.output, self.output
+        return K.bert_layer(x, wqkv, bqkv, ao.dense.weight, ao.dense.bias, ao.LayerNorm.weight, ao.LayerNorm.bias, self.intermediate.dense.weight,
+                            self.intermediate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight, o.LayerNorm.bias, self.num_heads, self.eps,
+                            p_attn, p_hidden, seeds, masks, seed_dev)
+
+
+class _BertEncoderParams(nn.Module):
+    """``BertModel.encoder``: ``layer.{i}``"""
+
+    def __init__(self, dim, heads, intermediate, depth):
+        super().__init__()
+        self.layer = nn.ModuleList([_BertLayerParams(dim, heads, intermediate) for _ in range(depth)])
+
+
+_BERT_GEOMETRY = {"bert-base-uncased": (12, 12, 3072), "bert-base-cased": (12, 12, 3072), "bert-large-uncased": (24, 16, 4096)}     # depth, heads, intermediate
+
+
+@MODELS.register_module()
+class ACTPromptedDiscreteVAEwithBERT(DiscreteVAE):
+    """The language teacher (models/dvae.py:617-857): DiscreteVAE with a prompt-tuned, FROZEN BERT encoder between the codebook lookup and dgcnn_2.
+
+    ``visual_embed = nn.Sequential(BertModel.encoder)`` is represented by a parameter container with transformers' key names
+    (``visual_embed.0.layer.{i}.…``), so a reference checkpoint loads with ``strict=True``; ``transformers`` is never imported and nothing is ever
+    fetched: the weights come from the dVAE checkpoint or from the optional local ``visual_embed_ckpt`` (a ``BertModel``'s or its encoder's
+    ``state_dict``), else they are random and the class says so.  What the reference computes, and this class with it:
+      * shallow prompts only -- ``pos`` is added ONCE before the first layer, prompts are prepended once, flow through all layers as full tokens and are
+        cut off at the end; there is no final norm.  ``use_deep_prompt: True`` crashes in the reference; here the deep parameters are created (they are
+        part of the ``state_dict``) and the forward raises ValueError;
+      * a BERT layer is post-LayerNorm with two dropouts (attention probabilities, hidden states; 0.1 each) that follow ``module.training``: live in
+        Stage-I training and in the Stage-II teacher forward (no_grad, train mode), off under ``.eval()``;
+      * ``forward_tokenizer_features`` defaults to ``return_global=False``.
+    ACT never trains the teacher: ``freeze_visual_embed: False`` raises NotImplementedError.  Config keys beyond the reference's:
+    ``visual_embed_depth`` / ``visual_embed_heads`` / ``visual_embed_intermediate`` (geometry; bert-base by default) and ``visual_embed_ckpt``."""
+
+    def __init__(self, config, **kwargs):
+        super().__init__(config)
+        self.visual_embed_type = config.visual_embed_type
+        self.visual_embed_dim = config.visual_embed_dim
+        self.freeze_visual_embed = config.freeze_visual_embed
+        self.num_prompt_token = config.num_prompt_token
+        self.use_deep_prompt = config.use_deep_prompt
+        if self.visual_embed_dim != 'none' and not self.freeze_visual_embed:
+            raise NotImplementedError("freeze_visual_embed: False -- training the language model's own weights is not built (ACT's recipe never trains "
+                                      "the teacher Transformer; only prompts and projections learn)")
+        self.build_visual_embedding(config)
+
+    def build_visual_embedding(self, config):
+        if self.visual_embed_dim == 'none':
+            self.visual_embed = None
+            return
+        depth, heads, inter = _BERT_GEOMETRY.get(self.visual_embed_type, (12, 12, 3072))
+        depth = int(config.get("visual_embed_depth", depth))
+        heads = int(config.get("visual_embed_heads", heads))
+        inter = int(config.get("visual_embed_intermediate", inter))
+        D = self.visual_embed_dim
+        if D % heads or D // heads not in (32, 64):
+            raise ValueError(f"visual_embed_dim {D} / visual_embed_heads {heads}: the attention kernels take head dimensions 32 and 64")
+        self.visual_embed = nn.Sequential(_BertEncoderParams(D, heads, inter, depth))
+        self.visual_embed_depth = depth
+        self.proj_pre = nn.Linear(self.tokens_dims, D)
+        self.visual_pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, D))
+        self.proj_post = nn.Linear(D, self.tokens_dims)
+        Pn = self.num_prompt_token
+        if Pn > 0:
+            self.visual_prompt_proj = nn.Identity()
+            self.prompt_dropout = nn.Dropout(0.1)
+            self.visual_prompt_token = nn.Parameter(torch.zeros(1, Pn, D))
+            self.visual_prompt_pos = nn.Parameter(torch.randn(1, Pn, D))
+            trunc_normal_(self.visual_prompt_token, std=.02)
+            trunc_normal_(self.visual_prompt_pos, std=.02)
+            if self.use_deep_prompt:                                   # created as the reference does (:682-689); no forward uses them
+                self.deep_prompt_tokens = nn.Parameter(torch.zeros(depth - 1, Pn, D))
+                self.deep_prompt_pos = nn.Parameter(torch.randn(depth - 1, Pn, D))
+                trunc_normal_(self.deep_prompt_tokens, std=.02)
+                trunc_normal_(self.deep_prompt_pos, std=.02)
+        else:
+            self.visual_prompt_token = None
+        ckpt = config.get("visual_embed_ckpt", None)
+        if ckpt and str(ckpt).lower() not in ("none", "random", ""):
+            self.load_language_model(ckpt)
+        else:
+            import warnings
+            warnings.warn("ACTPromptedDiscreteVAEwithBERT: no visual_embed_ckpt -- the language model is RANDOMLY INITIALISED unless a dVAE checkpoint "
+                          "that contains it is loaded afterwards.  Real Stage-I training must point visual_embed_ckpt at a local BertModel (or "
+                          "BertModel.encoder) state_dict of " + str(self.visual_embed_type) + "; nothing is ever downloaded.", stacklevel=2)
+        for param in self.visual_embed.parameters():
+            param.requires_grad = False
+
+    def load_language_model(self, path):
+        """``path``: a local ``state_dict`` file of a ``BertModel`` (``encoder.layer.*``, possibly behind ``bert.``) or of its encoder (``layer.*``)"""
+        sd = torch.load(path, map_location='cpu')
+        sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
+        enc = {}
+        for k, v in sd.items():
+            i = k.find("layer.")
+            if i >= 0 and (i == 0 or k[:i] in ("encoder.", "bert.encoder.")):
+                enc[k[i:]] = v
+        self.visual_embed[0].load_state_dict(enc, strict=True)
+
+    # ---- random draws ------------------------------------------------------------------------------
+    def _layer_draws(self, i, B, S, D, H, p_attn, p_hidden, draws, device):
+        """-> (masks or None, seeds) of layer i: injected / recorded keep masks when ``draws`` carries or records them, host-drawn Philox seeds else"""
+        keys = (f"bert.{i}.attn", f"bert.{i}.hidden1", f"bert.{i}.hidden2")
+        if draws is not None and (draws.record or any(draws.has(k) for k in keys)):
+            shapes, ps = ((B, H, S, S), (B, S, D), (B, S, D)), (p_attn, p_hidden, p_hidden)
+            ms = [draws.get(k, lambda s=s, p=p: (torch.rand(s, device=device) >= p)) if p > 0 else None for k, s, p in zip(keys, shapes, ps)]
+            return (ms[0].to(torch.uint8) if ms[0] is not None else None, ms[1].to(torch.float32) if ms[1] is not None else None,
+                    ms[2].to(torch.float32) if ms[2] is not None else None), (0, 0, 0)
+        return None, None
+
+    def _encode(self, x, draws=None, rng=None):
+        """the BertEncoder on x [B,S,D] (already x + pos): every layer one K.BertLayerFn"""
+        B, S, D = x.shape
+        layers = self.visual_embed[0].layer
+        frozen_path = rng is not None                                   # the no_grad teacher forward (forward_tokenizer_features) hands its stream down
+        seeds_host = None
+        base, ctr = rng if frozen_path else (None, None)
+        for i, lyr in enumerate(layers):
+            p_attn = lyr.p_attn if self.training else 0.0
+            p_hidden = lyr.p_hidden if self.training else 0.0
+            masks, seeds = (None, (0, 0, 0))
+            seed_dev = None
+            if p_attn > 0 or p_hidden > 0:
+                masks, seeds = self._layer_draws(i, B, S, D, lyr.num_heads, p_attn, p_hidden, draws, x.device)
+                if seeds is None:
+                    if frozen_path:                                    # teacher forward: base seed + device counter (fresh masks per captured replay)
+                        seeds = tuple((base + 7919 * (3 * i + j + 1) + 0x3c6ef372) & (2 ** 62 - 1) for j in range(3))
+                        seed_dev = ctr
+                    else:
+                        if seeds_host is None:                         # host RNG, one draw for the stack: no device sync
+                            seeds_host = torch.randint(0, 2 ** 62, (3 * len(layers),)).tolist()
+                        seeds = tuple(seeds_host[3 * i:3 * i + 3])
+            x = lyr(x, p_attn, p_hidden, seeds, masks, seed_dev)
+        return x
+
+    def _prompt_rows(self, B, draws):
+        """dropout(prompt tokens) + prompt positions for every cloud, [B, Pn, D] (incorporate_prompt :738-751), one HIP launch per direction"""
+        tok, ppos = self.visual_prompt_token[0], self.visual_prompt_pos[0]
+        p = self.prompt_dropout.p if self.training else 0.0
+        mask = None
+        if p > 0 and draws is not None and (draws.has("prompt.0") or draws.record):
+            shape = (B,) + tuple(tok.shape)
+            mask = draws.get("prompt.0", lambda: (torch.rand(shape, device=tok.device) >= p)).to(tok.dtype)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (p > 0 and mask is None) else 0       # host RNG: no device sync
+        return K.prompt_rows(tok, ppos, B, p, seed, mask).view(B, tok.shape[0], tok.shape[1])
+
+    def visual_embedding(self, input, center, draws=None, rng=None):
+        """models/dvae.py:756-777"""
+        if self.use_deep_prompt:
+            raise ValueError("use_deep_prompt: True has no forward with a BERT teacher (the reference fails on it too: 'BertEncoder' object is not "
+                             "subscriptable); only the shallow prompt form exists")
+        if self.visual_embed is None:
+            return input
+        vp = self.visual_pos_embed
+        pos = K.mlp(center, vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias)
+        feature = K.linear(input, self.proj_pre.weight, self.proj_pre.bias)
+        if self.visual_prompt_token is None:
+            with torch.no_grad():                                      # frozen and promptless: nothing upstream receives a gradient (:766-768)
+                feature = self._encode(feature + pos, draws, rng)
+        else:
+            Pn = self.num_prompt_token
+            x = torch.cat((self._prompt_rows(input.shape[0], draws), feature + pos), dim=1)
+            feature = self._encode(x, draws, rng)[:, Pn:].contiguous()
+        return K.linear(feature, self.proj_post.weight, self.proj_post.bias)
+
+    def forward_tokenizer_features(self, neighborhood, center, return_global=False, draws=None):
+        return super().forward_tokenizer_features(neighborhood, center, return_global=return_global, draws=draws)

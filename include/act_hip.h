@@ -721,6 +721,28 @@ int act_tsne_kl_f32(const int32_t* indptr, const int32_t* indices, const float* 
 size_t act_tsne_pca_workspace(int N, int D);
 int act_tsne_pca_init_f32(const float* X, int N, int D, float* Y, double* info, void* workspace, size_t workspace_bytes, act_stream_t stream);
 
+/* ---- frozen post-LayerNorm language teacher (csrc/bert.hip; reference models/dvae.py:617-857) ------------------------------------ */
+/* y = LayerNorm(keep o t / (1 - drop_p) + res) * gamma + beta on rows [T, D] (D % 4 == 0, D <= 2048); rstd [T] (nullable) for the backward.
+ * keep: `mask` (0/1 floats [T, D], nullable) or Philox4x32-10 keyed by (seed, row, column/4) and the device-resident counter seed_dev (nullable),
+ * the convention of act_prompt_layernorm_fwd_f32; drop_p == 0 reads neither.
+ * backward: dres = LayerNorm backward of dy, dt = dres o keep / (1 - drop_p) with the mask regenerated; the normalised row comes back from the
+ * forward's output, (y - beta) / gamma, so gamma must have no zero entry.  No dgamma / dbeta: the language model is frozen. */
+int act_dropout_add_layernorm_fwd_f32(const float* t, const float* res, const float* mask, int T, int D, float drop_p, uint64_t seed,
+                                      const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, float* y, float* rstd,
+                                      act_stream_t stream);
+int act_dropout_add_layernorm_bwd_f32(const float* dy, const float* y, const float* mask, int T, int D, float drop_p, uint64_t seed,
+                                      const uint64_t* seed_dev, const float* gamma, const float* beta, const float* rstd, float* dt,
+                                      float* dres, act_stream_t stream);
+/* Self-attention with dropout on the probabilities: out = (softmax(q k^t scale) o keep / (1 - drop_p)) v, the normaliser over the undropped
+ * probabilities; qkv / out / lse / dqkv as act_attention_fwd_f32, any S >= 1, hd in {32,64}, B*H <= 65535.
+ * keep: `mask` (uint8 [B,H,S,S], nullable) or Philox4x32-10 keyed by (seed, (b H + h) S + query, key/4) and seed_dev (nullable).
+ * backward: recomputes P from lse and the mask from its key; delta [B,H,S] is scratch (rowsum(dout o out)). */
+int act_attention_dropout_fwd_f32(const float* qkv, const uint8_t* mask, float* out, float* lse, int B, int S, int H, int head_dim,
+                                  float scale, float drop_p, uint64_t seed, const uint64_t* seed_dev, act_stream_t stream);
+int act_attention_dropout_bwd_f32(const float* qkv, const uint8_t* mask, const float* out, const float* dout, const float* lse,
+                                  float* delta, float* dqkv, int B, int S, int H, int head_dim, float scale, float drop_p, uint64_t seed,
+                                  const uint64_t* seed_dev, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
