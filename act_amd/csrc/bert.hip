@@ -445,7 +445,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dkv_kernel(const BertAttnAr
 }
 
 bool attn_args_ok(int B, int S, int H, int hd, float p) {
-    return B > 0 && S > 0 && H > 0 && (hd == 32 || hd == 64) && p >= 0.f && p < 1.f && (long long)B * H * S < (1ll << 32) && (long long)B * H <= 65535;
+    return B >= 0 && S >= 0 && H > 0 && (hd == 32 || hd == 64) && p >= 0.f && p < 1.f && (long long)B * H * S < (1ll << 32) && (long long)B * H <= 65535;
 }
 
 }  // namespace
@@ -453,9 +453,9 @@ bool attn_args_ok(int B, int S, int H, int hd, float p) {
 extern "C" int act_dropout_add_layernorm_fwd_f32(const float* t, const float* res, const float* mask, int T, int D, float drop_p, uint64_t seed,
                                                  const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, float* y, float* rstd,
                                                  act_stream_t stream) {
-    if (!t || !res || !gamma || !beta || !y) return ACT_E_NULLPTR;
     if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * BLN_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
-    if (T == 0) return 0;
+    if (T == 0) return 0;                                               // before the pointers: an empty tensor has none
+    if (!t || !res || !gamma || !beta || !y) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D * (3 + (mask && drop_p > 0.f ? 1 : 0)));
 #define BLF(MV_) hipLaunchKernelGGL((bert_dropout_ln_fwd_kernel<MV_>), dim3((T + 3) / 4), dim3(256), 0, s, t, res, mask, gamma, beta, y, rstd, T, D, eps, drop_p, seed, seed_dev)
@@ -467,9 +467,9 @@ extern "C" int act_dropout_add_layernorm_fwd_f32(const float* t, const float* re
 extern "C" int act_dropout_add_layernorm_bwd_f32(const float* dy, const float* y, const float* mask, int T, int D, float drop_p, uint64_t seed,
                                                  const uint64_t* seed_dev, const float* gamma, const float* beta, const float* rstd, float* dt,
                                                  float* dres, act_stream_t stream) {
-    if (!dy || !y || !gamma || !beta || !rstd || !dt || !dres) return ACT_E_NULLPTR;
     if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * BLN_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
     if (T == 0) return 0;
+    if (!dy || !y || !gamma || !beta || !rstd || !dt || !dres) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_BWD, s, 0.0, 4.0 * T * (double)D * (4 + (mask && drop_p > 0.f ? 1 : 0)));
 #define BLB(MV_) hipLaunchKernelGGL((bert_dropout_ln_bwd_kernel<MV_>), dim3((T + 3) / 4), dim3(256), 0, s, dy, y, mask, gamma, beta, rstd, dt, dres, T, D, drop_p, seed, seed_dev)
@@ -480,9 +480,9 @@ extern "C" int act_dropout_add_layernorm_bwd_f32(const float* dy, const float* y
 
 extern "C" int act_attention_dropout_fwd_f32(const float* qkv, const uint8_t* mask, float* out, float* lse, int B, int S, int H, int head_dim,
                                              float scale, float drop_p, uint64_t seed, const uint64_t* seed_dev, act_stream_t stream) {
-    if (!qkv || !out) return ACT_E_NULLPTR;
-    if (B == 0 || S == 0) return 0;
     if (!attn_args_ok(B, S, H, head_dim, drop_p)) return ACT_E_BADARG;
+    if (B == 0 || S == 0) return 0;                                     // before the pointers: an empty tensor has none
+    if (!qkv || !out) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
     BertAttnArgs a{};
     a.qkv = qkv; a.mask = mask; a.o = out; a.lse_out = lse; a.B = B; a.S = S; a.H = H; a.scale = scale;
@@ -497,9 +497,9 @@ extern "C" int act_attention_dropout_fwd_f32(const float* qkv, const uint8_t* ma
 extern "C" int act_attention_dropout_bwd_f32(const float* qkv, const uint8_t* mask, const float* out, const float* dout, const float* lse,
                                              float* delta, float* dqkv, int B, int S, int H, int head_dim, float scale, float drop_p, uint64_t seed,
                                              const uint64_t* seed_dev, act_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !delta || !dqkv) return ACT_E_NULLPTR;
-    if (B == 0 || S == 0) return 0;
     if (!attn_args_ok(B, S, H, head_dim, drop_p)) return ACT_E_BADARG;
+    if (B == 0 || S == 0) return 0;
+    if (!qkv || !out || !dout || !lse || !delta || !dqkv) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
     BertAttnArgs a{};
     a.qkv = qkv; a.mask = mask; a.out = out; a.dout = dout; a.lse = lse; a.delta = delta; a.dqkv = dqkv; a.B = B; a.S = S; a.H = H; a.scale = scale;
