@@ -70,12 +70,16 @@ class Dgcnn(ctypes.Structure):                         # act_dgcnn_t
                 [(n, _vp) for n in ("w_in", "b_in", "w5")] + [("stacked", _vp * 4), ("gn_w", _vp * 4), ("gn_b", _vp * 4)])
 
 
+class AugmentOp(ctypes.Structure):                     # act_augment_op_t
+    _fields_ = [("kind", _i), ("p0", _f), ("p1", _f), ("p2", _f), ("draws", _vp), ("draws2", _vp)]
+
+
 # header typedef -> its mirror (act_block_grads_t has the fields of act_block_params_t and shares its class)
 STRUCTS = {
     "act_gemm_epilogue_t": GemmEpilogue, "act_gemm_tn_problem_t": GemmTnProblem, "act_gemm_fx_t": GemmFx,
     "act_block_params_t": BlockParams, "act_block_grads_t": BlockParams, "act_block_dims_t": BlockDims, "act_block_stack_t": BlockStack,
     "act_prefix_vit_t": PrefixVit, "act_vit_bf16x3_t": VitBf16x3, "act_pointnet_params_t": PointnetParams,
-    "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn,
+    "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn, "act_augment_op_t": AugmentOp,
 }
 
 _epi, _probs, _fx = _P(GemmEpilogue), _P(GemmTnProblem), _P(GemmFx)
@@ -102,6 +106,8 @@ _TABLE = {
     "act_gather_points_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "act_scale_translate_f32": [_vp, _vp, _vp, _i, _i, _vp],
     "act_rotate_points_f32": [_vp, _vp, _i, _i, _vp],
+    # fused augmentation chain (csrc/augment.hip)
+    "act_augment_f32": [_vp, _i, _i, _P(AugmentOp), _i, _u64, _vp, _i, _vp],
     # Chamfer distance (csrc/chamfer.hip)
     "act_chamfer_fwd_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "act_chamfer_fwd_ex_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],

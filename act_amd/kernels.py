@@ -1985,3 +1985,40 @@ class BertLayerFn(torch.autograd.Function):
 def bert_layer(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps=1e-12, p_attn=0.0, p_hidden=0.0, seeds=(0, 0, 0), masks=None,
                seed_dev=None):
     return BertLayerFn.apply(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps, p_attn, p_hidden, seeds, masks, seed_dev)
+
+
+# ---- fused augmentation chain (csrc/augment.hip) ----------------------------------------------------------------------------------------
+AUG_SCALE, AUG_TRANSLATE, AUG_SCALE_TRANSLATE, AUG_ROTATE_Y, AUG_JITTER, AUG_DROPOUT, AUG_FLIP = 1, 2, 3, 4, 5, 6, 7
+AUG_GLOBAL = 1
+# shape of the (up to two) injected draw tensors of each kind for a batch [B, N, 3]
+_AUG_DRAW_SHAPES = {AUG_SCALE: lambda B, N: ((B, 3),), AUG_TRANSLATE: lambda B, N: ((B, 3),), AUG_SCALE_TRANSLATE: lambda B, N: ((B, 3), (B, 3)),
+                    AUG_ROTATE_Y: lambda B, N: ((B,),), AUG_JITTER: lambda B, N: ((B, N, 3),), AUG_DROPOUT: lambda B, N: ((B,), (B, N)),
+                    AUG_FLIP: lambda B, N: ((B, 3),)}
+
+
+def augment(pc, ops, draws=None, seed=0, seed_dev=None, force_global=False):
+    """An ordered chain of 1..8 augmentation ops on pc f32 [B,N,3], in place, by one launch (act_augment_f32).  ``ops``: (kind, p0, p1, p2) per op;
+    ``draws`` (nullable): per op None or a tuple of the op's injected draw tensors (None entries: Philox keyed by ``seed`` and the device-resident
+    counter ``seed_dev``); ``force_global``: skip the LDS staging at any N."""
+    if pc.dim() != 3 or pc.shape[2] != 3 or pc.dtype != torch.float32:
+        raise _C.ActHipError("augment expects a float32 tensor [B, N, 3]")
+    B, N, _ = pc.shape
+    table = (_C._abi.AugmentOp * max(1, len(ops)))()
+    keep = []
+    for i, (kind, p0, p1, p2) in enumerate(ops):
+        inj = tuple(draws[i] or ()) if draws is not None and i < len(draws) else ()
+        shapes = _AUG_DRAW_SHAPES.get(int(kind), lambda B, N: ())(B, N)
+        ptrs = [None, None]
+        for j, t in enumerate(inj[:2]):
+            if t is None:
+                continue
+            t = torch.as_tensor(t, device=pc.device).to(torch.float32).contiguous()
+            if j >= len(shapes) or tuple(t.shape) != shapes[j]:
+                raise _C.ActHipError(f"augment: draw {j} of op {i} has shape {tuple(t.shape)}, expected {shapes[j] if j < len(shapes) else None}")
+            keep.append(t)
+            ptrs[j] = ptr(t)
+        table[i].kind, table[i].p0, table[i].p1, table[i].p2 = int(kind), float(p0), float(p1), float(p2)
+        table[i].draws, table[i].draws2 = ptrs
+    check(lib.act_augment_f32(ptr(pc), B, N, table, len(ops), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), AUG_GLOBAL if force_global else 0,
+                              stream()), "act_augment_f32")
+    return pc

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import builder
-from .runner_pretrain import wrap_ddp, _Single
+from .runner_pretrain import wrap_ddp, _Single, transforms_from_config
 from .. import kernels as K
 from ..datasets import data_transforms
 from ..pointnet2_ops import pointnet2_utils
@@ -81,14 +81,17 @@ def accuracy_scores(label, pred, num_classes=None):
     return acc, acc_avg
 
 
-def prepare_batch(points_raw, config, augment=True, choice=None, rot_u=None):
-    """raw cloud batch -> network input: FPS pool, random npoints-subset, rotation (tools/runner_finetune.py:141-159)."""
+def prepare_batch(points_raw, config, augment=True, choice=None, rot_u=None, transforms=None, aug_draws=None):
+    """raw cloud batch -> network input: FPS pool, random npoints-subset, rotation (tools/runner_finetune.py:141-159).
+    ``transforms``: the Compose of the config's ``train_transforms`` key in place of the rotation (``aug_draws``: its injected draws)."""
     npoints = config.npoints
     pts, _ = subsample(points_raw, npoints, point_all_for(npoints), choice)
-    return train_transforms(pts, rot_u) if augment else pts
+    if not augment:
+        return pts
+    return train_transforms(pts, rot_u) if transforms is None else transforms(pts, draws=aug_draws)
 
 
-def prefetch_batch(next_points_raw, config, augment=True):
+def prefetch_batch(next_points_raw, config, augment=True, transforms=None):
     """Enqueue prepare_batch(next batch) on the auxiliary stream: the 8192 -> 1200 farthest-point sampling is a serial chain
     that keeps one workgroup per cloud busy for ~1.2 ms (32 of 256 CUs at B=32) -- it hides behind the current batch's backward.
     The result is attached to the raw tensor and picked up by the next train_step()."""
@@ -96,28 +99,29 @@ def prefetch_batch(next_points_raw, config, augment=True):
     main, side = torch.cuda.current_stream(dev), K.side_stream(dev)
     side.wait_stream(main)
     with torch.cuda.stream(side):
-        pts = prepare_batch(next_points_raw, config, augment)
+        pts = prepare_batch(next_points_raw, config, augment, transforms=transforms)
         ev = torch.cuda.Event()
         ev.record(side)
     next_points_raw._act_prepared = (pts, ev)
 
 
 def train_step(base_model, optimizer, points, label, config, num_iter=1, augment=True, draws=None, choice=None, rot_u=None,
-               next_points=None):
+               next_points=None, transforms=None, aug_draws=None):
     """one optimisation step on a raw device batch [B,N_raw,3]; -> (loss, acc%) detached device tensors (no host sync).
-    ``next_points``: the next raw batch, whose preparation is started on the auxiliary stream before this backward."""
+    ``next_points``: the next raw batch, whose preparation is started on the auxiliary stream before this backward.
+    ``transforms`` / ``aug_draws``: see prepare_batch."""
     pre = getattr(points, "_act_prepared", None)
-    if pre is not None and choice is None and rot_u is None:
+    if pre is not None and choice is None and rot_u is None and aug_draws is None:
         points, ev = pre
         main = torch.cuda.current_stream(points.device)
         main.wait_event(ev)
         points.record_stream(main)
     else:
-        points = prepare_batch(points, config, augment, choice, rot_u)
+        points = prepare_batch(points, config, augment, choice, rot_u, transforms, aug_draws)
     ret = base_model(points, draws=draws) if draws is not None else base_model(points)
     loss, acc = base_model.module.get_loss_acc(ret, label)
     if next_points is not None and next_points.is_cuda:
-        prefetch_batch(next_points, config, augment)
+        prefetch_batch(next_points, config, augment, transforms)
     loss.backward()
     if num_iter == config.step_per_update:
         if config.get('grad_norm_clip') is not None:
@@ -137,6 +141,7 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
         builder.dataset_builder(args, config.dataset.val)
     base_model = builder.model_builder(config.model)
     misc.summary_parameters(base_model, logger)
+    transforms = transforms_from_config(config)
     start_epoch, best_epoch = 0, 0
     best_metrics, best_metrics_vote, metrics = Acc_Metric(0., 0.), Acc_Metric(0., 0.), Acc_Metric(0., 0.)
     if args.resume:
@@ -183,7 +188,7 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
             nxt = next(loader, None)                         # one batch of look-ahead: its FPS / subset / rotation overlap this backward
             cur = (nxt[2][0].to(device, non_blocking=True), nxt[2][1].to(device, non_blocking=True)) if nxt is not None else None
             loss, acc = train_step(base_model, optimizer, points, label, config, num_iter,
-                                   next_points=cur[0] if cur is not None else None)
+                                   next_points=cur[0] if cur is not None else None, transforms=transforms)
             if num_iter == config.step_per_update:
                 num_iter = 0
             if args.distributed:

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import builder
-from ..datasets.data_transforms import PointcloudScaleAndTranslate
+from ..datasets.data_transforms import PointcloudScaleAndTranslate, build_transforms
 from ..utils import dist_utils, misc
 from ..utils.AverageMeter import AverageMeter
 from ..utils.logger import get_logger, print_log
@@ -133,21 +133,31 @@ class _Announced:
         return ref is not None and ref() is t and version == t._version
 
 
-def train_step(base_model, optimizer, points, config, num_iter=1, augment=True, draws=None, next_points=None, next_draws=None):
+def transforms_from_config(config):
+    """None without the optional top-level key ``train_transforms`` (the module-level object is then used, exactly as before); with it, a
+    Compose of the listed {NAME: <class>, <keyword arguments>}: the whole chain is one launch per batch"""
+    spec = config.get('train_transforms')
+    return build_transforms(spec) if spec is not None else None
+
+
+def train_step(base_model, optimizer, points, config, num_iter=1, augment=True, draws=None, next_points=None, next_draws=None,
+               transforms=None, aug_draws=None, next_aug_draws=None):
     """one optimisation step on a device batch [B,N,3]; returns the detached loss tensor (no host sync).
 
     ``next_points`` (optional): the NEXT batch.  It is augmented here and announced to the model, which starts its grouping and
     frozen-teacher forward on the auxiliary stream while this batch's backward runs; pass that same tensor as ``points`` of the
-    next call (it is not augmented twice).  ``draws`` / ``next_draws`` (parity tests): injected random draws of this step / of the next step's teacher."""
+    next call (it is not augmented twice).  ``draws`` / ``next_draws`` (parity tests): injected random draws of this step / of the next step's teacher.
+    ``transforms``: the Compose of the config's ``train_transforms`` key (None: the module-level ``train_transforms``); ``aug_draws`` /
+    ``next_aug_draws``: its injected draws for this batch / the next one."""
     inner = base_model.module if hasattr(base_model, "module") else base_model
     if augment and not _Announced.is_marked(inner, points):
-        points = train_transforms(points)
+        points = train_transforms(points) if transforms is None else transforms(points, draws=aug_draws)
     loss = base_model(points, draws=draws) if draws is not None else base_model(points)
     if isinstance(loss, tuple):                      # ACT_PointBERT returns (moco, dvae, cutmix): summed (tools/runner_pretrain.py:140-142)
         loss = loss[0] + loss[1] + loss[2]
     if next_points is not None:
         if augment:
-            next_points = train_transforms(next_points)
+            next_points = train_transforms(next_points) if transforms is None else transforms(next_points, draws=next_aug_draws)
             _Announced.mark(inner, next_points)
         if hasattr(inner, "prefetch_teacher"):
             inner.prefetch_teacher(next_points, next_draws) if next_draws is not None else inner.prefetch_teacher(next_points)
@@ -167,6 +177,7 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
     extra_train_dataloader = builder.dataset_builder(args, config.dataset.extra_train)[1] if svm_val else None
     base_model = builder.model_builder(config.model)
     freeze_unused_heads(base_model)
+    transforms = transforms_from_config(config)
     device = torch.device("cuda", args.local_rank % max(1, torch.cuda.device_count()))
     if args.use_gpu:
         torch.cuda.set_device(device)          # every launch goes to the current device's current stream
@@ -229,7 +240,7 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
             data_time.update(time.time() - batch_start_time)
             nxt = next(loader, None)                         # one batch of look-ahead: its teacher forward overlaps this backward
             next_points = to_points(nxt[2]) if nxt is not None else None
-            loss = train_step(base_model, optimizer, points, config, num_iter, next_points=next_points)
+            loss = train_step(base_model, optimizer, points, config, num_iter, next_points=next_points, transforms=transforms)
             points = next_points
             if num_iter == config.step_per_update:
                 num_iter = 0

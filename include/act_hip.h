@@ -67,6 +67,48 @@ int act_scale_translate_f32(float* pc, const float* scale, const float* shift, i
  * (the reference builds R = [[c,0,s],[0,1,0],[-s,0,c]] per sample on the host; any per-sample 3x3 is accepted here). */
 int act_rotate_points_f32(float* pc, const float* rot, int B, int N, act_stream_t stream);
 
+/* ---- fused augmentation chain (csrc/augment.hip; datasets/data_transforms.py, all seven transforms) ------------------------------
+ * An ordered chain of 1 .. ACT_AUGMENT_MAX_OPS ops applied in place to pc [B,N,3] by ONE launch: one workgroup per cloud; for N <= 8192 the
+ * cloud is staged once into LDS, every op runs there and it is written back once; for larger N, or with ACT_AUGMENT_GLOBAL in flags, the same op
+ * code runs in place on global memory.  Every op sees the cloud as the earlier ops of the chain left it.  The table `ops` is a HOST array; it
+ * reaches the kernel as an argument by value (nothing is allocated or copied, the entry can be captured in a hipGraph).
+ * Draws are per cloud unless stated.  u denotes a uniform in [0,1).
+ *   kind             p0, p1, p2      effect
+ *   SCALE            lo, hi, -       s[3] = lo + (hi - lo) u;  p[:,c] *= s[c]
+ *   TRANSLATE        r, -, -         t[3] = -r + (2 r) u;      p[:,c] += t[c]
+ *   SCALE_TRANSLATE  lo, hi, r       p[:,c] = p[:,c] * s[c] + t[c], multiply then add (the bits of act_scale_translate_f32 for the same s, t)
+ *   ROTATE_Y         -               angle 2 pi u; R = [[c,0,s],[0,1,0],[-s,0,c]]; out_j = (p0 R0j + p1 R1j) + p2 R2j
+ *   JITTER           std, clip, -    per point and axis z ~ N(0,1): p += clamp(std z, -clip, clip)
+ *   DROPOUT          max_ratio, -, - ratio = u_b max_ratio (fp32); per point u_n; every point with u_n <= ratio becomes a copy of point 0
+ *   FLIP             upright axis    three draws (gate, first horizontal axis, second; the horizontal axes ascending); if gate < 0.95, every
+ *                    (0, 1 or 2)     horizontal axis whose draw is < 0.5 becomes max_n(x) - x
+ * Injected draws (device pointers, NULL: Philox): draws = scale [B,3] (SCALE, SCALE_TRANSLATE: the scale itself, not its uniform), shift [B,3]
+ * (TRANSLATE), u [B] (ROTATE_Y), z [B,N,3] (JITTER), u_b [B] (DROPOUT), [B,3] (FLIP); draws2 = shift [B,3] (SCALE_TRANSLATE), u_n [B,N] (DROPOUT).
+ * Philox4x32-10 draws: key = seed ^ (seed_dev[0] * 0x9E3779B97F4A7C15) (seed_dev nullable: the device-resident step counter of the bert.hip
+ * kernels), counter words (c0, c1, c2, c3) = (slot, cloud, 3, position + 8 sub) with `position` the index of the op in the chain; a uniform is
+ * (word >> 8) * 2^-24.  sub = 0, the per-cloud draws: slot 0 words 0..2 = the three scale / shift / flip uniforms, word 0 = the rotation's u or
+ * the dropout's u_b; SCALE_TRANSLATE takes its shift uniforms from slot 1 words 0..2.  sub = 1, the per-point draws, slot = point index n:
+ * DROPOUT u_n = word 0; JITTER is Box-Muller, z0 = r01 cos(2 pi u1), z1 = r01 sin(2 pi u1), z2 = r23 cos(2 pi u3) with
+ * r01 = sqrt(-2 ln(((w0 >> 8) + 1) 2^-24)), u1 = (w1 >> 8) 2^-24, r23 and u3 likewise from w2 and w3 (|z| <= 5.77).
+ * Returns ACT_E_BADARG for nops outside 1..8, an unknown kind or flag, lo > hi, a negative std, clip, r or max_ratio, max_ratio >= 1, an upright
+ * axis other than 0, 1, 2; B == 0 or N == 0 is a success without a launch. */
+#define ACT_AUGMENT_MAX_OPS 8
+#define ACT_AUGMENT_GLOBAL  1          /* flags: run in place on global memory at any N (tests compare the two paths) */
+#define ACT_AUG_SCALE           1
+#define ACT_AUG_TRANSLATE       2
+#define ACT_AUG_SCALE_TRANSLATE 3
+#define ACT_AUG_ROTATE_Y        4
+#define ACT_AUG_JITTER          5
+#define ACT_AUG_DROPOUT         6
+#define ACT_AUG_FLIP            7
+typedef struct {
+    int kind;
+    float p0, p1, p2;
+    const float *draws, *draws2;
+} act_augment_op_t;
+int act_augment_f32(float* pc, int B, int N, const act_augment_op_t* ops, int nops, uint64_t seed, const uint64_t* seed_dev, int flags,
+                    act_stream_t stream);
+
 /* ---- Chamfer distance (extensions/chamfer_dist: chamfer_cuda.cpp:12-39, chamfer.cu:15-229) --- */
 /* forward: xyz1 [B,n,3], xyz2 [B,m,3] -> dist1 [B,n], dist2 [B,m] (squared), idx1 int32 [B,n], idx2 int32 [B,m] */
 int act_chamfer_fwd_f32(const float* xyz1, const float* xyz2, int B, int n, int m,
