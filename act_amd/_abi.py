@@ -266,6 +266,9 @@ _TABLE = {
     "act_dropout_add_layernorm_bwd_f32": [_vp, _vp, _vp, _i, _i, _f, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "act_attention_dropout_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _u64, _vp, _vp],
     "act_attention_dropout_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _u64, _vp, _vp],
+    # CLIP image teacher (csrc/clip.hip)
+    "act_quickgelu_fwd_f32": [_vp, _vp, _i, _i, _vp],
+    "act_quickgelu_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

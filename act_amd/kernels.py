@@ -1987,6 +1987,97 @@ def bert_layer(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, e
     return BertLayerFn.apply(x, wqkv, bqkv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2, heads, eps, p_attn, p_hidden, seeds, masks, seed_dev)
 
 
+# ---- frozen CLIP image teacher (csrc/clip.hip) -------------------------------------------------------------------------------------------
+def quickgelu_fwd(pre, out=None):
+    """pre * sigmoid(1.702 pre) on dense fp32 of any shape"""
+    pre = _f32c(pre, "pre")
+    out = torch.empty_like(pre) if out is None else out
+    cols = pre.shape[-1] if pre.dim() else 1
+    check(lib.act_quickgelu_fwd_f32(ptr(pre), ptr(out), pre.numel() // max(cols, 1), cols, stream()), "act_quickgelu_fwd_f32")
+    return out
+
+
+def quickgelu_bwd(pre, dy, out=None):
+    """dy * s * (1 + 1.702 pre (1 - s)), s = sigmoid(1.702 pre); ``out`` may be ``dy`` (in place)"""
+    pre, dy = _f32c(pre, "pre"), _f32c(dy, "dy")
+    if dy.shape != pre.shape:
+        raise _C.ActHipError(f"quickgelu_bwd: dy {tuple(dy.shape)} vs pre {tuple(pre.shape)}")
+    out = torch.empty_like(pre) if out is None else out
+    cols = pre.shape[-1] if pre.dim() else 1
+    check(lib.act_quickgelu_bwd_f32(ptr(pre), ptr(dy), ptr(out), pre.numel() // max(cols, 1), cols, stream()), "act_quickgelu_bwd_f32")
+    return out
+
+
+class QuickGeluFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _f32c(x)
+        ctx.save_for_backward(x)
+        return quickgelu_fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return quickgelu_bwd(x, dy)
+
+
+def quickgelu(x):
+    return QuickGeluFn.apply(x)
+
+
+class ClipBlockFn(torch.autograd.Function):
+    """One FROZEN residual block of CLIP's visual Transformer applied to (x + pos) on x [B,S,D], batch first (reference models/dvae.py:505-506 through CLIP's
+    ResidualAttentionBlock; the reference's sequence-first permutes are layout only):
+
+        xin = x + pos ; x1 = xin + out_proj(attn(in_proj(LN1(xin)))) ; x2 = x1 + c_proj(quickgelu(c_fc(LN2(x1))))
+
+    ``in_proj_weight`` stacks q, k, v with the heads major inside each -- timm's qkv layout -- so the packed attention kernels apply as they are.  Built from
+    the entries BlockFnPerKernel uses, with c_fc under EPI_NONE and QuickGELU as its own pass (act_quickgelu_fwd_f32 / _bwd_f32).  Kept for the backward:
+    what BlockFnPerKernel keeps less what only weight gradients read (the MLP activation, the LN outputs), the pre-activation included.  The backward
+    produces the gradient of x and pos only: the weights are frozen.  Under no_grad nothing is kept."""
+
+    @staticmethod
+    def forward(ctx, x, pos, n1w, n1b, wqkv, bqkv, wo, bo, n2w, n2b, wfc, bfc, wproj, bproj, heads, eps):
+        B, S, D = x.shape
+        hd = D // heads
+        x2d = _f32c(x).reshape(B * S, D)
+        pos2d = _f32c(pos).reshape(B * S, D) if pos is not None else None
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        n1, xin, mean1, rstd1 = layernorm_fwd(x2d, pos2d, n1w, n1b, eps, want_stats=need_grad)
+        qkv = gemm(n1, wqkv, True, True, bias=bqkv)
+        att, lse = attention_fwd(qkv, B, S, heads, hd, want_lse=need_grad)
+        x1 = gemm(att, wo, True, True, bias=bo, res=xin)
+        n2, _, mean2, rstd2 = layernorm_fwd(x1, None, n2w, n2b, eps, want_stats=need_grad)
+        hpre = gemm(n2, wfc, True, True, bias=bfc, act=EPI_NONE)
+        a = quickgelu_fwd(hpre, out=None if need_grad else hpre)
+        x2 = gemm(a, wproj, True, True, bias=bproj, res=x1)
+        if need_grad:
+            ctx.save_for_backward(xin, mean1, rstd1, qkv, att, lse, x1, mean2, rstd2, hpre, n1w, wqkv, wo, n2w, wfc, wproj)
+            ctx.dims = (B, S, D, heads, hd)
+            ctx.has_pos = pos is not None
+        return x2.reshape(B, S, D)
+
+    @staticmethod
+    def backward(ctx, dx2):
+        xin, mean1, rstd1, qkv, att, lse, x1, mean2, rstd2, hpre, n1w, wqkv, wo, n2w, wfc, wproj = ctx.saved_tensors
+        B, S, D, heads, hd = ctx.dims
+        dx2 = _f32c(dx2).reshape(B * S, D)
+        da = gemm(dx2, wproj, True, False)
+        dh = quickgelu_bwd(hpre, da, out=da)
+        dn2 = gemm(dh, wfc, True, False)
+        dx1, _, _ = layernorm_bwd(dn2, x1, n2w, mean2, rstd2, dres=dx2, want_params=False)
+        datt = gemm(dx1, wo, True, False)
+        dqkv = attention_bwd(qkv, att, datt, lse, B, S, heads, hd)
+        dn1 = gemm(dqkv, wqkv, True, False)
+        dxin, _, _ = layernorm_bwd(dn1, xin, n1w, mean1, rstd1, dres=dx1, want_params=False)
+        dxin = dxin.reshape(B, S, D)
+        return (dxin if ctx.needs_input_grad[0] else None, dxin if ctx.has_pos and ctx.needs_input_grad[1] else None) + (None,) * 14
+
+
+def clip_block(x, pos, n1w, n1b, wqkv, bqkv, wo, bo, n2w, n2b, wfc, bfc, wproj, bproj, heads, eps=1e-5):
+    return ClipBlockFn.apply(x, pos, n1w, n1b, wqkv, bqkv, wo, bo, n2w, n2b, wfc, bfc, wproj, bproj, heads, eps)
+
+
 # ---- fused augmentation chain (csrc/augment.hip) ----------------------------------------------------------------------------------------
 AUG_SCALE, AUG_TRANSLATE, AUG_SCALE_TRANSLATE, AUG_ROTATE_Y, AUG_JITTER, AUG_DROPOUT, AUG_FLIP = 1, 2, 3, 4, 5, 6, 7
 AUG_GLOBAL = 1

@@ -234,6 +234,39 @@ class _FrozenBlock(nn.Module):
                                m.fc2.weight, m.fc2.bias, self.num_heads, self.eps, train_w)
 
 
+class _ClipAttnParams(nn.Module):
+    """``nn.MultiheadAttention``'s parameters under its key names: in_proj_weight [3D, D] (q, k, v stacked, heads major inside each), in_proj_bias, out_proj"""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        self.out_proj = nn.Linear(dim, dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+
+
+class _ClipBlock(nn.Module):
+    """parameter container of one CLIP ``ResidualAttentionBlock``, its key names and order (attn.{in_proj_weight,in_proj_bias,out_proj}, ln_1,
+    mlp.{c_fc,c_proj}, ln_2); the arithmetic is K.clip_block."""
+
+    def __init__(self, dim, heads, eps=1e-5):
+        super().__init__()
+        self.num_heads, self.eps = heads, eps
+        self.attn = _ClipAttnParams(dim)
+        self.ln_1 = nn.LayerNorm(dim, eps=eps)
+        self.mlp = nn.Module()
+        self.mlp.c_fc = nn.Linear(dim, dim * 4)
+        self.mlp.c_proj = nn.Linear(dim * 4, dim)
+        self.ln_2 = nn.LayerNorm(dim, eps=eps)
+
+    def forward(self, x, pos=None):
+        a, m = self.attn, self.mlp
+        return K.clip_block(x, pos, self.ln_1.weight, self.ln_1.bias, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+                            self.ln_2.weight, self.ln_2.bias, m.c_fc.weight, m.c_fc.bias, m.c_proj.weight, m.c_proj.bias, self.num_heads, self.eps)
+
+
+_CLIP_GEOMETRY = {"vit-b/16": (12, 12), "vit-b/32": (12, 12), "vit-l/14": (24, 16)}      # clip:<name> -> (layers, heads) of the visual tower; head dimension 64
+
 _VIT_GEOMETRY = {            # timm names -> (depth, heads); width must equal config.visual_embed_dim
     "vit_base_patch16_384": (12, 12), "vit_base_patch16_224": (12, 12), "vit_small_patch16_384": (12, 6),
     "vit_small_patch16_224": (12, 6), "deit_base_distilled_patch16_384": (12, 12),
@@ -367,7 +400,13 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
     The pretrained image Transformer is represented by its ``blocks`` + ``norm`` (what the reference keeps,
     :405-410) with timm's key names; weights come from the dVAE checkpoint (``ckpt``), never from the network.
     Optional config keys (absent from the reference YAML): ``visual_embed_depth`` / ``visual_embed_heads``
-    override the geometry implied by ``visual_embed_type``."""
+    override the geometry implied by ``visual_embed_type``.
+
+    ``visual_embed_type: clip:ViT-B/16`` (any name with 'clip' in it, :394-403) is CLIP's visual tower instead: ``visual_embed = Sequential(ln_pre, resblocks,
+    ln_post)`` with CLIP's key names, QuickGELU, LayerNorm eps 1e-5; its length of 3 is how the forward tells the two apart (:501).  The ``clip`` package is never
+    imported and nothing is fetched: the weights come from the dVAE checkpoint or from the optional local ``visual_embed_ckpt``, else they are random and the
+    class says so.  Shallow prompts only: ``use_deep_prompt: True`` raises ValueError (the reference's deep path hands a batch-first tensor to a sequence-first
+    attention) and ``freeze_visual_embed: False`` raises NotImplementedError.  The CLIP teacher always runs in fp32 (ACT_TEACHER_BF16X3 does not reach it)."""
 
     def __init__(self, config, **kwargs):
         super().__init__(config)
@@ -386,12 +425,18 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
         if self.visual_embed_dim == 'none':
             self.visual_embed = None
             return
-        depth, heads = _VIT_GEOMETRY.get(self.visual_embed_type, (12, 12))
-        depth = int(config.get("visual_embed_depth", depth))
-        heads = int(config.get("visual_embed_heads", heads))
         D = self.visual_embed_dim
-        blocks = nn.Sequential(*[_FrozenBlock(D, heads) for _ in range(depth)])
-        self.visual_embed = nn.Sequential(blocks, nn.LayerNorm(D, eps=1e-6))
+        self.is_clip = 'clip' in str(self.visual_embed_type).lower()
+        if self.is_clip:
+            depth, heads = self._clip_geometry(config)
+            self.visual_embed = nn.Sequential(nn.LayerNorm(D, eps=1e-5), nn.Sequential(*[_ClipBlock(D, heads) for _ in range(depth)]),
+                                              nn.LayerNorm(D, eps=1e-5))
+        else:
+            depth, heads = _VIT_GEOMETRY.get(self.visual_embed_type, (12, 12))
+            depth = int(config.get("visual_embed_depth", depth))
+            heads = int(config.get("visual_embed_heads", heads))
+            blocks = nn.Sequential(*[_FrozenBlock(D, heads) for _ in range(depth)])
+            self.visual_embed = nn.Sequential(blocks, nn.LayerNorm(D, eps=1e-6))
         self.visual_embed_depth = depth
         self.proj_pre = nn.Linear(self.tokens_dims, D)
         self.visual_pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, D))
@@ -411,9 +456,79 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
                 trunc_normal_(self.deep_prompt_pos, std=.02)
         else:
             self.visual_prompt_token = None
+        if self.is_clip:
+            ckpt = config.get("visual_embed_ckpt", None)
+            if ckpt and str(ckpt).lower() not in ("none", "random", ""):
+                self.load_clip_visual(ckpt)
+            else:
+                import warnings
+                warnings.warn("ACTPromptedDiscreteVAEwithVIT: no visual_embed_ckpt -- the CLIP visual Transformer is RANDOMLY INITIALISED unless a dVAE "
+                              "checkpoint that contains it is loaded afterwards.  Real Stage-I training must point visual_embed_ckpt at a local CLIP file of "
+                              + str(self.visual_embed_type) + " (its state_dict or its TorchScript archive); nothing is ever downloaded.", stacklevel=2)
         if self.freeze_visual_embed:
             for param in self.visual_embed.parameters():
                 param.requires_grad = False
+
+    def _clip_geometry(self, config):
+        """the refusals and the (layers, heads) of a CLIP teacher"""
+        if self.use_deep_prompt:
+            raise ValueError("use_deep_prompt: True is not built for a CLIP teacher: in the reference's visual_embedding_deep_prompt the permute(0, 1, 2) calls "
+                             "are identities, so the batch-first tensor enters nn.MultiheadAttention, which reads dimension 0 as the sequence, and attention "
+                             "runs across the clouds of a batch.  Neither that nor the presumably intended per-cloud attention is computed; use "
+                             "use_deep_prompt: False (shallow prompts)")
+        if not self.freeze_visual_embed:
+            raise NotImplementedError("freeze_visual_embed: False -- training CLIP's own weights is not built (ACT's recipe never trains the teacher "
+                                      "Transformer; only prompts and projections learn)")
+        name = str(self.visual_embed_type).split(":", 1)[-1].strip().lower()
+        has = lambda k: config.get(k, None) is not None       # noqa: E731
+        if name not in _CLIP_GEOMETRY and not (has("visual_embed_depth") and has("visual_embed_heads")):
+            raise ValueError(f"visual_embed_type {self.visual_embed_type!r}: the CLIP visual Transformers are {sorted('clip:' + k for k in _CLIP_GEOMETRY)} "
+                             "(the ResNet towers have no Transformer blocks); any other needs visual_embed_depth and visual_embed_heads")
+        depth, heads = _CLIP_GEOMETRY.get(name, (0, 0))
+        depth = int(config.get("visual_embed_depth")) if has("visual_embed_depth") else depth
+        heads = int(config.get("visual_embed_heads")) if has("visual_embed_heads") else heads
+        D = self.visual_embed_dim
+        if depth < 1 or heads < 1 or D % heads or D // heads not in (32, 64):
+            raise ValueError(f"visual_embed_dim {D} / visual_embed_heads {heads} / visual_embed_depth {depth}: the attention kernels take head dimensions "
+                             "32 and 64")
+        return depth, heads
+
+    def load_clip_visual(self, path):
+        """``path``: a local file of CLIP -- a ``state_dict`` (``torch.save``) or the TorchScript archive CLIP distributes -- either the whole model's
+        (``visual.ln_pre.*``, ``visual.transformer.resblocks.{i}.*``, ``visual.ln_post.*``) or one already in this class's ``visual_embed.*`` form.
+        fp16 is cast to fp32; a missing or mis-shaped key raises and names it."""
+        try:
+            sd = torch.load(path, map_location='cpu')
+        except Exception:
+            sd = torch.jit.load(path, map_location='cpu')
+        if hasattr(sd, "state_dict"):
+            sd = sd.state_dict()
+        sd = sd.get("state_dict", sd)
+        forms = (("visual.ln_pre.", "visual_embed.0."), ("visual.transformer.resblocks.", "visual_embed.1."), ("visual.ln_post.", "visual_embed.2."),
+                 ("visual_embed.", "visual_embed."))
+        got = {}
+        for k, v in sd.items():
+            k = k[7:] if k.startswith("module.") else k
+            for src, dst in forms:
+                if k.startswith(src):
+                    got[dst + k[len(src):]] = v
+                    break
+        with torch.no_grad():
+            for name, p in self.visual_embed.state_dict().items():
+                key = "visual_embed." + name
+                if key not in got:
+                    raise KeyError(f"{path}: {key} is missing (CLIP form: {self._clip_form(key)})")
+                v = got[key]
+                if tuple(v.shape) != tuple(p.shape):
+                    raise ValueError(f"{path}: {key} has shape {tuple(v.shape)}, the model's is {tuple(p.shape)}")
+                p.copy_(v.to(torch.float32))
+
+    @staticmethod
+    def _clip_form(key):
+        for src, dst in (("visual.ln_pre.", "visual_embed.0."), ("visual.transformer.resblocks.", "visual_embed.1."), ("visual.ln_post.", "visual_embed.2.")):
+            if key.startswith(dst):
+                return src + key[len(dst):]
+        return key
 
     # ---- prompt-tuned frozen Transformer ---------------------------------------------------------
     def _drop(self, t, draws, key):
@@ -455,12 +570,20 @@ class ACTPromptedDiscreteVAEwithVIT(DiscreteVAE):
         pos = K.mlp(center, vp[0].weight, vp[0].bias, vp[2].weight, vp[2].bias)
         hidden = K.linear(input, self.proj_pre.weight, self.proj_pre.bias)
         train_w = not self.freeze_visual_embed
-        nrm = self.visual_embed[1]
+        nrm = self.visual_embed[-1]
+        if len(self.visual_embed) == 3:                    # CLIP (:501-507): ln_pre on the prompted rows (pos is not normalised), then x = blk(x + pos)
+            pre = self.visual_embed[0]
 
-        def stack(h, p):
-            for blk in self.visual_embed[0]:
-                h = blk(h, p, None, None, train_w)
-            return h
+            def stack(h, p):
+                h = K.layer_norm(h, pre.weight, pre.bias, pre.eps)
+                for blk in self.visual_embed[1]:
+                    h = blk(h, p)
+                return h
+        else:
+            def stack(h, p):
+                for blk in self.visual_embed[0]:
+                    h = blk(h, p, None, None, train_w)
+                return h
         if self.visual_prompt_token is None:
             if self.freeze_visual_embed:
                 with torch.no_grad():

@@ -785,6 +785,13 @@ int act_attention_dropout_bwd_f32(const float* qkv, const uint8_t* mask, const f
                                   float* delta, float* dqkv, int B, int S, int H, int head_dim, float scale, float drop_p, uint64_t seed,
                                   const uint64_t* seed_dev, act_stream_t stream);
 
+/* ---- CLIP image teacher (csrc/clip.hip; reference models/dvae.py:394-403, :500-511) ------------------------------------------------ */
+/* QuickGELU of CLIP's residual blocks on rows [rows, cols] (dense; any rows * cols, any 4-byte aligned pointers, 16-byte accesses where the
+ * pointers agree modulo 16 bytes):  out = pre * sigmoid(1.702 pre);  dx = dy * s * (1 + 1.702 pre (1 - s)),  s = sigmoid(1.702 pre).
+ * Finite for every finite input: s and 1 - s come from exp(-|1.702 pre|).  out may alias pre, dx may alias dy. */
+int act_quickgelu_fwd_f32(const float* pre, float* out, int rows, int cols, act_stream_t stream);
+int act_quickgelu_bwd_f32(const float* pre, const float* dy, float* dx, int rows, int cols, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
