@@ -269,6 +269,12 @@ _TABLE = {
     # CLIP image teacher (csrc/clip.hip)
     "act_quickgelu_fwd_f32": [_vp, _vp, _i, _i, _vp],
     "act_quickgelu_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
+    # weighted k-NN validation of frozen features (csrc/knn_probe.hip)
+    "act_knn_probe_normalize_f32": [_vp, _i, _i, _vp, _vp],
+    "act_knn_probe_splits": [_i, _i, _i, _i],
+    "act_knn_probe_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "act_knn_probe_search_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
+    "act_knn_probe_vote_f32": [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _P(_i), _i, _f, _vp, _vp, _vp, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -1880,6 +1880,63 @@ def tsne_pca_init(x, want_info=False):
     return (Y, info) if want_info else Y
 
 
+# ---- weighted k-NN validation of frozen features (csrc/knn_probe.hip): fused similarity + streaming top-k, weighted class vote -------------------
+KNN_PROBE_MAX_K = 256
+KNN_PROBE_MAX_CLASSES = 1024
+KNN_PROBE_MAX_KS = 16
+
+
+def knn_probe_normalize(x):
+    """x [N,D] -> x / max(|x|, 1e-12) per row (a zero row stays zero)"""
+    x = _svm_rows(x, "knn_probe_normalize x")
+    out = torch.empty_like(x)
+    check(lib.act_knn_probe_normalize_f32(ptr(x), x.shape[0], x.shape[1], ptr(out), stream()), "act_knn_probe_normalize_f32")
+    return out
+
+
+def knn_probe_search(q, bank, k, normalize=True, exclude_self=False, splits=0):
+    """q [Nq,D], bank [Nb,D] -> (sim fp32 [Nq,k], idx int32 [Nq,k]): the k most similar bank rows of every query, best first, ties towards the
+    lower bank index; ``exclude_self``: query i never selects bank row i; ``splits``: bank ranges searched separately (0 = chosen by the library;
+    the result does not depend on it)"""
+    q, bank = _svm_rows(q, "knn_probe_search q"), _svm_rows(bank, "knn_probe_search bank")
+    (Nq, D), Nb = q.shape, bank.shape[0]
+    k = int(k)
+    if bank.shape[1] != D or Nq < 1 or D < 1:
+        raise _C.ActHipError(f"knn_probe_search: q {tuple(q.shape)} and bank {tuple(bank.shape)} do not agree")
+    if not 1 <= k <= min(Nb - bool(exclude_self), KNN_PROBE_MAX_K):
+        raise _C.ActHipError(f"knn_probe_search: k = {k} outside 1 .. min({Nb} bank rows - {int(bool(exclude_self))}, {KNN_PROBE_MAX_K})")
+    idx = torch.empty(Nq, k, dtype=torch.int32, device=q.device)
+    sim = torch.empty(Nq, k, dtype=torch.float32, device=q.device)
+    nbytes = lib.act_knn_probe_workspace(Nq, Nb, D, k, int(splits))
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=q.device)      # the padded copy of a large bank outgrows the persistent scratch
+    check(lib.act_knn_probe_search_f32(ptr(q), Nq, ptr(bank), Nb, D, k, int(bool(normalize)), int(bool(exclude_self)), int(splits), ptr(idx),
+                                       ptr(sim), ptr(ws), ws.numel() * 4, stream()), "act_knn_probe_search_f32")
+    return sim, idx
+
+
+def knn_probe_vote(sim, idx, bank_cls, num_classes, ks, T, q_cls=None, want_scores=True):
+    """sim / idx [Nq,kmax] of knn_probe_search, bank_cls int32 [Nb] class indices, ks ascending -> (scores fp32 [Nq,len(ks),C] or None,
+    pred int64 [Nq,len(ks)] class indices, counts int64 [len(ks),2] top-1 / top-5 hits against q_cls, or None without it)"""
+    sim = _svm_rows(sim, "knn_probe_vote sim")
+    Nq, kmax = sim.shape
+    idx = _tsne_i32(idx, (Nq, kmax), "knn_probe_vote idx")
+    bank_cls = _tsne_i32(bank_cls, None, "knn_probe_vote bank_cls")
+    ks = [int(v) for v in ks]
+    C = int(num_classes)
+    if not ks or len(ks) > KNN_PROBE_MAX_KS or ks[0] < 1 or ks[-1] > kmax or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise _C.ActHipError(f"knn_probe_vote: ks = {ks} must be 1 .. {KNN_PROBE_MAX_KS} ascending values in 1 .. {kmax}")
+    if not 1 <= C <= KNN_PROBE_MAX_CLASSES or bank_cls.dim() != 1 or not float(T) > 0:
+        raise _C.ActHipError(f"knn_probe_vote: {C} classes (supported: 1 .. {KNN_PROBE_MAX_CLASSES}), T = {T}")
+    if q_cls is not None:
+        q_cls = _tsne_i32(q_cls, (Nq,), "knn_probe_vote q_cls")
+    scores = torch.empty(Nq, len(ks), C, dtype=torch.float32, device=sim.device) if want_scores else None
+    pred = torch.empty(Nq, len(ks), dtype=torch.int64, device=sim.device)
+    counts = torch.zeros(len(ks), 2, dtype=torch.int64, device=sim.device) if q_cls is not None else None
+    check(lib.act_knn_probe_vote_f32(ptr(sim), ptr(idx), Nq, kmax, ptr(bank_cls), bank_cls.numel(), ptr(q_cls), C, (ctypes.c_int * len(ks))(*ks),
+                                     len(ks), float(T), ptr(scores), ptr(pred), ptr(counts), stream()), "act_knn_probe_vote_f32")
+    return scores, pred, counts
+
+
 # ---- frozen post-LayerNorm language teacher (csrc/bert.hip) ---------------------------------------------------------------------------
 def dropout_add_layernorm_fwd(t, res, gamma, beta, eps, p=0.0, seed=0, mask=None, seed_dev=None, want_rstd=True):
     """y = LN(keep o t / (1-p) + res) * gamma + beta on rows [T, D]; keep: ``mask`` (0/1 floats [T, D]) or in-kernel Philox(seed, seed_dev)."""

@@ -8,7 +8,9 @@ Differences forced by the hardware-first design, none of them visible in the con
     all-reduce overlapped with backward;
   * the logged loss is all-reduced every step but read back only every ``log_every`` steps;
   * the linear-SVM validation (reference :47-51, :228-287, which its run_net never calls) is solved on the device (utils/svm.py) and is
-    opt-in: ``svm_val: True`` in the config, a ``dataset.extra_train`` section and a positive ``--val_freq``.
+    opt-in: ``svm_val: True`` in the config, a ``dataset.extra_train`` section and a positive ``--val_freq``;
+  * a weighted k-NN probe of the same features (utils/knn_probe.py; no solver, nothing to tune) runs next to the SVM or instead of it:
+    ``knn_val: {k: [10, 20], T: 0.07}`` under the same two other conditions.
 """
 import time
 import os
@@ -46,6 +48,14 @@ def evaluate_svm(train_features, train_labels, test_features, test_labels):
     return float((pred == test_labels.to(pred.dtype)).sum() * 100. / pred.shape[0])
 
 
+def evaluate_knn(train_features, train_labels, test_features, test_labels, ks=(10, 20), T=0.07):
+    """{"knn@k": top-1 accuracy (percent), "knn@k/top5": ...} on the test features of the weighted k-NN vote over the train features (cosine
+    similarity, weights exp(sim / T)): search, vote and the hit counts stay on the device, the counts are the one thing read back"""
+    from ..utils.knn_probe import KNNClassifier
+    ks = [int(ks)] if isinstance(ks, int) else [int(k) for k in ks]
+    return KNNClassifier(k=ks, T=float(T)).fit(train_features, train_labels).score(test_features, test_labels)
+
+
 def extract_features(base_model, dataloader, npoints):
     """(features [n, C], labels [n]) of a ModelNet-style loader, concatenated on the device: misc.fps to ``npoints``, ``forward(noaug=True)``"""
     feats, labels = [], []
@@ -59,7 +69,12 @@ def extract_features(base_model, dataloader, npoints):
 
 def validate(base_model, extra_train_dataloader, test_dataloader, epoch, val_writer, args, config, logger=None):
     """Point-BERT's linear-SVM protocol (reference :228-287): features of the extra_train and val splits, a linear SVM on the first, accuracy
-    on the second.  Under ``args.distributed`` the features are all-gathered and every rank solves the same problem."""
+    on the second.  Under ``args.distributed`` the features are all-gathered and every rank solves the same problem.
+    ``knn_val`` in the config adds the weighted k-NN probe on the same (gathered) features; it alone makes its first k's top-1 the metric, next
+    to ``svm_val`` the SVM accuracy stays the metric and the k-NN accuracies are logged."""
+    svm_val, knn_val = bool(config.get('svm_val', False)), config.get('knn_val', None)
+    if not knn_val:
+        svm_val = True                                  # (called directly without either key: the SVM protocol, as before)
     print_log(f"[VALIDATION] Start validating epoch {epoch}", logger=logger)
     base_model.eval()
     npoints = config.dataset.train.others.npoints
@@ -69,11 +84,23 @@ def validate(base_model, extra_train_dataloader, test_dataloader, epoch, val_wri
         if args.distributed:
             train_features, train_label, test_features, test_label = (dist_utils.gather_tensor(t, args) for t in
                                                                       (train_features, train_label, test_features, test_label))
-        svm_acc = evaluate_svm(train_features.float(), train_label, test_features.float(), test_label)
-        print_log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, svm_acc), logger=logger)
+        train_features, test_features = train_features.float(), test_features.float()
+        if svm_val:
+            svm_acc = evaluate_svm(train_features, train_label, test_features, test_label)
+            print_log('[Validation] EPOCH: %d  acc = %.4f' % (epoch, svm_acc), logger=logger)
+        if knn_val:
+            ks = knn_val.get('k', [10, 20])
+            ks = [int(ks)] if isinstance(ks, int) else [int(k) for k in ks]
+            knn_acc = evaluate_knn(train_features, train_label, test_features, test_label, ks, float(knn_val.get('T', 0.07)))
+            for k in ks:
+                print_log('[Validation] EPOCH: %d  knn@%d = %.4f' % (epoch, k, knn_acc['knn@%d' % k]), logger=logger)
     if val_writer is not None:
-        val_writer.add_scalar('Metric/ACC', svm_acc, epoch)
-    return Acc_Metric(svm_acc)
+        if svm_val:
+            val_writer.add_scalar('Metric/ACC', svm_acc, epoch)
+        if knn_val:
+            for k in ks:
+                val_writer.add_scalar('Metric/KNN@%d' % k, knn_acc['knn@%d' % k], epoch)
+    return Acc_Metric(svm_acc if svm_val else knn_acc['knn@%d' % ks[0]])
 
 
 def freeze_unused_heads(model):
@@ -172,8 +199,10 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
     logger = get_logger(args.log_name)
     (train_sampler, train_dataloader), (_, test_dataloader) = builder.dataset_builder(args, config.dataset.train), \
         builder.dataset_builder(args, config.dataset.val)
-    # linear-SVM validation is opt-in: without all three of these the loop, its random draws and its checkpoints are what they are without it
-    svm_val = bool(config.dataset.get('extra_train')) and getattr(args, 'val_freq', 0) > 0 and bool(config.get('svm_val', False))
+    # validation is opt-in: without all three of these the loop, its random draws and its checkpoints are what they are without it
+    # (svm_val: the linear SVM; knn_val: the weighted k-NN probe; either switches the validation on)
+    svm_val = bool(config.dataset.get('extra_train')) and getattr(args, 'val_freq', 0) > 0 and \
+        (bool(config.get('svm_val', False)) or bool(config.get('knn_val', None)))
     extra_train_dataloader = builder.dataset_builder(args, config.dataset.extra_train)[1] if svm_val else None
     base_model = builder.model_builder(config.model)
     freeze_unused_heads(base_model)

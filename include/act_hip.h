@@ -792,6 +792,33 @@ int act_attention_dropout_bwd_f32(const float* qkv, const uint8_t* mask, const f
 int act_quickgelu_fwd_f32(const float* pre, float* out, int rows, int cols, act_stream_t stream);
 int act_quickgelu_bwd_f32(const float* pre, const float* dy, float* dx, int rows, int cols, act_stream_t stream);
 
+/* ---- weighted k-NN validation of frozen features (csrc/knn_probe.hip) ----------------------------------------------------------------
+ * The protocol of Wu et al. 2018 (instance discrimination) that DINO's eval_knn uses: for every query the kmax most similar bank rows under
+ * the dot product of (optionally L2-normalised) fp32 features, then per k a class vote weighted by exp(sim / T).  No solver, no tolerance.
+ * Order is total: larger similarity first, then lower bank index.  Every similarity is one k-ordered fp32 fmaf chain (v_mfma_f32_16x16x4_f32),
+ * so all outputs are bit-identical run to run and do not depend on `splits`.  1 <= kmax <= 256; the Nq x Nb similarities never reach memory.
+ *
+ * normalize: out [N,D] = x / max(|x|, 1e-12), the norm summed in a fixed order; a zero row stays zero. */
+int act_knn_probe_normalize_f32(const float* X, int N, int D, float* out, act_stream_t stream);
+/* search: Q fp32 [Nq,D], bank fp32 [Nb,D] -> idx int32 [Nq,kmax], sim fp32 [Nq,kmax] (either may be NULL), best first.  normalize != 0: both
+ * sides are normalised as above (into the workspace) first.  exclude_self != 0: query i never selects bank row i (by index: leave-one-out of
+ * the bank on itself; an exact duplicate elsewhere is still returned).  kmax <= Nb - (exclude_self != 0).
+ * splits: number of bank ranges searched by separate workgroups and merged (0 = chosen from the shape; at most 16 and at most ceil(Nb / 128));
+ * act_knn_probe_splits returns the number used.  The workspace (16-byte aligned) holds the padded copies of both sides and kmax 64-bit keys
+ * per query and split. */
+int act_knn_probe_splits(int Nq, int Nb, int kmax, int splits);
+size_t act_knn_probe_workspace(int Nq, int Nb, int D, int kmax, int splits);
+int act_knn_probe_search_f32(const float* Q, int Nq, const float* bank, int Nb, int D, int kmax, int normalize, int exclude_self, int splits,
+                             int32_t* idx, float* sim, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* vote: sim / idx [Nq,kmax] of a search, bank_cls int32 [Nb] and q_cls int32 [Nq] (may be NULL) class indices in 0 .. C-1 (C <= 1024; a q_cls
+ * outside that range never counts as a hit), ks: nk <= 16 ascending values in 1 .. kmax, read on the HOST.  For every query and ks[j]:
+ *   scores [Nq,nk,C] (may be NULL): s_c = sum over ranks r < ks[j] with bank_cls[idx_r] == c of exp(sim_r / T), added in rank order in fp32;
+ *   pred int64 [Nq,nk] (may be NULL): the class index of the largest score, ties to the lowest class;
+ *   counts int64 [nk,2] (may be NULL): += 1 per query whose q_cls is the prediction (column 0) / among the five best scores under the same tie
+ *   rule (column 1).  Integer atomics: the caller zeroes counts, may accumulate several calls into it, and reads it once. */
+int act_knn_probe_vote_f32(const float* sim, const int32_t* idx, int Nq, int kmax, const int32_t* bank_cls, int Nb, const int32_t* q_cls, int C,
+                           const int* ks, int nk, float T, float* scores, long long* pred, long long* counts, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
