@@ -275,6 +275,11 @@ _TABLE = {
     "act_knn_probe_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "act_knn_probe_search_f32": [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "act_knn_probe_vote_f32": [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _P(_i), _i, _f, _vp, _vp, _vp, _vp],
+    # Earth Mover's Distance (csrc/emd.hip)
+    "act_emd_max_points": [],
+    "act_emd_fwd_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
+    "act_emd_fwd_ex_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "act_emd_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

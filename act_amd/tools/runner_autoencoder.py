@@ -203,6 +203,19 @@ def aggregate_rows(rows, taxonomy_ids):
     return dict(losses=losses, per_taxonomy=per, overall=overall)
 
 
+def aggregate_emd(emd_rows, taxonomy_ids):
+    """the EMD column of ``evaluate`` (config key ``emd_val``): ``emd_rows`` float64 [n, 2] = (value, info) per cloud as
+    ``utils.metrics.emd_distance`` returned them -> dict(values, info, per_taxonomy = {id: mean}, overall = mean over taxonomies of the
+    per-taxonomy means like the other columns, capped = clouds whose matching the round cap ended)"""
+    emd_rows = np.asarray(emd_rows, dtype=np.float64).reshape(-1, 2)
+    members = {}
+    for i, t in enumerate(taxonomy_ids):
+        members.setdefault(t, []).append(i)
+    per = {t: float(emd_rows[ix, 0].mean()) for t, ix in members.items()}
+    return dict(values=emd_rows[:, 0].copy(), info=emd_rows[:, 1].astype(np.int64), per_taxonomy=per,
+                overall=float(np.mean(list(per.values()))) if per else 0.0, capped=int((emd_rows[:, 1] < 0).sum()))
+
+
 def results_table(per_taxonomy, overall, names=None, synset=None):
     """the reference's TEST RESULTS table (:292-314) as plain text: Taxonomy | #Sample | metrics | Category, a footing row 'Overall'"""
     from ..utils.metrics import Metrics as FullMetrics
@@ -258,7 +271,12 @@ def evaluate(base_model, test_dataloader, epoch, args, config, logger=None, val_
 
     Returns ``utils.metrics.Metrics(config.consider_metric, overall)``, overall = mean over taxonomies of the per-taxonomy means.  The details
     ride on the returned object as attributes: ``per_taxonomy`` {id: (count, [F-Score, CDL1, CDL2])}, ``losses`` (the four mean losses x1000),
-    ``rows`` (float64 ndarray [samples, RECON_FIELDS]) and ``taxonomy_ids`` / ``model_ids`` (one per row)."""
+    ``rows`` (float64 ndarray [samples, RECON_FIELDS]) and ``taxonomy_ids`` / ``model_ids`` (one per row).
+
+    Config key ``emd_val: True`` (or ``emd_val: {eps: ...}``) adds the Earth Mover's Distance of (dense, gt) per cloud
+    (``utils.metrics.emd_distance``: the dense output is first reduced to the ground truth's count by farthest-point sampling): a column
+    ``EMD`` in the table and its footing row, writer key ``Metric/EMD``, and ``emd`` on the returned object (``aggregate_emd``).  The values
+    stay on the device and come to the host in the same single read; the returned ``Metrics`` values are the three they always were."""
     from .. import kernels as K
     from ..utils.metrics import Metrics as FullMetrics
     print_log(f"[VALIDATION] Start validating epoch {epoch}", logger=logger)
@@ -273,17 +291,39 @@ def evaluate(base_model, test_dataloader, epoch, args, config, logger=None, val_
         raise NotImplementedError(f'Train phase do not support {section._base_.NAME}')
     n_samples = len(test_dataloader.dataset)
     out = torch.zeros(n_samples, K.RECON_FIELDS, dtype=torch.float64, device=device)
+    emd_val = config.get('emd_val', None)                             # opt-in: True or {eps: ...}; absent or false: nothing below runs
+    if emd_val:
+        from ..utils.metrics import emd_distance
+        emd_eps = emd_val.get('eps', None) if isinstance(emd_val, dict) else None
+        emd_out = torch.zeros(n_samples, 2, dtype=torch.float64, device=device)          # per cloud: value, info
     taxonomy_ids, model_ids, row0 = [], [], 0
     for idx, (tax, mids, data) in enumerate(test_dataloader):
         points = data.to(device, non_blocking=True)
-        eval_batch(module, points, out, row0, seed)
+        ret = eval_batch(module, points, out, row0, seed)
+        if emd_val:
+            v, info = emd_distance(ret[1], points, emd_eps)
+            emd_out[row0:row0 + points.shape[0], 0] = v
+            emd_out[row0:row0 + points.shape[0], 1] = info
         taxonomy_ids += [_tax(t) for t in tax]
         model_ids += [_tax(m) for m in mids]
         row0 += points.shape[0]
         if max_batches is not None and idx + 1 >= max_batches:
             break
-    rows = out[:row0].cpu().numpy()                                   # the one device -> host read
+    if emd_val:
+        rows = torch.cat([out[:row0], emd_out[:row0]], dim=1).cpu().numpy()          # still the one device -> host read
+        rows, emd_rows = np.ascontiguousarray(rows[:, :K.RECON_FIELDS]), rows[:, K.RECON_FIELDS:]
+    else:
+        rows = out[:row0].cpu().numpy()                               # the one device -> host read
     agg = aggregate_rows(rows, taxonomy_ids)
+    names, per_taxonomy, overall = FullMetrics.names(), agg["per_taxonomy"], agg["overall"]
+    if emd_val:
+        emd = aggregate_emd(emd_rows, taxonomy_ids)
+        names = names + ['EMD']
+        per_taxonomy = {t: (c, v + [emd["per_taxonomy"][t]]) for t, (c, v) in per_taxonomy.items()}
+        overall = overall + [emd["overall"]]
+        if emd["capped"]:
+            print_log('[Validation] EMD: the round cap ended the matching of %d of %d clouds; their values are upper bounds without the '
+                      'N * eps guarantee' % (emd["capped"], row0), logger=logger)
     for i in range(1999, row0, 2000):
         r = rows[i]
         print_log('Test[%d/%d] Taxonomy = %s Sample = %s Losses = %s Metrics = %s' %
@@ -291,14 +331,16 @@ def evaluate(base_model, test_dataloader, epoch, args, config, logger=None, val_
                    ['%.4f' % m for m in (r[K.RECON_FSCORE], r[K.RECON_CDL1] * 1000, r[K.RECON_CDL2] * 1000)]), logger=logger)
     print_log('[Validation] EPOCH: %d  Metrics = %s' % (epoch, ['%.4f' % m for m in agg["overall"]]), logger=logger)
     print_log('============================ TEST RESULTS ============================', logger=logger)
-    print_log('\n' + results_table(agg["per_taxonomy"], agg["overall"], FullMetrics.names(), _synset_names()), logger=logger)
+    print_log('\n' + results_table(per_taxonomy, overall, names, _synset_names()), logger=logger)
     if val_writer is not None:
         val_writer.add_scalar('Loss/Epoch/Sparse', agg["losses"][0], epoch)
         val_writer.add_scalar('Loss/Epoch/Dense', agg["losses"][2], epoch)
-        for name, v in zip(FullMetrics.names(), agg["overall"]):
+        for name, v in zip(names, overall):
             val_writer.add_scalar('Metric/%s' % name, v, epoch)
     m = FullMetrics(config.consider_metric, list(agg["overall"]))
     m.per_taxonomy, m.losses, m.rows, m.taxonomy_ids, m.model_ids = agg["per_taxonomy"], agg["losses"], rows, taxonomy_ids, model_ids
+    if emd_val:
+        m.emd = emd                                                   # not a Metrics item: better_than / state_dict do not see it
     return m
 
 

@@ -1,6 +1,8 @@
 """Stage-I reconstruction metrics (reference: utils/metrics.py): F-Score@0.01, CDL1, CDL2 (the Chamfer distances with ``ignore_zeros``, x1000),
 with the reference's ``Metrics`` surface.  The values come from one ``kernels.recon_eval`` launch per batch instead of open3d KD-tree queries
-on the host and two Chamfer calls per cloud; ``Metrics.get`` needs CUDA tensors like every other op of this package."""
+on the host and two Chamfer calls per cloud; ``Metrics.get`` needs CUDA tensors like every other op of this package.
+
+``emd_distance`` is the opt-in second reconstruction distance (extensions/emd); it is not one of ``Metrics.ITEMS``."""
 import logging
 
 import torch
@@ -88,3 +90,23 @@ class Metrics(object):
         else:
             raise ValueError('Metrics: no metric named %r to compare by' % (self.metric_name,))
         return self._values[i] > other._values[i] if item['is_greater_better'] else self._values[i] < other._values[i]
+
+
+def emd_distance(pred, gt, eps=None):
+    """Earth Mover's Distance of every cloud of a batch, on the scale CDL1 is reported on: (values, info) with values a float64 device tensor
+    [B] of mean_i sqrt(dist_i) * 1000 over the one-to-one matching of ``extensions.emd`` (sum of squared distances within N * eps of the
+    optimum), and info the int32 device tensor [B] of that solve (rounds used, negative when the round cap was hit).  Nothing is read on the
+    host.  ``eps``: None -> ``extensions.emd.DEFAULT_EPS``.
+
+    The matching needs clouds of one size.  When ``pred`` has more points than ``gt`` (Stage-I: dense 2,048 against 1,024) it is first reduced
+    to ``gt``'s count by farthest-point sampling from index 0 (``misc.fps``).  That rule is this project's own protocol, not the reference's,
+    which has no EMD; fewer points than ``gt`` raise ValueError."""
+    from ..extensions.emd import DEFAULT_EPS, emd_cuda
+    n, m = pred.shape[1], gt.shape[1]
+    if n < m:
+        raise ValueError(f"emd_distance: the prediction has {n} points and the ground truth {m}; a prediction is only ever reduced")
+    if n > m:
+        from .misc import fps
+        pred = fps(pred.detach(), m)
+    dist, _, info = emd_cuda.forward(pred.detach(), gt, DEFAULT_EPS if eps is None else eps)
+    return dist.double().sqrt().mean(dim=1) * 1000.0, info

@@ -819,6 +819,33 @@ int act_knn_probe_search_f32(const float* Q, int Nq, const float* bank, int Nb, 
 int act_knn_probe_vote_f32(const float* sim, const int32_t* idx, int Nq, int kmax, const int32_t* bank_cls, int Nb, const int32_t* q_cls, int C,
                            const int* ks, int nk, float T, float* scores, long long* pred, long long* counts, act_stream_t stream);
 
+/* ---- Earth Mover's Distance between equal-sized clouds (csrc/emd.hip) ------------------------------------------------------------------
+ * xyz1, xyz2 fp32 [B,N,3], 1 <= N <= act_emd_max_points(): the bijection a that minimises sum_i |xyz1[i] - xyz2[a(i)]|^2, by a forward
+ * auction with eps-scaling (Bertsekas), one workgroup per pair for the whole solve, all state in LDS.  xyz1 are the bidders, xyz2 the objects;
+ * cost d_ij = (dx*dx + dy*dy) + dz*dz in fp32, every product and sum rounded.  One round (Jacobi): every unassigned bidder takes its best and
+ * second-best value -(d_ij + price_j) (ties: lower j) and bids price_j1 + (v1 - v2) + eps on j1 (N == 1: price + eps; never less than the next
+ * float above the price); every object that got bids takes the highest (ties: lower bidder), raises its price to it and evicts its owner.
+ * A phase ends when nobody is unassigned; the next one drops all assignments, keeps the prices and runs with eps / 4.  The ladder is
+ * eps_final * 4^k, k descending from the smallest k with eps_final * 4^k >= max_ij d_ij / 4 (so every eps is eps_final times a power of two
+ * and lattice inputs stay exact), and the solve ends after the phase at eps_final.  Then, in exact arithmetic,
+ *     sum_i dist[i] <= optimum + N * eps_final;
+ * in fp32 every comparison carries at most 3 ulp of the largest d_ij + price_j on top of eps_final.
+ * The rounds of all phases together are capped by max_rounds (>= 1): when the cap is hit the bidders still unassigned get the objects still
+ * free, both in ascending index order, so `assignment` is ALWAYS a bijection.  Bids are resolved by a 64-bit LDS atomic max whose result does
+ * not depend on arrival order: all outputs are bit-identical run to run and a pair's result does not depend on its batch.
+ * dist fp32 [B,N] = d_{i,a(i)}; assignment int32 [B,N] = a(i); info int32 [B] = rounds used, NEGATED when the cap was hit;
+ * evals uint64 [B] (may be NULL) = bids made, i.e. the sum over rounds of the unassigned bidders (x N = distance evaluations).
+ * eps_final must be positive and finite.  B == 0 is a no-op. */
+int act_emd_max_points(void);
+int act_emd_fwd_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, int max_rounds, float* dist, int32_t* assignment,
+                    int32_t* info, act_stream_t stream);
+int act_emd_fwd_ex_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, int max_rounds, float* dist, int32_t* assignment,
+                       int32_t* info, uint64_t* evals, act_stream_t stream);
+/* gx1[i] = (2 * (xyz1[i] - xyz2[a(i)])) * grad_dist[i], gx2[a(i)] = -gx1[i] (fp32 [B,N,3] each, the operations in this order, no atomics).
+ * Rows of gx2 that `assignment` does not name are zero; an entry outside [0,N) is skipped. */
+int act_emd_bwd_f32(const float* xyz1, const float* xyz2, const int32_t* assignment, const float* grad_dist, int B, int N, float* gx1,
+                    float* gx2, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
