@@ -1288,8 +1288,12 @@ def three_nn(xyz, centers, want_adj=True):
 
 def interp_rows_fwd(P, idx, w, B, N, G, xyz=None, wxyz=None, bias=None):
     """P [B*G,C] -> Y [B*N,C] = sum_k w * P[idx] (+ xyz . wxyz^T + bias)"""
-    P = _f32c(P)
+    P, idx, w = _f32c(P), _i32c(idx), _f32c(w)
+    xyz, wxyz, bias = (None if t is None else _f32c(t) for t in (xyz, wxyz, bias))
     C = P.shape[1]
+    if P.shape[0] != B * G or idx.numel() != 3 * B * N or w.numel() != 3 * B * N or (xyz is not None and xyz.numel() != 3 * B * N) or (
+            wxyz is not None and wxyz.shape != (C, 3)) or (bias is not None and bias.numel() != C):
+        raise _C.ActHipError("interp_rows_fwd: operand shapes do not match B, N, G, C")
     Y = torch.empty(B * N, C, dtype=torch.float32, device=P.device)
     check(lib.act_interp_rows_fwd_f32(ptr(P), ptr(idx), ptr(w), ptr(xyz), ptr(wxyz), ptr(bias), B, N, G, C, ptr(Y), stream()),
           "act_interp_rows_fwd_f32")
@@ -1297,8 +1301,10 @@ def interp_rows_fwd(P, idx, w, B, N, G, xyz=None, wxyz=None, bias=None):
 
 
 def interp_rows_bwd(dY, off, ent, w, B, N, G):
-    dY = _f32c(dY)
+    dY, off, ent, w = _f32c(dY), _i32c(off), _i32c(ent), _f32c(w)
     C = dY.shape[1]
+    if dY.shape[0] != B * N or off.numel() != B * (G + 1) or ent.numel() != 3 * B * N or w.numel() != 3 * B * N:
+        raise _C.ActHipError("interp_rows_bwd: operand shapes do not match B, N, G")
     dP = torch.empty(B * G, C, dtype=torch.float32, device=dY.device)
     check(lib.act_interp_rows_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_bwd_f32")
     return dP
@@ -1306,8 +1312,10 @@ def interp_rows_bwd(dY, off, ent, w, B, N, G):
 
 def interp_xyz_grad(dY, xyz, want_w=True, want_b=True):
     """-> (dY^T xyz [C,3] | None, column sums of dY [C] | None)"""
-    dY = _f32c(dY)
+    dY, xyz = _f32c(dY), _f32c(xyz)
     R, C = dY.shape
+    if xyz.numel() != 3 * R:
+        raise _C.ActHipError("interp_xyz_grad: xyz must hold 3 values per row of dY")
     dw = torch.empty(C, 3, dtype=torch.float32, device=dY.device) if want_w else None
     db = torch.empty(C, dtype=torch.float32, device=dY.device) if want_b else None
     ws = workspace(dY.device, lib.act_interp_xyz_grad_workspace(R, C))
