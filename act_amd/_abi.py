@@ -280,6 +280,13 @@ _TABLE = {
     "act_emd_fwd_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
     "act_emd_fwd_ex_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "act_emd_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    # PointNet++ set abstraction (csrc/sa.hip)
+    "act_ball_query_f32": [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp],
+    "act_group_rows_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "act_group_rows_bwd_workspace": (_sz, [_i, _i, _i, _i]),
+    "act_group_rows_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
+    "act_group_gather_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "act_group_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -2178,3 +2178,139 @@ def augment(pc, ops, draws=None, seed=0, seed_dev=None, force_global=False):
     check(lib.act_augment_f32(ptr(pc), B, N, table, len(ops), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(seed_dev), AUG_GLOBAL if force_global else 0,
                               stream()), "act_augment_f32")
     return pc
+
+
+# ---- PointNet++ set abstraction (csrc/sa.hip): radius search, grouped rows and their deterministic backward -----------------------------------
+def _sa_f32(t, name, shape):
+    """float32 CUDA operand ``name`` whose shape matches ``shape`` (None entries are free), made contiguous"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _C.ActHipError(f"{name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise _C.ActHipError(f"{name}: expected float32, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise _C.ActHipError(f"{name}: expected shape {['*' if s is None else s for s in shape]}, got {list(t.shape)}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _sa_idx(idx, name, B):
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+        raise _C.ActHipError(f"{name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if idx.dtype not in (torch.int32, torch.int64):
+        raise _C.ActHipError(f"{name}: expected int32 (or int64) indices, got {idx.dtype}")
+    if idx.dim() != 3 or idx.shape[0] != B or idx.shape[1] < 1 or idx.shape[2] < 1:
+        raise _C.ActHipError(f"{name}: expected shape [{B}, S, nsample], got {list(idx.shape)}")
+    return _i32c(idx)
+
+
+def ball_query(xyz, new_xyz, radius, nsample, inclusive=False, want_cnt=False):
+    """xyz [B,N,3], new_xyz [B,S,3] -> idx int32 [B,S,nsample] (and cnt int32 [B,S] = min(hits, nsample) with ``want_cnt``): the lowest
+    ``nsample`` indices within the radius in ascending order, the rest of the row repeating the first hit, zeros when nothing is in reach.
+    ``inclusive=False``: d2 < r^2 (upstream pointnet2_ops); ``inclusive=True``: d2 <= r^2 (the reference's query_ball_point).  d2 is the fp32
+    difference form, r^2 the fp32 product."""
+    xyz = _sa_f32(xyz, "ball_query: xyz", (None, None, 3))
+    B, N, _ = xyz.shape
+    new_xyz = _sa_f32(new_xyz, "ball_query: new_xyz", (B, None, 3))
+    S = new_xyz.shape[1]
+    nsample = int(nsample)
+    if nsample < 1:
+        raise _C.ActHipError(f"ball_query: nsample must be >= 1, got {nsample}")
+    if not float(radius) >= 0.0:
+        raise _C.ActHipError(f"ball_query: radius must be >= 0, got {radius}")
+    if B < 1 or N < 1 or S < 1:
+        raise _C.ActHipError(f"ball_query: xyz {list(xyz.shape)} / new_xyz {list(new_xyz.shape)} must not be empty")
+    idx = torch.empty(B, S, nsample, dtype=torch.int32, device=xyz.device)
+    cnt = torch.empty(B, S, dtype=torch.int32, device=xyz.device) if want_cnt else None
+    check(lib.act_ball_query_f32(ptr(xyz), ptr(new_xyz), B, N, S, float(radius), nsample, int(bool(inclusive)), ptr(idx), ptr(cnt), stream()),
+          "act_ball_query_f32")
+    return (idx, cnt) if want_cnt else idx
+
+
+def _adj_workspace(dev, B, N, S, ns):
+    return workspace(dev, lib.act_group_rows_bwd_workspace(B, N, S, ns))
+
+
+class GroupRowsFn(torch.autograd.Function):
+    """sample_and_group's gather in row form: rows [B*S*nsample, (3 if use_xyz) + D], row (b,s,j) = xyz[b,i] - new_xyz[b,s] | feat[b,i];
+    the backward gathers over the inverse adjacency in ascending (s, j) order (no atomics, bit-identical run to run).  xyz, new_xyz and idx are
+    constants: the cloud is a leaf, as in InterpRowsFn."""
+
+    @staticmethod
+    def forward(ctx, feat, xyz, new_xyz, idx, use_xyz):
+        B, S, ns = idx.shape
+        N = xyz.shape[1] if xyz is not None else feat.shape[1]
+        D = 0 if feat is None else feat.shape[2]
+        dev = idx.device
+        rows = torch.empty(B * S * ns, (3 if use_xyz else 0) + D, dtype=torch.float32, device=dev)
+        check(lib.act_group_rows_fwd_f32(ptr(xyz) if use_xyz else None, ptr(new_xyz) if use_xyz else None, ptr(feat), ptr(idx), B, N, S, ns, D,
+                                         int(use_xyz), ptr(rows), stream()), "act_group_rows_fwd_f32")
+        ctx.save_for_backward(idx)
+        ctx.dims = (B, N, S, ns, D, int(use_xyz))
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        (idx,) = ctx.saved_tensors
+        B, N, S, ns, D, use_xyz = ctx.dims
+        if D == 0 or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        drows = _f32c(drows, "group_rows: grad")
+        dfeat = torch.empty(B, N, D, dtype=torch.float32, device=drows.device)
+        ws = _adj_workspace(drows.device, B, N, S, ns)
+        check(lib.act_group_rows_bwd_f32(ptr(drows), ptr(idx), B, N, S, ns, D, use_xyz, ptr(dfeat), ptr(ws), ws.numel() * 4, stream()),
+              "act_group_rows_bwd_f32")
+        return dfeat, None, None, None, None
+
+
+def group_rows(xyz, new_xyz, feat, idx, use_xyz=True):
+    """xyz [B,N,3], new_xyz [B,S,3], feat [B,N,D] or None, idx int [B,S,nsample] -> rows [B*S*nsample, (3 if use_xyz) + D], differentiable
+    in ``feat``"""
+    if feat is None and not use_xyz:
+        raise _C.ActHipError("group_rows: feat is None and use_xyz is False: nothing to group")
+    if use_xyz:
+        xyz = _sa_f32(xyz, "group_rows: xyz", (None, None, 3))
+        B, N = xyz.shape[0], xyz.shape[1]
+        idx = _sa_idx(idx, "group_rows: idx", B)
+        new_xyz = _sa_f32(new_xyz, "group_rows: new_xyz", (B, idx.shape[1], 3))
+        if feat is not None:
+            feat = _sa_f32(feat, "group_rows: feat", (B, N, None))
+    else:
+        feat = _sa_f32(feat, "group_rows: feat", (None, None, None))
+        idx = _sa_idx(idx, "group_rows: idx", feat.shape[0])
+        xyz = new_xyz = None
+    if feat is not None and feat.shape[2] < 1:
+        raise _C.ActHipError(f"group_rows: feat: expected at least one channel, got {list(feat.shape)}")
+    return GroupRowsFn.apply(feat, xyz, new_xyz, idx, bool(use_xyz))
+
+
+class GroupingOperationFn(torch.autograd.Function):
+    """upstream pointnet2_ops grouping_operation: features [B,C,N], idx int32 [B,S,nsample] -> [B,C,S,nsample]; the backward sums, per point and
+    channel, the incoming gradients in ascending (s, j) order (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, features, idx):
+        features = _sa_f32(features, "grouping_operation: features", (None, None, None))
+        B, C, N = features.shape
+        idx = _sa_idx(idx, "grouping_operation: idx", B)
+        _, S, ns = idx.shape
+        if C < 1 or N < 1:
+            raise _C.ActHipError(f"grouping_operation: features: expected a non-empty [B, C, N], got {list(features.shape)}")
+        out = torch.empty(B, C, S, ns, dtype=torch.float32, device=features.device)
+        check(lib.act_group_gather_f32(ptr(features), ptr(idx), B, C, N, S, ns, ptr(out), stream()), "act_group_gather_f32")
+        ctx.save_for_backward(idx)
+        ctx.dims = (B, C, N, S, ns)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        B, C, N, S, ns = ctx.dims
+        dout = _f32c(dout, "grouping_operation: grad")
+        df = torch.empty(B, C, N, dtype=torch.float32, device=dout.device)
+        ws = _adj_workspace(dout.device, B, N, S, ns)
+        check(lib.act_group_gather_bwd_f32(ptr(dout), ptr(idx), B, C, N, S, ns, ptr(df), ptr(ws), ws.numel() * 4, stream()),
+              "act_group_gather_bwd_f32")
+        return df, None
+
+
+def grouping_operation(features, idx):
+    return GroupingOperationFn.apply(features, idx)

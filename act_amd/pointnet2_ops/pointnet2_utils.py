@@ -1,7 +1,9 @@
-"""Drop-in for the two pointnet2_ops entry points ACT uses (utils/misc.py:44-45):
-``furthest_point_sample`` and ``gather_operation``, backed by act_fps_f32 /
-act_gather_points_f32 (include/act_hip.h)."""
+"""Drop-in for the pointnet2_ops entry points: ``furthest_point_sample`` and ``gather_operation`` (the two ACT uses, utils/misc.py:44-45),
+backed by act_fps_f32 / act_gather_points_f32, and the grouping family of a PointNet++ baseline -- ``ball_query``, ``grouping_operation``,
+``QueryAndGroup``, ``GroupAll`` -- backed by csrc/sa.hip (include/act_hip.h).  ``three_nn`` / ``three_interpolate`` in upstream's form
+(distances, not weights) are not provided: the project's three-NN kernel (kernels.three_nn) returns the normalised weights."""
 import torch
+import torch.nn as nn
 
 from .. import _C
 
@@ -80,3 +82,49 @@ class GatherOperation(torch.autograd.Function):
 
 
 gather_operation = GatherOperation.apply
+
+
+def ball_query(radius, nsample, xyz, new_xyz):
+    """upstream's signature and rule: xyz [B,N,3], new_xyz [B,S,3] -> int32 [B,S,nsample], the first ``nsample`` indices with d2 < radius^2
+    in ascending order, the rest of the row repeating the first hit (a row of zeros when nothing is in reach).  Non-differentiable."""
+    from .. import kernels as K
+    return K.ball_query(xyz, new_xyz, radius, nsample, inclusive=False)
+
+
+def grouping_operation(features, idx):
+    """features f32 [B,C,N], idx int32 [B,S,nsample] -> [B,C,S,nsample]; differentiable in ``features`` (deterministic backward)"""
+    from .. import kernels as K
+    return K.grouping_operation(features, idx)
+
+
+class QueryAndGroup(nn.Module):
+    """upstream QueryAndGroup: forward(xyz [B,N,3], new_xyz [B,S,3], features [B,C,N] or None) -> [B, 3 + C, S, nsample]
+    (grouped xyz minus the centre first; [B, C, S, nsample] with ``use_xyz=False``)."""
+
+    def __init__(self, radius, nsample, use_xyz=True):
+        super().__init__()
+        self.radius, self.nsample, self.use_xyz = radius, nsample, use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        idx = ball_query(self.radius, self.nsample, xyz, new_xyz)
+        grouped_xyz = grouping_operation(xyz.transpose(1, 2).contiguous(), idx) - new_xyz.transpose(1, 2).unsqueeze(-1)
+        if features is None:
+            assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
+            return grouped_xyz
+        grouped = grouping_operation(features, idx)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
+
+
+class GroupAll(nn.Module):
+    """upstream GroupAll: forward(xyz [B,N,3], new_xyz ignored, features [B,C,N] or None) -> [B, 3 + C, 1, N]"""
+
+    def __init__(self, use_xyz=True):
+        super().__init__()
+        self.use_xyz = use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        grouped_xyz = xyz.transpose(1, 2).unsqueeze(2)
+        if features is None:
+            return grouped_xyz
+        grouped = features.unsqueeze(2)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped

@@ -846,6 +846,29 @@ int act_emd_fwd_ex_f32(const float* xyz1, const float* xyz2, int B, int N, float
 int act_emd_bwd_f32(const float* xyz1, const float* xyz2, const int32_t* assignment, const float* grad_dist, int B, int N, float* gx1,
                     float* gx2, act_stream_t stream);
 
+/* ---- PointNet++ set abstraction (csrc/sa.hip; reference models/pointnet2_utils.py:84-155, upstream pointnet2_ops ball_query / group_points) ----
+ * Ball query: xyz [B,N,3], new_xyz [B,S,3] -> idx int32 [B,S,nsample]: for every query the lowest nsample point indices whose squared
+ * distance passes the radius test, in ascending index order; the remaining slots repeat the first hit; a query with no hit gets a row of
+ * zeros.  cnt int32 [B,S] (may be NULL) = min(hits, nsample).  The distance is the DIFFERENCE form (dx*dx + dy*dy) + dz*dz in fp32, every
+ * product and sum rounded; the threshold is the fp32 product radius * radius.  inclusive == 0: d2 < radius^2 (upstream pointnet2_ops);
+ * inclusive != 0: d2 <= radius^2 (the reference's torch form, which drops sqrdists > radius ** 2).  Any N >= 1, nsample >= 1; B <= 65535. */
+int act_ball_query_f32(const float* xyz, const float* new_xyz, int B, int N, int S, float radius, int nsample, int inclusive, int32_t* idx,
+                       int32_t* cnt, act_stream_t stream);
+/* rows [B*S*nsample, (use_xyz ? 3 : 0) + D]: row (b,s,j) = xyz[b,i] - new_xyz[b,s] (if use_xyz) followed by feat[b,i,:] (feat [B,N,D]; NULL
+ * when D == 0), i = idx[b,s,j]: sample_and_group's output in the row layout of the row GEMMs.  An index outside [0,N) gives a row of zeros. */
+int act_group_rows_fwd_f32(const float* xyz, const float* new_xyz, const float* feat, const int32_t* idx, int B, int N, int S, int nsample, int D,
+                           int use_xyz, float* rows, act_stream_t stream);
+/* dfeat [B,N,D] = for every point the sum of the feature columns of the rows that gathered it, in ascending (s, j) order over an inverse
+ * adjacency built in the workspace (count, exclusive scan, fill; no atomics): bit-identical run to run.  The xyz columns carry no gradient. */
+size_t act_group_rows_bwd_workspace(int B, int N, int S, int nsample);
+int act_group_rows_bwd_f32(const float* drows, const int32_t* idx, int B, int N, int S, int nsample, int D, int use_xyz, float* dfeat,
+                           void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* upstream's channel-first grouping: features [B,C,N], idx [B,S,nsample] -> out [B,C,S,nsample] (index outside [0,N): 0), and its backward
+ * dfeatures [B,C,N] over the same adjacency (workspace: act_group_rows_bwd_workspace).  B, C <= 65535. */
+int act_group_gather_f32(const float* features, const int32_t* idx, int B, int C, int N, int S, int nsample, float* out, act_stream_t stream);
+int act_group_gather_bwd_f32(const float* dout, const int32_t* idx, int B, int C, int N, int S, int nsample, float* dfeatures, void* workspace,
+                             size_t workspace_bytes, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
