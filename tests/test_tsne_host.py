@@ -1,5 +1,6 @@
 """CPU: the float64 t-SNE reference of tests/tsne_ref.py checked against its own definitions (no package is an authority), and the text fallback of
-utils.tsne_utils.plot_tsne."""
+utils.tsne_utils.plot_tsne; the CSR / blocked forms of the gradient, KL and step against the dense ones, and the generators of
+tests/test_gpu_tsne_edges.py against what they promise."""
 import builtins
 
 import numpy as np
@@ -60,6 +61,63 @@ def test_a_step_leaves_the_embedding_centred_and_follows_the_gain_rule():
     assert flip.any() and (~flip).any()
     assert np.allclose(gains2[flip], 0.211) and np.all(gains2[~flip] == 0.01)          # 0.011 * 0.8 is under the floor
     assert np.allclose(upd2, 0.5 * upd - 200.0 * gains2 * g)
+
+
+def _csr_of(label):
+    return R.affinities(label)[4:7]
+
+
+@pytest.mark.parametrize("label", ["A", "B"])
+def test_csr_gradient_kl_and_step_agree_with_the_dense_ones(label):
+    """attraction along the CSR and the all-pairs part over row blocks (B has a ragged second block) against the N x N x 2 forms, to 1e-12"""
+    P = R.affinities(label)[3]
+    csr = _csr_of(label)
+    N = P.shape[0]
+    assert (label == "B") == (N > R.PAIR_BLOCK)
+    rel = lambda a, b: np.abs(a - b).max() / np.abs(b).max()
+    for state, ex in ((0, 12.0), (1, 1.0)):
+        Y, U, G = R.embeddings(label)[state]
+        g, Z = R.gradient(P, Y, ex)
+        gc, Zc = R.gradient_csr(*csr, Y, ex)
+        pairs = R.repulsion(Y)
+        dense, sparse = R.step(P, Y, U, G, ex, 0.8, 200.0), R.step_csr(*csr, Y, U, G, ex, 0.8, 200.0, pairs=pairs)
+        worst = max([rel(gc, g), abs(Zc / Z - 1), abs(R.kl_csr(*csr, Y) / R.kl(P, Y) - 1), abs(R.kl_csr(*csr, Y, pairs=pairs) / R.kl(P, Y) - 1)] +
+                    [rel(b, a) for a, b in zip(dense, sparse)])
+        print(f"{label} state {state}: worst relative difference {worst:.2e}")
+        assert worst <= 1e-12
+        assert np.array_equal(dense[2], sparse[2])                                                  # the same gain branch everywhere
+
+
+@pytest.mark.parametrize("N,deg", [(300, 20), (1100, 80)])
+def test_random_csr_is_symmetric_sorted_and_sums_to_one(N, deg):
+    indptr, indices, values = R.random_csr(N, deg, 3)
+    assert indptr.dtype == indices.dtype == np.int32 and indptr[0] == 0 and indptr[-1] == len(indices) == len(values)
+    rows = np.repeat(np.arange(N), np.diff(indptr))
+    assert np.all(np.diff(rows.astype(np.int64) * N + indices) > 0)                                 # row-major, columns ascending, no entry twice
+    assert np.all(rows != indices) and indices.min() >= 0 and indices.max() < N
+    P = np.zeros((N, N))
+    P[rows, indices] = values
+    assert np.array_equal(P, P.T) and np.all(values > 0) and abs(values.sum() - 1) < 1e-12
+    if deg == 80:
+        assert (np.diff(indptr) > 64).mean() > 0.5 and (np.diff(indptr) <= 64).any()                 # rows on both sides of one wave
+
+
+def test_hub_idx_has_the_in_degrees_it_promises():
+    hubs = {7: 1299, 650: 600, 1000: 0, 3: 257}
+    idx = R.hub_idx(1300, 5, hubs)
+    assert idx.shape == (1300, 5) and idx.dtype == np.int32 and idx.min() >= 0 and idx.max() < 1300
+    assert np.all(idx != np.arange(1300)[:, None])
+    assert all(len(set(row)) == 5 for row in idx.tolist())
+    indeg = np.bincount(idx.ravel(), minlength=1300)
+    assert {h: int(indeg[h]) for h in hubs} == hubs
+    assert np.array_equal(idx, R.hub_idx(1300, 5, hubs))
+
+
+def test_make_lowrank_has_rank_r_and_the_labels_of_make():
+    X, y = R.make_lowrank(200, 40, 4, 5, 1.0)
+    assert X.dtype == np.float32 and X.shape == (200, 40) and np.array_equal(y, R.make(200, 12, 4, 5, 1.0)[1])
+    sv = np.linalg.svd(X.astype(np.float64), compute_uv=False)
+    assert sv[11] > 1e-2 * sv[0] and sv[12] < 1e-6 * sv[0]
 
 
 def test_plot_tsne_writes_its_text_fallback(tmp_path, monkeypatch):

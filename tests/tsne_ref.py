@@ -1,6 +1,10 @@
 """Shared pieces of the t-SNE tests: the generated problems and a float64 numpy restatement of every stage of csrc/tsne.hip -- cosine kNN by
 stable argsort, the perplexity bisection, the dense symmetrisation and its CSR pattern, the gradient, one step, KL, the PCA initialisation by
-numpy.linalg.eigh, a whole fit.  Everything is computed once per process."""
+numpy.linalg.eigh, a whole fit.  Everything is computed once per process.
+
+The second half serves tests/test_gpu_tsne_edges.py: low-rank features for sizes at which isotropic data has no decidable neighbour sets, kNN of an
+array, the gradient / KL / step along a CSR with the all-pairs part taken over row blocks (no N x N x 2 array), a random symmetric CSR and a
+neighbour table with chosen in-degrees."""
 import functools
 
 import numpy as np
@@ -232,3 +236,128 @@ def fit_floor():
         kls.append(kl(P, Y))
         agr.append(knn_label_agreement(Y, y[perm]))
     return tuple(kls), tuple(agr)
+
+
+# ---- sizes past one wave, one scan chunk and one repulsion chunk (tests/test_gpu_tsne_edges.py) ------------------------------------------------
+def make_lowrank(N, D, K, seed, sep, r=12):
+    """features of rank r: the latent clusters of make(N, r, ...) with axis a scaled by 1 / sqrt(a + 1), mixed into D columns by a fixed Gaussian
+    matrix.  Isotropic Gaussian rows at D >= 260 concentrate the cosine distances until more than 2 % of the rows have a k-th / (k+1)-th gap under
+    1e-5; these keep that share near 1 % and separate the leading eigenvalues of the covariance.  -> (X float32 [N,D], labels)"""
+    Z, y = make(N, r, K, seed, sep)
+    A = np.random.default_rng(seed + 1000).normal(size=(r, D)) / np.sqrt(r)
+    X = (Z.astype(np.float64) * (1.0 / np.sqrt(np.arange(1, r + 1)))) @ A
+    return X.astype(np.float32), y
+
+
+def knn_of(X, k):
+    """knn() of an array -> (idx int32 [N,k], dist float64 [N,k], gap float64 [N])"""
+    N = X.shape[0]
+    Dm = cosine_distances(X)
+    order = np.argsort(Dm, axis=1, kind="stable")
+    srt = np.take_along_axis(Dm, order, axis=1)
+    gap = srt[:, k] - srt[:, k - 1] if k < N - 1 else np.full(N, np.inf)
+    return order[:, :k].astype(np.int32), srt[:, :k].copy(), gap
+
+
+PAIR_BLOCK = 512
+
+
+def repulsion(Y):
+    """the all-pairs part of a step over blocks of PAIR_BLOCK rows -> (R [N,2] = sum_j w_ij^2 (y_i - y_j), Z = sum_{i != j} w_ij)"""
+    Y = np.asarray(Y, np.float64)
+    N = Y.shape[0]
+    R, Z = np.empty((N, 2)), 0.0
+    for b in range(0, N, PAIR_BLOCK):
+        e = min(N, b + PAIR_BLOCK)
+        dx, dy = Y[b:e, None, 0] - Y[None, :, 0], Y[b:e, None, 1] - Y[None, :, 1]
+        w = 1.0 / (1.0 + dx * dx + dy * dy)
+        w[np.arange(e - b), np.arange(b, e)] = 0.0
+        Z += w.sum()
+        w *= w
+        R[b:e, 0], R[b:e, 1] = (w * dx).sum(1), (w * dy).sum(1)
+    return R, Z
+
+
+def _csr_edges(indptr, indices, Y):
+    """-> (row of every entry, y_row - y_column [nnz,2], w of the pair [nnz])"""
+    rows = np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
+    diff = Y[rows] - Y[np.asarray(indices)]
+    return rows, diff, 1.0 / (1.0 + (diff * diff).sum(1))
+
+
+def gradient_csr(indptr, indices, values, Y, exaggeration=1.0, pairs=None):
+    """gradient() with P given as a CSR; pairs: repulsion(Y) where the caller already has it -> (g [N,2], Z)"""
+    Y = np.asarray(Y, np.float64)
+    N = Y.shape[0]
+    R, Z = repulsion(Y) if pairs is None else pairs
+    rows, diff, w = _csr_edges(indptr, indices, Y)
+    pw = np.asarray(values, np.float64) * w
+    attr = np.stack([np.bincount(rows, pw * diff[:, c], minlength=N) for c in range(2)], axis=1)
+    return exaggeration * attr - R / Z, Z
+
+
+def kl_csr(indptr, indices, values, Y, pairs=None):
+    Y = np.asarray(Y, np.float64)
+    _, Z = repulsion(Y) if pairs is None else pairs
+    _, _, w = _csr_edges(indptr, indices, Y)
+    v = np.asarray(values, np.float64)
+    m = v > 0
+    return float((v[m] * np.log(v[m] / (w[m] / Z))).sum())
+
+
+def step_csr(indptr, indices, values, Y, update, gains, exaggeration, momentum, lr, pairs=None):
+    """step() with P given as a CSR -> (Y, update, gains, g)"""
+    Y, update, gains = (np.asarray(a, np.float64) for a in (Y, update, gains))
+    g, _ = gradient_csr(indptr, indices, values, Y, exaggeration, pairs)
+    flip = np.sign(g) != np.sign(update)
+    gains = np.maximum(np.where(flip, gains + 0.2, gains * 0.8), 0.01)
+    update = momentum * update - lr * gains * g
+    Y = Y + update
+    return Y - Y.mean(0), update, gains, g
+
+
+def random_csr(N, deg, seed):
+    """a symmetric P of about deg entries per row from a random edge list: unordered pairs i < j coded i N + j and made unique, one positive value per
+    pair, both directions sorted by code (row-major, columns ascending); the values sum to 1 -> (indptr int32 [N+1], indices int32, values)"""
+    r = np.random.default_rng(seed)
+    a, b = r.integers(0, N, N * deg // 2), r.integers(0, N, N * deg // 2)
+    keep = a != b
+    lo, hi = np.minimum(a, b)[keep].astype(np.int64), np.maximum(a, b)[keep].astype(np.int64)
+    code = np.unique(lo * N + hi)
+    lo, hi = code // N, code % N
+    v = r.uniform(0.2, 1.8, len(code))
+    both, vals = np.concatenate([lo * N + hi, hi * N + lo]), np.concatenate([v, v])
+    order = np.argsort(both, kind="stable")
+    both, vals = both[order], vals[order]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(both // N, minlength=N))]).astype(np.int32)
+    return indptr, (both % N).astype(np.int32), vals / vals.sum()
+
+
+def hub_idx(N, k, hubs, seed=0):
+    """a neighbour table int32 [N,k] of distinct non-self indices in which row h is named by exactly hubs[h] other rows (the hubs[h] lowest-numbered
+    ones), for every h in hubs; the rest of every row is drawn from the rows that are not in hubs"""
+    r = np.random.default_rng(seed)
+    rows = [[] for _ in range(N)]
+    for h, deg in hubs.items():
+        assert 0 <= deg <= N - 1
+        for s in [i for i in range(N) if i != h][:deg]:
+            rows[s].append(h)
+    free = np.array([i for i in range(N) if i not in hubs])
+    out = np.empty((N, k), np.int32)
+    for i in range(N):
+        assert len(rows[i]) <= k
+        pool = free[free != i]
+        row = np.concatenate([np.array(rows[i], np.int64), r.choice(pool, k - len(rows[i]), replace=False)])
+        out[i] = r.permutation(row)
+    return out
+
+
+def edge_state(N, which):
+    """the states the large step tests start from -> (Y, update, gains), centred Y: 0 = N(0, 1e-4^2), no update, unit gains (the first iteration);
+    1 = N(0, 3^2), so that w covers (0, 1], updates N(0, 0.05^2) of either sign and gains between the floor 0.01 and 4"""
+    r = np.random.default_rng(100 + which)
+    Y = r.normal(size=(N, 2)) * (1e-4 if which == 0 else 3.0)
+    Y -= Y.mean(0)
+    if which == 0:
+        return Y, np.zeros((N, 2)), np.ones((N, 2))
+    return Y, r.normal(size=(N, 2)) * 0.05, np.maximum(r.uniform(-0.2, 4.0, size=(N, 2)), 0.01)
