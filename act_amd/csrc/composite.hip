@@ -70,10 +70,13 @@ int gemm_nn(int M, int N, int K, const float* A, int lda, const float* B, int ld
     return act_sgemm_f32(1, 0, M, N, K, A, lda, B, ldb, C, ldc, &e, ws, wsb, s);
 }
 // dW[M,N] = dY[K,M]^T . X[K,N]               weight gradient: both operands stored [K][*]
-int gemm_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* ws, size_t wsb, hipStream_t s) {
+int gemm_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const act_gemm_epilogue_t& e, float* ws, size_t wsb,
+            hipStream_t s) {
     if (collecting(0, 0, M, N, K)) return 0;
-    const act_gemm_epilogue_t e = epi0();
     return act_sgemm_f32(0, 0, M, N, K, A, lda, B, ldb, C, ldc, &e, ws, wsb, s);
+}
+int gemm_tn(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, float* ws, size_t wsb, hipStream_t s) {
+    return gemm_tn(M, N, K, A, lda, B, ldb, C, ldc, epi0(), ws, wsb, s);
 }
 int colsum(const float* in, int R, int C, float* out, float* ws, size_t wsb, hipStream_t s) {
     if (t_collect) return 0;
@@ -636,13 +639,21 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
 //    max-pools are epilogues (the 512 -> C conv does not even store its output), and the weight gradients of the convs behind a
 //    BatchNorm recompute the activated operand on load.  Per forward: 2 statistics passes, 2 apply passes, 2 max-pool passes and the
 //    h4 store (1.4 ms of the 35 ms Stage-II step for the two encoders) disappear.
+//    Composed (ACT_PN_COMPOSE=0 disables): nothing but the first max-pool stands between the 128 -> 256 conv and the local half W3b of the
+//    512 -> 512 conv, so  h3 = (a1 . (W3b W2)^T + W3b b2) + gw  contracts over 128 channels instead of 256 and h2 is never stored (the 128 -> 256
+//    conv only leaves its group max); the backward products of the pair shrink the same way (act_pointnet_bwd_f32).  Exact in real arithmetic,
+//    not bit-identical to the sequential form.
 //  * plain: one kernel per layer (tiny test geometries, odd channel counts).
 namespace {
-struct PnSaved { float *h1, *a1, *h2, *fg, *gw, *h3, *a3, *h4, *st1, *st2, *tstats; int32_t *arg1, *arg2; };   // st* = mean | rstd | scale | shift
+struct PnSaved { float *h1, *a1, *h2, *fg, *gw, *h3, *a3, *h4, *st1, *st2, *tstats, *w32, *b32; int32_t *arg1, *arg2; };   // st* = mean | rstd | scale | shift
 bool pn_fused(const act_pointnet_dims_t& d) {
     static const bool on = [] { const char* e = getenv("ACT_PN_FUSE"); return !(e && e[0] == '0'); }();
     const long long R = (long long)d.BG * d.n;
     return on && (d.n == 32 || d.n == 64) && R % 128 == 0 && d.C % 64 == 0;
+}
+bool pn_compose(const act_pointnet_dims_t& d) {
+    static const bool on = [] { const char* e = getenv("ACT_PN_COMPOSE"); return !(e && e[0] == '0'); }();
+    return on && pn_fused(d);
 }
 // fused schedule with C % 128 == 0: the scattered gradient of the second max-pool (dh4, [R][C]) is never written -- the two GEMMs that
 // consume it generate it from (dout, arg2) while they stage their A operand, and the first pool's scatter-add is an epilogue of the GEMM
@@ -662,20 +673,23 @@ bool pn_pool_bwd_live() {                                                       
 }
 size_t carve_pn(float* base, const act_pointnet_dims_t& d, PnSaved& sv) {
     const size_t R = (size_t)d.BG * d.n, BG = d.BG, C = d.C;
-    const bool fused = pn_fused(d);
+    const bool fused = pn_fused(d), composed = pn_compose(d);
     Carver c(base);
-    sv.h1 = c.take(R * 128); sv.h2 = c.take(R * 256); sv.fg = c.take(BG * 256); sv.gw = c.take(BG * 512); sv.h3 = c.take(R * 512);
+    sv.h1 = c.take(R * 128); sv.h2 = composed ? nullptr : c.take(R * 256); sv.fg = c.take(BG * 256); sv.gw = c.take(BG * 512); sv.h3 = c.take(R * 512);
+    sv.w32 = composed ? c.take(512 * 128) : nullptr; sv.b32 = composed ? c.take(512) : nullptr;          // W3b W2 | W3b b2
     sv.st1 = c.take(4 * 128); sv.st2 = c.take(4 * 512);
     sv.arg1 = reinterpret_cast<int32_t*>(c.take(BG * 256)); sv.arg2 = reinterpret_cast<int32_t*>(c.take(BG * C));
     if (fused) { sv.a1 = sv.a3 = sv.h4 = nullptr; sv.tstats = c.take(act_sgemm_fx_tile_stats_floats((int)R, 512)); }
     else { sv.a1 = c.take(R * 128); sv.a3 = c.take(R * 512); sv.h4 = c.take(R * C); sv.tstats = nullptr; }
     return c.used;
 }
-struct PnBwdScratch { float *dh4, *da3, *dh3, *dgw, *dh2, *dfg, *da1, *dh1, *act; int32_t* live; };
+struct PnBwdScratch { float *dh4, *da3, *dh3, *dgw, *dh2, *dfg, *da1, *dh1, *act, *g32; int32_t* live; };
 size_t carve_pn_bwd(float* base, const act_pointnet_dims_t& d, PnBwdScratch& sc) {
     const size_t R = (size_t)d.BG * d.n, BG = d.BG, C = d.C;
     Carver c(base);
-    sc.dh4 = pn_pool_bwd_on_load(d) ? nullptr : c.take(R * C); sc.da3 = c.take(R * 512); sc.dh3 = c.take(R * 512); sc.dgw = c.take(BG * 512); sc.dh2 = c.take(R * 256);
+    sc.dh4 = pn_pool_bwd_on_load(d) ? nullptr : c.take(R * C); sc.da3 = c.take(R * 512); sc.dh3 = c.take(R * 512); sc.dgw = c.take(BG * 512);
+    const bool composed = pn_compose(d);
+    sc.dh2 = composed ? nullptr : c.take(R * 256); sc.g32 = composed ? c.take(512 * 128) : nullptr;    // composed: G = dh3^T . a1 instead of dh2
     sc.dfg = c.take(BG * 256); sc.da1 = c.take(R * 128); sc.dh1 = c.take(R * 128);
     sc.act = (pn_fused(d) && d.C % 128 != 0) ? c.take(R * 512) : nullptr;      // a3 rebuilt for the one weight gradient the fused TN kernel cannot take
     sc.live = reinterpret_cast<int32_t*>(c.take(BG));                            // groups with a non-zero gradient row (Stage II: the visible patches)
@@ -706,7 +720,7 @@ int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet
     if (groups && !pn_fused(*d)) groups = nullptr;                  // (the one-kernel-per-layer schedule computes every group)
     hipStream_t s = (hipStream_t)stream;
     const int BG = d->BG, n = d->n, C = d->C, R = BG * n;
-    const bool fused = pn_fused(*d);
+    const bool fused = pn_fused(*d), composed = pn_compose(*d);
     PnSaved sv; carve_pn(saved, *d, sv);
     float *scale1 = sv.st1 + 2 * 128, *shift1 = sv.st1 + 3 * 128, *scale2 = sv.st2 + 2 * 512, *shift2 = sv.st2 + 3 * 512;
     // statistics of a tensor that is already in HBM (BatchNorm-1 always: its producer is the K = 3 conv; BatchNorm-2 on the plain schedule)
@@ -728,9 +742,13 @@ int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet
         CK(gemm_nt(R, 256, 128, sv.a1, 128, w->c2_w, 128, sv.h2, 256, e, ws, wsb, s));
         RUN(act_group_max_f32(sv.h2, BG, n, 256, sv.fg, sv.arg1, s));
     } else {                                            // conv 128->256 on relu(bn1(h1)) applied on load; max over the group in the epilogue
-        act_gemm_fx_t fx{}; fx.a_scale = scale1; fx.a_shift = shift1; fx.gmax = sv.fg; fx.garg = sv.arg1; fx.group = n; fx.store_c = 1;
-        e = epi0(); e.bias = w->c2_b;
+        act_gemm_fx_t fx{}; fx.a_scale = scale1; fx.a_shift = shift1; fx.gmax = sv.fg; fx.garg = sv.arg1; fx.group = n; fx.store_c = composed ? 0 : 1;
+        e = epi0(); e.bias = w->c2_b;                   // (composed: h2 is only wanted for its group max -- same kernel body, no store)
         CK(gemm_fx(1, 1, R, 256, 128, sv.h1, 128, w->c2_w, 128, sv.h2, 256, e, fx, ws, wsb, s));
+    }
+    if (composed) {                                     // W32 = W3b . W2 and b32 = W3b . b2, from the weights of THIS call (never cached)
+        CK(gemm_nn(512, 128, 256, w->c3_w + 256, 512, w->c2_w, 128, sv.w32, 128, epi0(), ws, wsb, s));
+        CK(gemm_nt(1, 512, 256, w->c2_b, 256, w->c3_w + 256, 512, sv.b32, 512, epi0(), ws, wsb, s));
     }
     // conv 512->512 on cat(global, local): the global half once per group, broadcast-added in the epilogue of the local half
     e = epi0(); e.bias = w->c3_b;
@@ -745,7 +763,14 @@ int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet
         RUN(act_group_max_f32(sv.h4, BG, n, C, out, keep_for_backward ? sv.arg2 : nullptr, s));
         return 0;
     }
-    if (training) {                                     // BatchNorm-2 statistics from the epilogue of the conv that produces h3
+    if (composed) {                                     // h3 = (relu(bn1(h1)) . W32^T + b32) + gw[group]: K = 128, the activation applied on load;
+        e.bias = sv.b32;                                // b2 enters where it did (the per-point half), so gw keeps the bits of the sequential form
+        act_gemm_fx_t fx{}; fx.a_scale = scale1; fx.a_shift = shift1; fx.tile_stats = training ? sv.tstats : nullptr; fx.store_c = 1;
+        CK(gemm_fx(1, 1, R, 512, 128, sv.h1, 128, sv.w32, 128, sv.h3, 512, e, fx, ws, wsb, s));
+        if (training) RUN(act_bn_tiles_finalize_f32(sv.tstats, R / 128, 128, 512, w->bn2_w, w->bn2_b, d->eps2, d->momentum2, w->bn2_mean, w->bn2_var, sv.st2,
+                                                    sv.st2 + 512, scale2, shift2, s));
+        else RUN(act_bn_eval_affine_f32(w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, d->eps2, 512, scale2, shift2, s));
+    } else if (training) {                              // BatchNorm-2 statistics from the epilogue of the conv that produces h3
         act_gemm_fx_t fx{}; fx.tile_stats = sv.tstats; fx.store_c = 1;
         CK(gemm_fx(1, 1, R, 512, 256, sv.h2, 256, w->c3_w + 256, 512, sv.h3, 512, e, fx, ws, wsb, s));
         RUN(act_bn_tiles_finalize_f32(sv.tstats, R / 128, 128, 512, w->bn2_w, w->bn2_b, d->eps2, d->momentum2, w->bn2_mean, w->bn2_var, sv.st2, sv.st2 + 512,
@@ -779,7 +804,7 @@ int act_pointnet_bwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params
     if (bad_pn(d)) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const int BG = d->BG, n = d->n, C = d->C, R = BG * n;
-    const bool fused = pn_fused(*d);
+    const bool fused = pn_fused(*d), composed = pn_compose(*d);
     PnSaved sv; carve_pn(const_cast<float*>(saved), *d, sv);
     PnBwdScratch sc; carve_pn_bwd(scratch, *d, sc);
     auto st = [](float* base, int Cc, int which) { return base + which * Cc; };               // 0 mean, 1 rstd, 2 scale, 3 shift
@@ -820,21 +845,39 @@ int act_pointnet_bwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params
     RUN(act_bn_bwd_groups_f32(sv.h3, sc.da3, st(sv.st2, 512, 2), st(sv.st2, 512, 3), st(sv.st2, 512, 0), st(sv.st2, 512, 1), 1, R, 512, live, n, sc.dh3,
                               g->bn2_w, g->bn2_b, ws, wsb, s));
     // the two column halves of dW3 [512, 512]: [:, :256] from the per-group path, [:, 256:] from the per-point path
-    CK(gemm_tn(512, 256, R, sc.dh3, 512, sv.h2, 256, g->c3_w + 256, 512, ws, wsb, s));
+    if (!composed) CK(gemm_tn(512, 256, R, sc.dh3, 512, sv.h2, 256, g->c3_w + 256, 512, ws, wsb, s));
     RUN(act_group_sum_f32(sc.dh3, BG, n, 512, sc.dgw, s));
     CK(gemm_tn(512, 256, BG, sc.dgw, 512, sv.fg, 256, g->c3_w, 512, ws, wsb, s));
     CK(colsum(sc.dgw, BG, 512, g->c3_b, ws, wsb, s));
     CK(gemm_nn(BG, 256, 512, sc.dgw, 512, w->c3_w, 512, sc.dfg, 256, epi0(), ws, wsb, s));
-    if (pool_on_load) {                                 // dh2 = dh3 . W3[:, 256:] + the first pool's backward of dfg, added in the epilogue
-        act_gemm_fx_t fe{}; fe.ep_src = sc.dfg; fe.ep_arg = sv.arg1; fe.group = n;
-        CK(gemm_fx(1, 0, R, 256, 512, sc.dh3, 512, w->c3_w + 256, 512, sc.dh2, 256, epi0(), fe, ws, wsb, s));
+    if (composed) {
+        // h2 = a1 . W2^T + b2 fed h3 through W3b and the first pool only, so with G = dh3^T . a1 [512, 128], s3 = colsum(dh3) (= db3 above) and
+        // S = dfg scattered to the arg-max rows (one live entry per (group, channel), walked as for the second pool: pool_bwd.hip)
+        //   dW3b = G . W2^T + s3 (x) b2     dW2 = W3b^T . G + S^T . a1     db2 = W3b^T . s3 + sum_g dfg[g]     da1 = dh3 . W32 + S . W2
+        // every R-row product contracts over or produces 128 channels instead of 256.  The sparse terms are written first and the dense products
+        // accumulate onto them in the epilogue: no atomics, a fixed order.
+        act_gemm_epilogue_t ea = epi0(); ea.accumulate = 1;
+        CK(wgrad_act(sc.dh3, 512, sv.h1, nullptr, sv.st1, 128, sc.g32));
+        CK(gemm_nt(512, 256, 128, sc.g32, 128, w->c2_w, 128, g->c3_w + 256, 512, epi0(), ws, wsb, s));
+        CK(gemm_nt(512, 256, 1, g->c3_b, 1, w->c2_b, 1, g->c3_w + 256, 512, ea, ws, wsb, s));
+        RUN(act_group_max_bwd_wgrad_f32(sc.dfg, sv.arg1, BG, n, 256, sv.h1, 128, 128, st(sv.st1, 128, 2), st(sv.st1, 128, 3), g->c2_w, 128, ws, wsb, s));
+        CK(gemm_tn(256, 128, 512, w->c3_w + 256, 512, sc.g32, 128, g->c2_w, 128, ea, ws, wsb, s));
+        CK(colsum(sc.dfg, BG, 256, g->c2_b, ws, wsb, s));
+        CK(gemm_nn(1, 256, 512, g->c3_b, 512, w->c3_w + 256, 512, g->c2_b, 256, ea, ws, wsb, s));
+        RUN(act_group_max_bwd_matmul_live_f32(sc.dfg, sv.arg1, BG, n, 256, w->c2_w, 128, 128, sc.da1, 128, nullptr, s));
+        CK(gemm_nn(R, 128, 512, sc.dh3, 512, sv.w32, 128, sc.da1, 128, ea, ws, wsb, s));
     } else {
-        CK(gemm_nn(R, 256, 512, sc.dh3, 512, w->c3_w + 256, 512, sc.dh2, 256, epi0(), ws, wsb, s));
-        RUN(act_group_max_bwd_f32(sc.dfg, sv.arg1, BG, n, 256, 1, sc.dh2, s));
+        if (pool_on_load) {                                 // dh2 = dh3 . W3[:, 256:] + the first pool's backward of dfg, added in the epilogue
+            act_gemm_fx_t fe{}; fe.ep_src = sc.dfg; fe.ep_arg = sv.arg1; fe.group = n;
+            CK(gemm_fx(1, 0, R, 256, 512, sc.dh3, 512, w->c3_w + 256, 512, sc.dh2, 256, epi0(), fe, ws, wsb, s));
+        } else {
+            CK(gemm_nn(R, 256, 512, sc.dh3, 512, w->c3_w + 256, 512, sc.dh2, 256, epi0(), ws, wsb, s));
+            RUN(act_group_max_bwd_f32(sc.dfg, sv.arg1, BG, n, 256, 1, sc.dh2, s));
+        }
+        CK(wgrad_act(sc.dh2, 256, sv.h1, sv.a1, sv.st1, 128, g->c2_w));
+        CK(colsum(sc.dh2, R, 256, g->c2_b, ws, wsb, s));
+        CK(gemm_nn(R, 128, 256, sc.dh2, 256, w->c2_w, 128, sc.da1, 128, epi0(), ws, wsb, s));
     }
-    CK(wgrad_act(sc.dh2, 256, sv.h1, sv.a1, sv.st1, 128, g->c2_w));
-    CK(colsum(sc.dh2, R, 256, g->c2_b, ws, wsb, s));
-    CK(gemm_nn(R, 128, 256, sc.dh2, 256, w->c2_w, 128, sc.da1, 128, epi0(), ws, wsb, s));
     RUN(act_bn_bwd_f32(sv.h1, sc.da1, st(sv.st1, 128, 2), st(sv.st1, 128, 3), st(sv.st1, 128, 0), st(sv.st1, 128, 1), 1, R, 128, sc.dh1, g->bn1_w, g->bn1_b,
                        ws, wsb, s));
     CK(gemm_tn(128, 3, R, sc.dh1, 128, x, 3, g->c1_w, 3, ws, wsb, s));

@@ -6,6 +6,8 @@ bool launch_sgemm_nt16_fx(const GemmParams& p, int tile, int fx, dim3 grid, hipS
 #define FXL(BN_, MASK) hipLaunchKernelGGL((sgemm_nt16_kernel<128, BN_, false, MASK, false, ACT_EPI_NONE>), grid, dim3(256), 0, s, p); return true
     if (tile == 0) {
         if (fx == FX_COLSTATS) { FXL(128, FX_COLSTATS); }
+        if (fx == FX_AFFINE_A) { FXL(128, FX_AFFINE_A); }                                       // composed conv3 of the mini-PointNet (K = 128), eval
+        if (fx == (FX_AFFINE_A | FX_COLSTATS)) { FXL(128, FX_AFFINE_A | FX_COLSTATS); }         // ... training: BatchNorm-2 tile statistics
         if (fx == (FX_AFFINE_A | FX_GROUPMAX)) { FXL(128, FX_AFFINE_A | FX_GROUPMAX); }
         if (fx == (FX_AFFINE_A | FX_GROUPMAX | FX_NOSTORE)) { FXL(128, FX_AFFINE_A | FX_GROUPMAX | FX_NOSTORE); }
     } else if (tile == 1) {

@@ -103,7 +103,8 @@ __global__ __launch_bounds__(256) void pool_bwd_dx_kernel(const float* __restric
 
 // The same walk with 16-byte loads: a row of N floats takes N / 4 threads, so the workgroup splits into P = 1024 / N parts that take the rows
 // r = p (mod P) -- buckets are laid out part-major so every part walks one contiguous run of the sorted entries.  (Half the load instructions of
-// the float2 form at N = 512: 469 -> 334 us at the Stage-II geometry, 1643 -> 1146 us at C5.)
+// the float2 form at N = 512: 469 -> 334 us at the Stage-II geometry, 1643 -> 1146 us at C5.)  N = 128 (P = 8) is the first pool's term S . W2 of the
+// composed mini-PointNet backward.
 template <int P>
 __global__ __launch_bounds__(256) void pool_bwd_dx4_kernel(const float* __restrict__ dout, const int32_t* __restrict__ arg, const float* __restrict__ W,
                                                            int ldw, int n, int C, float* __restrict__ out, int ldo, int skip_zero, const int32_t* __restrict__ glive) {
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void pool_bwd_dx4_kernel(const float* __restri
     __syncthreads();
 
     constexpr int TP = 256 / P;
-    const int part = tid / TP, q = tid - part * TP;                              // (wave-uniform: TP >= 64)
+    const int part = tid / TP, q = tid - part * TP;                              // (wave-uniform for TP >= 64; P = 8: two parts per wave, each with its own walk)
     const int b_end = (part + 1) * npp;
     int b = part * npp;
     const int j_end = s_start[b_end];
@@ -382,9 +383,10 @@ extern "C" int act_group_max_bwd_matmul_f32(const float* dout, const int32_t* ar
 extern "C" int act_group_max_bwd_matmul_live_f32(const float* dout, const int32_t* arg, int G, int n, int C, const float* w, int ldw, int N, float* dx,
                                                  int lddx, const int32_t* live, act_stream_t stream) {
     if (!dout || !arg || !w || !dx) return ACT_E_NULLPTR;
-    if (G < 0 || !pool_geom_ok(n, C) || N <= 0 || (N != 256 && N != 512 && N != 1024) || ldw < N || lddx < N || (ldw & 3) || (lddx & 3) ||
+    if (G < 0 || !pool_geom_ok(n, C) || N <= 0 || (N != 128 && N != 256 && N != 512 && N != 1024) || ldw < N || lddx < N || (ldw & 3) || (lddx & 3) ||
         ((uintptr_t)w & 15) || ((uintptr_t)dx & 15))
         return ACT_E_BADARG;
+    if (N == 128 && n % 8) return ACT_E_BADARG;                                  // (128 columns: the float4 walk only, eight parts of 32 threads)
     if (G == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     // compulsory bytes: dx [G n, N] written, dout + arg [G, C] of the live groups read, w [C, N] read once (dead groups: their dx rows are zero-filled)
@@ -393,7 +395,8 @@ extern "C" int act_group_max_bwd_matmul_live_f32(const float* dout, const int32_
     const size_t lds = (size_t)C * 8 + (size_t)(n + 1 + 4) * 4 + (size_t)C * 2;
     const int parts = 1024 / N, skip = pool_live_on() ? 1 : 0;
     if (n % parts == 0) {
-        if (N == 256)      hipLaunchKernelGGL(pool_bwd_dx4_kernel<4>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);
+        if (N == 128)      hipLaunchKernelGGL(pool_bwd_dx4_kernel<8>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);
+        else if (N == 256) hipLaunchKernelGGL(pool_bwd_dx4_kernel<4>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);
         else if (N == 512) hipLaunchKernelGGL(pool_bwd_dx4_kernel<2>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);
         else               hipLaunchKernelGGL(pool_bwd_dx4_kernel<1>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);
     } else if (N == 256)   hipLaunchKernelGGL(pool_bwd_dx_kernel<1>, dim3(G), dim3(256), lds, s, dout, arg, w, ldw, n, C, dx, lddx, skip, live);   // (n = 1, 2)

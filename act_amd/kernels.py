@@ -384,8 +384,14 @@ def gemm_config(ak, bk, M, N, K, device, a=None, b=None, ws=None, publish=False)
             if torch.cuda.is_current_stream_capturing():
                 return None
             if a is None:
+                # operands of the timing only: the device generator is put back afterwards, so that a first-use timing does not move the caller's random
+                # stream (the masks, dropout and noise of the step would differ between a build whose shapes are all listed and one that times a new one)
+                idx = device.index if device.index is not None else (torch.cuda.current_device() if torch.cuda.is_available() else None)
+                rng = torch.cuda.get_rng_state(idx) if torch.cuda.is_available() else None
                 a = torch.randn((M, K) if ak else (K, M), dtype=torch.float32, device=device)
                 b = torch.randn((N, K) if bk else (K, N), dtype=torch.float32, device=device)
+                if rng is not None:
+                    torch.cuda.set_rng_state(rng, idx)
             cfg = _NEW_TUNED[key[:5]] = first_use_config(a, b, ak, bk, M, N, K, ws if ws is not None else workspace(device))
             publish = True
         _GEMM_CACHE[key] = cfg
