@@ -36,8 +36,9 @@ def _fit(name):
 
 
 # ---- 1. hinge ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,K", [(257, 5), (1000, 40), (130, 64)])
-def test_hinge_bits_sums_and_determinism(N, K):
+def check_hinge(N, K):
+    """R bit-equal to the float32 numpy expression (margins of exactly 1, an inactive column, one ulp either side of the margin), the float64 sums
+    within N 2^-52 of math.fsum, two calls bit-identical; shared with tests/test_gpu_svm_edges.py"""
     from act_amd import kernels as Kn
     r = np.random.default_rng(N + K)
     classes = np.sort(r.choice(100, K, replace=False)).astype(np.int64)
@@ -63,6 +64,11 @@ def test_hinge_bits_sums_and_determinism(N, K):
         print(f"hinge N={N} K={K} class {c}: |sum - fsum| / fsum = {abs(s[c] - exact) / max(exact, 1e-300):.2e} (bar {N * 2.0 ** -52:.2e})")
         assert abs(s[c] - exact) <= N * 2.0 ** -52 * exact
     assert torch.equal(Rd.view(torch.int32), Rd2.view(torch.int32)) and torch.equal(sums.view(torch.int64), sums2.view(torch.int64))
+
+
+@pytest.mark.parametrize("N,K", [(257, 5), (1000, 40), (130, 64)])
+def test_hinge_bits_sums_and_determinism(N, K):
+    check_hinge(N, K)
 
 
 # ---- 2. the two products -------------------------------------------------------------------------------------------------------------------
@@ -111,12 +117,10 @@ def test_scores_forward_bound_and_mask(name, N, D, K):
 
 
 # ---- 3. the solver -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(R.CASES))
-def test_solver_against_liblinear(name):
+def check_solver(name, clf):
     """Every figure (largest float64 gradient norm over the classes, Newton steps, rows left out by the gap rule) is printed before the
-    assertions; notebook/svm_val.md keeps them."""
+    assertions; notebook/svm_val.md keeps them.  Shared with tests/test_gpu_svm_edges.py"""
     X, y, Xt, _, classes = R.problem(name)
-    clf = _fit(name)
     K = len(classes)
     assert np.array_equal(clf.classes_.cpu().numpy(), classes)
     W, b = clf.coef_.cpu().numpy(), clf.intercept_.cpu().numpy()
@@ -142,6 +146,11 @@ def test_solver_against_liblinear(name):
     assert (f <= fd + 0.5 * g * g).all()
     assert (~keep).sum() <= 0.01 * R.N_TEST                                # a solver that stops early fails here instead of hiding
     assert np.array_equal(pred[keep], classes[so.argmax(1)][keep])
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_solver_against_liblinear(name):
+    check_solver(name, _fit(name))
 
 
 # ---- 4. classes_ with a skipped id -----------------------------------------------------------------------------------------------------------

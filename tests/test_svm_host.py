@@ -30,6 +30,16 @@ def test_float64_objective_is_liblinears(name):
         assert dist <= gm + go[c]
 
 
+@pytest.mark.parametrize("name", list(R.WIDE_CASES))
+def test_wide_cases_leave_room_for_the_gap_rule(name):
+    """a property of the wide problems and their oracle, checked before any device is used: a device result whose gradient norm is under
+    G_ALLOW_MIN (eight times the largest ending norm notebook/svm_val.md records) loses at most 1 % of the test rows to the gap rule"""
+    assert name not in R.CASES and len(R.problem(name)[4]) == R.WIDE_CASES[name][2]      # every id occurs in the draw
+    ga = R.g_allow(name)
+    print(f"{name}: g_allow = {ga:.3e} (bar {R.G_ALLOW_MIN:.0e})")
+    assert ga >= R.G_ALLOW_MIN
+
+
 def test_fit_refuses_cpu_tensors():
     from act_amd._C import ActHipError
     from act_amd.utils.svm import LinearSVC
