@@ -180,6 +180,7 @@ _TABLE = {
     "act_gemm_tune_set": [_i] * 7,
     "act_gemm_tune_get": [_i] * 5 + [_P(_i), _P(_i)],
     "act_gemm_tune_clear": [],
+    "act_gemm_tile_info": [_i] + [_P(_i)] * 4,
     "act_scale_rows_f32": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "act_bn_eval_affine_f32": [_vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
     # composite entry points (csrc/composite.hip)

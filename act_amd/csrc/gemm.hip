@@ -427,6 +427,63 @@ static void launch_variant(const GemmParams& p, int ak, int bk, bool vec, bool f
 #undef LV
 #undef L
 }
+// the kernels of this file: any shape, any layout; pipe: the 3-stage loop where the shape is full, else the plain kernels
+static bool launch_mfma32(const GemmParams& p, int bm, int bn, int ak, int bk, bool vec, bool full, bool pipe, dim3 grid, hipStream_t s) {
+    if (bm == 128 && bn == 128)     launch_variant<128, 128, 16>(p, ak, bk, vec, full, pipe, grid, s);
+    else if (bm == 128 && bn == 64) launch_variant<128, 64, 16>(p, ak, bk, vec, full, pipe, grid, s);
+    else if (bm == 64 && bn == 64)  launch_variant<64, 64, 16>(p, ak, bk, vec, full, pipe, grid, s);
+    else return false;
+    return true;
+}
+
+// ---- the tile table: every explicit launch configuration of act_sgemm_ex_f32 (id 0, the built-in cost model, is no row).  This is the one place
+// that says which ids exist, what tile and kernel family each names, which layouts it takes and what it needs of the shape; the dispatcher,
+// act_gemm_tune_set and act_gemm_tile_info (-> kernels.stable_candidates) all read it.  Dropping an id = dropping its row. ------------------------
+enum GemmFamily {
+    FAM_MFMA32,        // sgemm_kernel (this file): 32x32x2 MFMA, every shape
+    FAM_MFMA32_PIPE,   // ... with the 3-stage software-pipelined loop when the shape is full, else exactly the kernels of FAM_MFMA32
+    FAM_MFMA16,        // sgemm16_kernel (gemm16.hip): 16x16x4 MFMA
+    FAM_NT16,          // sgemm_nt16_kernel (gemm_nt16.hip): NT, ds_read_b128 operand fragments
+    FAM_NT16_PIPE,     // ... software-pipelined; bit-identical to FAM_NT16
+    FAM_NT32,          // sgemm_nt32_kernel (gemm_nt16.hip): NT, 32-deep K tiles; bit-identical to FAM_NT16
+    FAM_NT_ASM,        // sgemm_nt_asm_kernel (gemm_nt_asm.hip): NT, hand-scheduled loop; bit-identical to FAM_NT16
+    FAM_Q16,           // sgemm_q16_kernel (gemm_q16.hip): NN / TN quad fragments
+    FAM_Q_ASM,         // sgemm_q_asm_kernel (gemm_q_asm.hip): NN / TN, hand-scheduled loop; bit-identical to FAM_Q16
+};
+struct GemmTile { int id; GemmFamily fam; int bm, bn, layouts, need; };
+namespace {
+constexpr int L_ALL = ACT_GEMM_LAYOUT_TN | ACT_GEMM_LAYOUT_TT | ACT_GEMM_LAYOUT_NN | ACT_GEMM_LAYOUT_NT;
+constexpr int L_NT = ACT_GEMM_LAYOUT_NT, L_NN = ACT_GEMM_LAYOUT_NN, L_NN_TN = ACT_GEMM_LAYOUT_NN | ACT_GEMM_LAYOUT_TN;
+constexpr int N_ANY = ACT_GEMM_NEED_ANY, N_MTAIL = ACT_GEMM_NEED_FULL_OR_MTAIL, N_FULL = ACT_GEMM_NEED_FULL;
+constexpr int N_MTAIL_OFF = ACT_GEMM_NEED_FULL_OR_MTAIL | ACT_GEMM_NEED_OFFSET32;
+const GemmTile g_tiles[] = {
+    { 1, FAM_MFMA32,      128, 128, L_ALL,   N_ANY},       { 2, FAM_MFMA32,      128,  64, L_ALL,   N_ANY},       { 3, FAM_MFMA32,       64,  64, L_ALL,   N_ANY},
+    { 4, FAM_MFMA32_PIPE, 128, 128, L_ALL,   N_ANY},       { 5, FAM_MFMA32_PIPE, 128,  64, L_ALL,   N_ANY},       { 6, FAM_MFMA32_PIPE,  64,  64, L_ALL,   N_ANY},
+    { 7, FAM_MFMA16,      128, 128, L_ALL,   N_MTAIL},     { 8, FAM_MFMA16,      128,  64, L_ALL,   N_MTAIL},     { 9, FAM_MFMA16,       64,  64, L_ALL,   N_MTAIL},
+    {10, FAM_NT16,        128, 128, L_NT,    N_MTAIL},     {11, FAM_NT16,        128,  64, L_NT,    N_MTAIL},     {12, FAM_NT16,         64,  64, L_NT,    N_MTAIL},
+    {13, FAM_Q16,         128, 128, L_NN_TN, N_MTAIL},     {14, FAM_Q16,          64, 128, L_NN,    N_MTAIL},     {15, FAM_Q16,          64,  64, L_NN,    N_MTAIL},
+    {16, FAM_Q16,         128,  64, L_NN,    N_MTAIL},
+    {17, FAM_NT16_PIPE,   128, 128, L_NT,    N_FULL},      {18, FAM_NT16_PIPE,   128,  64, L_NT,    N_FULL},
+    {20, FAM_NT32,        128, 128, L_NT,    N_FULL},      {21, FAM_NT32,        128,  64, L_NT,    N_FULL},
+    {30, FAM_NT_ASM,      128, 128, L_NT,    N_MTAIL_OFF}, {31, FAM_NT_ASM,      128,  64, L_NT,    N_MTAIL_OFF}, {32, FAM_NT_ASM,       64,  64, L_NT,    N_MTAIL_OFF},
+    {33, FAM_Q_ASM,       128, 128, L_NN_TN, N_MTAIL_OFF}, {34, FAM_Q_ASM,        64, 128, L_NN,    N_MTAIL_OFF}, {35, FAM_Q_ASM,        64,  64, L_NN,    N_MTAIL_OFF},
+    {36, FAM_Q_ASM,       128,  64, L_NN,    N_MTAIL_OFF},
+};
+const GemmTile* gemm_tile_find(int id) {
+    for (const GemmTile& t : g_tiles) if (t.id == id) return &t;
+    return nullptr;
+}
+inline int gemm_layout_bit(int a_kmajor, int b_kmajor) { return 1 << ((a_kmajor ? 2 : 0) + (b_kmajor ? 1 : 0)); }
+}  // namespace
+extern "C" int act_gemm_tile_info(int tile, int* bm, int* bn, int* layouts, int* need) {
+    const GemmTile* t = gemm_tile_find(tile);
+    if (!t) return 1;
+    if (bm) *bm = t->bm;
+    if (bn) *bn = t->bn;
+    if (layouts) *layouts = t->layouts;
+    if (need) *need = t->need;
+    return 0;
+}
 
 // ---- launch-configuration table: (a_kmajor, b_kmajor, M, N, K) -> (tile id, split-K), filled by the host-side autotuner ----------
 #include <mutex>
@@ -441,7 +498,7 @@ std::mutex g_tune_mu;
 std::unordered_map<TuneKey, std::pair<int, int>, TuneHash> g_tune;
 }  // namespace
 extern "C" int act_gemm_tune_set(int ak, int bk, int M, int N, int K, int tile, int splits) {
-    if (tile < 0 || (tile > 21 && (tile < 30 || tile > 36)) || splits < 0) return ACT_E_BADARG;
+    if ((tile != 0 && !gemm_tile_find(tile)) || splits < 0) return ACT_E_BADARG;
     std::lock_guard<std::mutex> g(g_tune_mu);
     g_tune[TuneKey{ak != 0, bk != 0, M, N, K}] = {tile, splits};
     return 0;
@@ -456,12 +513,88 @@ extern "C" int act_gemm_tune_get(int ak, int bk, int M, int N, int K, int* tile,
 }
 extern "C" int act_gemm_tune_clear(void) { std::lock_guard<std::mutex> g(g_tune_mu); g_tune.clear(); return 0; }
 
+// tile rasterisation: ACT_GEMM_GROUP_M tile rows are swept column by column (GemmParams::group_m)
+static int gemm_group_m() {
+    static const int v = [] { const char* e = getenv("ACT_GEMM_GROUP_M"); return e ? atoi(e) : 8; }();
+    return v;
+}
+
+// The skinny weight gradients on the streaming kernels above (TN, min(M, N) <= 8).  GEMM_NOT_TAKEN: no K partition fits the workspace, nothing
+// was launched and the tiled kernels take the product; anything else is the return code of the whole product.
+constexpr int GEMM_NOT_TAKEN = 1 << 30;
+static int gemm_tn_skinny(const GemmParams& p, float* workspace, size_t workspace_bytes, hipStream_t s) {
+    const int M = p.M, N = p.N, K = p.K;
+    // wide operand as float4 rows (round 4): W % 4 == 0, 16 .. 64 threads per row, the rest of the workgroup are k-lanes
+    static const bool skinny4 = [] { const char* e = getenv("ACT_GEMM_SKINNY4"); return !(e && e[0] == '0'); }();
+    const bool small_n = N <= 8;
+    const float* wide = small_n ? p.A : p.B; const float* skin = small_n ? p.B : p.A;
+    const int ldw_ = small_n ? p.lda : p.ldb, lds_ = small_n ? p.ldb : p.lda, W = small_n ? M : N, ns = small_n ? N : M;
+    if (skinny4 && W % 4 == 0 && W >= 64 && (ldw_ & 3) == 0 && (reinterpret_cast<uintptr_t>(wide) & 15) == 0) {
+        int tpr_shift = 6; while ((4 << tpr_shift) > W && tpr_shift > 4) --tpr_shift;       // 64 / 32 / 16 threads per row
+        const int tpr = 1 << tpr_shift, KL = 256 >> tpr_shift, gx = (W + 4 * tpr - 1) / (4 * tpr);
+        int nparts = (1024 + gx - 1) / gx;                                                  // ~4 workgroups per CU
+        nparts = min(nparts, max(1, K / (8 * KL)));                                         // at least 8 rows per k-lane
+        nparts = min(nparts, 1024);
+        const size_t fit = workspace_bytes / ((size_t)M * N * sizeof(float));
+        if ((size_t)nparts > fit) nparts = (int)fit;
+        if (nparts >= 1) {
+            const int rpp = ((K + nparts - 1) / nparts + KL - 1) / KL * KL;
+            nparts = (K + rpp - 1) / rpp;
+            const size_t ldsb = (size_t)(KL - 1) * tpr * 32 * sizeof(float);
+            if (small_n) hipLaunchKernelGGL(sgemm_tn_skinny4_kernel<true>, dim3(gx, nparts), dim3(256), ldsb, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N,
+                                            tpr_shift, workspace);
+            else         hipLaunchKernelGGL(sgemm_tn_skinny4_kernel<false>, dim3(gx, nparts), dim3(256), ldsb, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N,
+                                            tpr_shift, workspace);
+            ACT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)(((long long)M * N + 63) / 64)), dim3(256), 0, s, workspace, nparts, M, N, p.C, p.ldc, p.epi);
+            ACT_LAUNCH_CHECK();
+            return 0;
+        }
+    }
+    int nparts = K / 1024; if (nparts > 256) nparts = 256; if (nparts < 1) nparts = 1;
+    const int rpp = ((K + nparts - 1) / nparts + 3) / 4 * 4;
+    nparts = (K + rpp - 1) / rpp;
+    if ((size_t)nparts * M * N * sizeof(float) > workspace_bytes) return GEMM_NOT_TAKEN;
+    if (small_n) hipLaunchKernelGGL(sgemm_tn_skinny_kernel<true>, dim3((M + 63) / 64, nparts), dim3(256), 0, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N, workspace);
+    else         hipLaunchKernelGGL(sgemm_tn_skinny_kernel<false>, dim3((N + 63) / 64, nparts), dim3(256), 0, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N, workspace);
+    ACT_LAUNCH_CHECK();
+    launch_splitk_reduce(workspace, nparts, M, N, p.C, p.ldc, p.epi, s);
+    ACT_LAUNCH_CHECK();
+    return 0;
+}
+
+// Tile shape + split-K of id 0 from a small cost model: every workgroup keeps one wave per SIMD busy, so the time of a launch
+// is ~ ceil(workgroups / 256 CUs) x (work per workgroup) / (efficiency of that tile shape); split-K (deterministic
+// two-pass) is considered when the tile grid alone cannot fill the chip (weight gradients: K = tokens) and there is a workspace for it.
+struct GemmModelChoice { int bm, bn, splits; };
+static GemmModelChoice gemm_cost_model(int M, int N, int K, bool have_workspace, size_t workspace_bytes) {
+    struct Cand { int bm, bn; double eff; };
+    const Cand cands[3] = {{128, 128, 1.00}, {128, 64, 0.93}, {64, 64, 0.82}};
+    GemmModelChoice c0{128, 128, 1}; double best = 1e300;
+    for (const Cand& c : cands) {
+        const long long nb = (long long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
+        int maxs = 1;
+        if (have_workspace && K >= 1024) { maxs = K / 512; if (maxs > 32) maxs = 32; if (maxs < 1) maxs = 1; }
+        for (int sp = 1; sp <= maxs; sp = (sp < 4 ? sp + 1 : sp * 2)) {
+            if (sp > 1 && (size_t)sp * M * N * sizeof(float) > workspace_bytes) break;
+            const double rounds = (double)((nb * sp + 255) / 256);
+            double cost = rounds * ((double)c.bm * c.bn * ((K + sp - 1) / sp + 32)) / c.eff;
+            if (sp > 1) cost += 2.0 * (double)M * N * sp / 256.0 * 8.0;      // partial write + reduce traffic (rough)
+            if (cost < best) { best = cost; c0 = {c.bm, c.bn, sp}; }
+            if (nb * sp >= 1024) break;
+        }
+    }
+    return c0;
+}
 
 extern "C" int act_sgemm_ex_f32(int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                                 float* C, int ldc, const act_gemm_epilogue_t* epi_in, float* workspace, size_t workspace_bytes,
                                 int tile, int force_splits, act_stream_t stream) {
     if (!A || !B || !C) return ACT_E_NULLPTR;
     if (M < 0 || N < 0 || K < 0) return ACT_E_BADARG;
+    // 1. the id: 0 = the cost model, else a row of the tile table
+    const GemmTile* row = tile == 0 ? nullptr : gemm_tile_find(tile);
+    if (tile != 0 && !row) return ACT_E_BADARG;
     if (M == 0 || N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     GemmParams p{};
@@ -475,110 +608,26 @@ extern "C" int act_sgemm_ex_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
     const int kid = (a_kmajor && b_kmajor) ? KID_GEMM_NT : (a_kmajor ? KID_GEMM_NN : KID_GEMM_TN);
     ActProfScope ps(kid, s, 2.0 * M * N * (double)K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
 
-    if (!a_kmajor && !b_kmajor && tile == 0 && (M <= 8 || N <= 8) && K >= 2048 && workspace) {
-        // wide operand as float4 rows (round 4): W % 4 == 0, 16 .. 64 threads per row, the rest of the workgroup are k-lanes
-        static const bool skinny4 = [] { const char* e = getenv("ACT_GEMM_SKINNY4"); return !(e && e[0] == '0'); }();
-        const bool small_n = N <= 8;
-        const float* wide = small_n ? A : B; const float* skin = small_n ? B : A;
-        const int ldw_ = small_n ? lda : ldb, lds_ = small_n ? ldb : lda, W = small_n ? M : N, ns = small_n ? N : M;
-        if (skinny4 && W % 4 == 0 && W >= 64 && (ldw_ & 3) == 0 && (reinterpret_cast<uintptr_t>(wide) & 15) == 0) {
-            int tpr_shift = 6; while ((4 << tpr_shift) > W && tpr_shift > 4) --tpr_shift;       // 64 / 32 / 16 threads per row
-            const int tpr = 1 << tpr_shift, KL = 256 >> tpr_shift, gx = (W + 4 * tpr - 1) / (4 * tpr);
-            int nparts = (1024 + gx - 1) / gx;                                                  // ~4 workgroups per CU
-            nparts = min(nparts, max(1, K / (8 * KL)));                                         // at least 8 rows per k-lane
-            nparts = min(nparts, 1024);
-            const size_t fit = workspace_bytes / ((size_t)M * N * sizeof(float));
-            if ((size_t)nparts > fit) nparts = (int)fit;
-            if (nparts >= 1) {
-                const int rpp = ((K + nparts - 1) / nparts + KL - 1) / KL * KL;
-                nparts = (K + rpp - 1) / rpp;
-                const size_t ldsb = (size_t)(KL - 1) * tpr * 32 * sizeof(float);
-                if (small_n) hipLaunchKernelGGL(sgemm_tn_skinny4_kernel<true>, dim3(gx, nparts), dim3(256), ldsb, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N,
-                                                tpr_shift, workspace);
-                else         hipLaunchKernelGGL(sgemm_tn_skinny4_kernel<false>, dim3(gx, nparts), dim3(256), ldsb, s, wide, ldw_, W, skin, lds_, ns, K, rpp, M, N,
-                                                tpr_shift, workspace);
-                ACT_LAUNCH_CHECK();
-                hipLaunchKernelGGL(skinny_reduce_kernel, dim3((unsigned)(((long long)M * N + 63) / 64)), dim3(256), 0, s, workspace, nparts, M, N, C, ldc, p.epi);
-                ACT_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        int nparts = K / 1024; if (nparts > 256) nparts = 256; if (nparts < 1) nparts = 1;
-        const int rpp = ((K + nparts - 1) / nparts + 3) / 4 * 4;
-        nparts = (K + rpp - 1) / rpp;
-        if ((size_t)nparts * M * N * sizeof(float) <= workspace_bytes) {
-            if (N <= 8) hipLaunchKernelGGL(sgemm_tn_skinny_kernel<true>, dim3((M + 63) / 64, nparts), dim3(256), 0, s, A, lda, M, B, ldb, N, K,
-                                           rpp, M, N, workspace);
-            else        hipLaunchKernelGGL(sgemm_tn_skinny_kernel<false>, dim3((N + 63) / 64, nparts), dim3(256), 0, s, B, ldb, N, A, lda, M, K,
-                                           rpp, M, N, workspace);
-            ACT_LAUNCH_CHECK();
-            launch_splitk_reduce(workspace, nparts, M, N, C, ldc, p.epi, s);
-            ACT_LAUNCH_CHECK();
-            return 0;
-        }
+    if (!row && !a_kmajor && !b_kmajor && (M <= 8 || N <= 8) && K >= 2048 && workspace) {
+        const int rc = gemm_tn_skinny(p, workspace, workspace_bytes, s);
+        if (rc != GEMM_NOT_TAKEN) return rc;
     }
-    // vector path: every float4 is fully in range or fully out, and 16-byte aligned
-    const bool vec = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && (lda & 3) == 0 &&
-                     (ldb & 3) == 0 && (a_kmajor ? (K & 3) == 0 : (M & 3) == 0) && (b_kmajor ? (K & 3) == 0 : (N & 3) == 0);
-
-    // Tile shape + split-K from a small cost model: every workgroup keeps one wave per SIMD busy, so the time of a launch
-    // is ~ ceil(workgroups / 256 CUs) x (work per workgroup) / (efficiency of that tile shape); split-K (deterministic
-    // two-pass) is considered when the tile grid alone cannot fill the chip (weight gradients: K = tokens).
-    struct Cand { int bm, bn; double eff; };
-    const Cand cands[3] = {{128, 128, 1.00}, {128, 64, 0.93}, {64, 64, 0.82}};
-    int BM = 128, BN = 128, splits = 1; double best = 1e300;
-    for (const Cand& c : cands) {
-        const long long nb = (long long)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
-        int maxs = 1;
-        if (workspace && K >= 1024) { maxs = K / 512; if (maxs > 32) maxs = 32; if (maxs < 1) maxs = 1; }
-        for (int sp = 1; sp <= maxs; sp = (sp < 4 ? sp + 1 : sp * 2)) {
-            if (sp > 1 && (size_t)sp * M * N * sizeof(float) > workspace_bytes) break;
-            const double rounds = (double)((nb * sp + 255) / 256);
-            double cost = rounds * ((double)c.bm * c.bn * ((K + sp - 1) / sp + 32)) / c.eff;
-            if (sp > 1) cost += 2.0 * (double)M * N * sp / 256.0 * 8.0;      // partial write + reduce traffic (rough)
-            if (cost < best) { best = cost; BM = c.bm; BN = c.bn; splits = sp; }
-            if (nb * sp >= 1024) break;
-        }
-    }
-    // tiles 33 (128x128), 34 (64x128), 35 (64x64), 36 (128x64): NN / TN kernels with the hand-scheduled main loop (gemm_q_asm_kernel.h); 34..36 NN only;
-    // bit-identical to 13 / 14 / 15 / 16
-    const bool qa = tile >= 33 && tile <= 36;
-    const int qa_tile = tile - 33;
-    if (qa) { if (b_kmajor || (tile != 33 && !a_kmajor)) return ACT_E_BADARG; tile -= 20; }
-    // tiles 30 (128x128), 31 (128x64), 32 (64x64): NT kernels with the hand-scheduled main loop (gemm_nt_asm_kernel.h); bit-identical to 10 / 11 / 12
-    const bool nta = tile >= 30 && tile <= 32;
-    const int nta_tile = tile - 30;
-    if (nta) { if (!(a_kmajor && b_kmajor)) return ACT_E_BADARG; tile -= 29; }
-    // tiles 20 (128x128), 21 (128x64): NT b128 kernels with 32-deep K tiles (full tiles, K per split % 32 == 0); bit-identical to 10 / 11
-    const bool nt32 = tile == 20 || tile == 21;
-    const int nt32_tile = tile - 20;
-    if (nt32) { if (!(a_kmajor && b_kmajor)) return ACT_E_BADARG; tile = tile == 20 ? 1 : 2; }
-    // tiles 17 (128x128), 18 (128x64): NT b128 kernels with the software-pipelined main loop (full tiles, K per split % 32 == 0)
-    const bool nt16p = tile == 17 || tile == 18;
-    const int nt16p_tile = tile == 17 ? 3 : 4;
-    if (nt16p) { if (!(a_kmajor && b_kmajor)) return ACT_E_BADARG; tile = tile == 17 ? 1 : 2; }
-    // tiles 13 (128x128), 14 (64x128), 15 (64x64), 16 (128x64): quad-fragment kernels of the NN / TN layouts (gemm_q16.hip); 14..16 NN only
-    const bool q16 = tile >= 13 && tile <= 16;
-    const int q16_tile = tile - 13;
-    if (q16) { if (b_kmajor || (tile != 13 && !a_kmajor)) return ACT_E_BADARG; tile = tile == 13 ? 1 : 0; }
-    const bool nt16 = tile >= 10 && tile <= 12;         // tiles 10..12 = tiles 1..3, NT-only b128-fragment kernel (gemm_nt16.hip)
-    if (nt16) { if (!(a_kmajor && b_kmajor)) return ACT_E_BADARG; tile -= 9; }
-    const bool mi16 = tile >= 7 && tile <= 9;           // tiles 7..9 = tiles 1..3 on v_mfma_f32_16x16x4_f32 (gemm16.hip)
-    if (mi16) tile -= 6;
-    const bool pipe = tile >= 4 && tile <= 6;           // tiles 4..6 = software-pipelined main loop of tiles 1..3
-    if (pipe) tile -= 3;
-    if (q16) {
-        BM = (q16_tile == 1 || q16_tile == 2) ? 64 : 128; BN = q16_tile >= 2 ? 64 : 128;
+    // 2. the configuration, validated against its row: layout, then room for the partial sums (the cost model ignores `splits` and fits its own)
+    GemmTile cfg{0, FAM_MFMA32, 0, 0, 0, ACT_GEMM_NEED_ANY};
+    int splits;
+    if (row) {
+        cfg = *row;
+        if (!(cfg.layouts & gemm_layout_bit(a_kmajor, b_kmajor))) return ACT_E_BADARG;
         splits = force_splits >= 1 ? force_splits : 1;
         if (splits > 1 && (!workspace || (size_t)splits * M * N * sizeof(float) > workspace_bytes)) return ACT_E_BADARG;
-    } else if (tile >= 1 && tile <= 3) {                // explicit configuration (autotuner)
-        BM = cands[tile - 1].bm; BN = cands[tile - 1].bn;
-        splits = force_splits >= 1 ? force_splits : 1;
-        if (splits > 1 && (!workspace || (size_t)splits * M * N * sizeof(float) > workspace_bytes)) return ACT_E_BADARG;
+    } else {
+        const GemmModelChoice m = gemm_cost_model(M, N, K, workspace != nullptr, workspace_bytes);
+        cfg.bm = m.bm; cfg.bn = m.bn; splits = m.splits;
     }
+    const int BM = cfg.bm, BN = cfg.bn;
+    // 3. tile grid and K ranges
     p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-    static const int group_m_env = [] { const char* e = getenv("ACT_GEMM_GROUP_M"); return e ? atoi(e) : 8; }();
-    p.group_m = group_m_env;
+    p.group_m = gemm_group_m();
     // XCD placement of the NT b128 kernels (experiment knob ACT_GEMM_XCD_ROWS = 1 | 2 | 4: r x 8/r grid of tile blocks; default 0 = row bands)
     static const int xcd_rows_env = [] { const char* e = getenv("ACT_GEMM_XCD_ROWS"); return e ? atoi(e) : 0; }();
     p.xcd_rows = 0;
@@ -586,45 +635,38 @@ extern "C" int act_sgemm_ex_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
         p.xcd_rows = xcd_rows_env;
     static const bool fastdiv_env = [] { const char* e = getenv("ACT_GEMM_FASTDIV"); return !(e && e[0] == '0'); }();   // dev A/B knob (gemm_set_tiling)
     if (fastdiv_env) gemm_set_tiling(p);
-    const long long nt = (long long)p.tiles_m * p.tiles_n;
     int kps = K;
-    if (splits > 1) { kps = (K + splits - 1) / splits; kps = (kps + 31) / 32 * 32; splits = (K + kps - 1) / kps; }
+    if (splits > 1) { const GemmSplit r = gemm_split_ranges(K, splits); kps = r.k_per_split; splits = r.splits; }
     p.k_per_split = kps;
     p.partial = splits > 1 ? workspace : nullptr;
-    if (K == 0) { p.k_per_split = 0; }
+    const dim3 grid((unsigned)((long long)p.tiles_m * p.tiles_n), 1, (unsigned)splits);
 
-    dim3 grid((unsigned)nt, 1, (unsigned)splits);
-    const bool full = vec && (M % BM == 0) && (N % BN == 0) && (K % 32 == 0) && (kps % 32 == 0) && K > 0;
-    // 16x16x4 kernels also take an M tail when A is K-major (rows = tokens): rows clamped on load, guarded on store
-    const bool full_mtail = vec && a_kmajor && (N % BN == 0) && (K % 32 == 0) && (kps % 32 == 0) && K > 0;
-    if (qa) {
-        if (!(full || full_mtail)) return ACT_E_BADARG;
-        if ((long long)(a_kmajor ? BM : 32) * lda * 4 >= (1ll << 31) || (long long)32 * ldb * 4 >= (1ll << 31)) return ACT_E_BADARG;   // 32-bit lane offsets inside a tile
-        if (!launch_sgemm_q_asm(p, qa_tile, a_kmajor, grid, s)) return ACT_E_BADARG;
-    } else if (nta) {
-        if (!(full || full_mtail)) return ACT_E_BADARG;
-        if ((long long)BM * lda * 4 >= (1ll << 31) || (long long)BN * ldb * 4 >= (1ll << 31)) return ACT_E_BADARG;     // 32-bit lane offsets inside a tile
-        launch_sgemm_nt_asm(p, nta_tile, grid, s);
-    } else if (nt32) {
-        if (!full) return ACT_E_BADARG;
-        launch_sgemm_nt32(p, nt32_tile, grid, s);
-    } else if (nt16p) {
-        if (!full) return ACT_E_BADARG;
-        launch_sgemm_nt16(p, nt16p_tile, grid, s);
-    } else if (q16) {
-        if (!(full || full_mtail)) return ACT_E_BADARG;
-        if (!launch_sgemm_q16(p, q16_tile, a_kmajor, b_kmajor, grid, s)) return ACT_E_BADARG;
-    } else if (nt16) {
-        if (!(full || full_mtail)) return ACT_E_BADARG;
-        launch_sgemm_nt16(p, BM == 128 ? (BN == 128 ? 0 : 1) : 2, grid, s);
-    } else if (mi16) {
-        if (!(full || full_mtail)) return ACT_E_BADARG;
-        launch_sgemm16(p, BM == 128 ? (BN == 128 ? 0 : 1) : 2, a_kmajor, b_kmajor, grid, s);
-    } else {
-        if (BM == 128 && BN == 128) launch_variant<128, 128, 16>(p, a_kmajor, b_kmajor, vec, full, pipe, grid, s);
-        else if (BM == 128)         launch_variant<128, 64, 16>(p, a_kmajor, b_kmajor, vec, full, pipe, grid, s);
-        else                        launch_variant<64, 64, 16>(p, a_kmajor, b_kmajor, vec, full, pipe, grid, s);
+    // vector path: every float4 is fully in range or fully out, and 16-byte aligned
+    const bool vec = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && (lda & 3) == 0 &&
+                     (ldb & 3) == 0 && (a_kmajor ? (K & 3) == 0 : (M & 3) == 0) && (b_kmajor ? (K & 3) == 0 : (N & 3) == 0);
+    // full: no loader needs a bounds check.  M tail: as full but for M % BM, with A K-major (rows = tokens): rows clamped on load, guarded on store
+    const bool full_but_m = vec && (N % BN == 0) && (K % 32 == 0) && (kps % 32 == 0) && K > 0;
+    const bool full = full_but_m && (M % BM == 0), full_mtail = full_but_m && a_kmajor;
+    const int need = cfg.need & ~ACT_GEMM_NEED_OFFSET32;
+    if (need == ACT_GEMM_NEED_FULL && !full) return ACT_E_BADARG;
+    if (need == ACT_GEMM_NEED_FULL_OR_MTAIL && !(full || full_mtail)) return ACT_E_BADARG;
+    if ((cfg.need & ACT_GEMM_NEED_OFFSET32) &&                         // hand-scheduled loops: 32-bit lane offsets inside one K tile of an operand
+        ((long long)(a_kmajor ? BM : 32) * lda * 4 >= (1ll << 31) || (long long)(b_kmajor ? BN : 32) * ldb * 4 >= (1ll << 31))) return ACT_E_BADARG;
+
+    // 4. one launch per family
+    bool ok = false;
+    switch (cfg.fam) {
+        case FAM_MFMA32:      ok = launch_mfma32(p, BM, BN, a_kmajor, b_kmajor, vec, full, false, grid, s); break;
+        case FAM_MFMA32_PIPE: ok = launch_mfma32(p, BM, BN, a_kmajor, b_kmajor, vec, full, true, grid, s); break;
+        case FAM_MFMA16:      ok = launch_sgemm16(p, BM, BN, a_kmajor, b_kmajor, grid, s); break;
+        case FAM_NT16:        ok = launch_sgemm_nt16(p, BM, BN, false, grid, s); break;
+        case FAM_NT16_PIPE:   ok = launch_sgemm_nt16(p, BM, BN, true, grid, s); break;
+        case FAM_NT32:        ok = launch_sgemm_nt32(p, BM, BN, grid, s); break;
+        case FAM_NT_ASM:      ok = launch_sgemm_nt_asm(p, BM, BN, grid, s); break;
+        case FAM_Q16:         ok = launch_sgemm_q16(p, BM, BN, a_kmajor, b_kmajor, grid, s); break;
+        case FAM_Q_ASM:       ok = launch_sgemm_q_asm(p, BM, BN, a_kmajor, grid, s); break;
     }
+    if (!ok) return ACT_E_BADARG;
     ACT_LAUNCH_CHECK();
     if (splits > 1) {
         launch_splitk_reduce(workspace, splits, M, N, C, ldc, p.epi, s);
@@ -681,8 +723,7 @@ extern "C" int act_sgemm_fx_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
         if ((fx->group != 32 && fx->group != 64) || ((reinterpret_cast<uintptr_t>(fx->ep_src) | reinterpret_cast<uintptr_t>(fx->ep_arg)) & 15)) return ACT_E_BADARG;
         scatter |= FX_SCATTER_EPI;
     }
-    static const int group_m_env = [] { const char* e = getenv("ACT_GEMM_GROUP_M"); return e ? atoi(e) : 8; }();
-    p.group_m = group_m_env;
+    p.group_m = gemm_group_m();
     const bool aligned = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 && (lda & 3) == 0 && (ldb & 3) == 0;
     if (!aligned) return ACT_E_BADARG;
     if (a_kmajor && b_kmajor) {                                        // forward conv: A-side affine + ReLU, column statistics, group max
@@ -693,13 +734,13 @@ extern "C" int act_sgemm_fx_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
         if (fx->gmax) { if (fx->group != 32 && fx->group != 64) return ACT_E_BADARG; mask |= FX_GROUPMAX; if (!fx->store_c) mask |= FX_NOSTORE; }
         if (mask == 0 || (M % 128) || (K % 16) || (N % 64)) return ACT_E_BADARG;
         if (!(mask & FX_NOSTORE) && !C) return ACT_E_NULLPTR;
-        const int tile = (N % 128 == 0) ? 0 : 1, BN = tile == 0 ? 128 : 64;
+        const int BN = (N % 128 == 0) ? 128 : 64;
         p.tiles_m = M / 128; p.tiles_n = N / BN; p.k_per_split = K; p.partial = nullptr;
         gemm_set_tiling(p);
         ActProfScope ps(KID_GEMM_NT, s, 2.0 * M * N * (double)K, 4.0 * ((double)M * K + (double)N * K + ((mask & FX_NOSTORE) ? 0.0 : (double)M * N)));
         // hand-scheduled main loop when every K tile is 32 deep (ACT_GEMM_FX_ASM=0: the compiler-scheduled kernels, for A/B runs); same bits either way
         const dim3 fgrid((unsigned)(p.tiles_m * p.tiles_n));
-        if (!((g_fx_asm.load() & 1) && !fx->row_groups && launch_sgemm_nt_asm_fx(p, tile, mask, fgrid, s)) && !launch_sgemm_nt16_fx(p, tile, mask, fgrid, s)) return ACT_E_BADARG;
+        if (!((g_fx_asm.load() & 1) && !fx->row_groups && launch_sgemm_nt_asm_fx(p, BN, mask, fgrid, s)) && !launch_sgemm_nt16_fx(p, BN, mask, fgrid, s)) return ACT_E_BADARG;
         ACT_LAUNCH_CHECK();
         return 0;
     }
@@ -711,7 +752,7 @@ extern "C" int act_sgemm_fx_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
         gemm_set_tiling(p);
         ActProfScope ps(KID_GEMM_NN, s, 2.0 * M * N * (double)K, 4.0 * ((double)N * K + (double)M * N));
         const dim3 qgrid((unsigned)(p.tiles_m * p.tiles_n));
-        if (!((g_fx_asm.load() & 2) && launch_sgemm_q_asm_fx(p, 1, scatter, qgrid, s)) && !launch_sgemm_q16_fx(p, 1, scatter, qgrid, s)) return ACT_E_BADARG;
+        if (!((g_fx_asm.load() & 2) && launch_sgemm_q_asm_fx(p, a_kmajor, scatter, qgrid, s)) && !launch_sgemm_q16_fx(p, a_kmajor, scatter, qgrid, s)) return ACT_E_BADARG;
         ACT_LAUNCH_CHECK();
         return 0;
     }
@@ -727,11 +768,11 @@ extern "C" int act_sgemm_fx_f32(int a_kmajor, int b_kmajor, int M, int N, int K,
         int splits = (int)((768 + nt - 1) / nt);                       // ~3 workgroups per CU; K = rows of the batch, a few hundred thousand
         if (splits > 256) splits = 256;                                // (the 256 x 128 gradient of the second conv is 2 tiles: 64 ranges left half the chip idle)
         while (splits > 1 && (K / splits < 256 || (size_t)splits * M * N * sizeof(float) > workspace_bytes)) --splits;
-        int kps = (K + splits - 1) / splits; kps = (kps + 31) / 32 * 32; splits = (K + kps - 1) / kps;
+        const GemmSplit r = gemm_split_ranges(K, splits); splits = r.splits;
         if (splits > 1 && !workspace) return ACT_E_NULLPTR;
-        p.k_per_split = kps; p.partial = splits > 1 ? workspace : nullptr;
+        p.k_per_split = r.k_per_split; p.partial = splits > 1 ? workspace : nullptr;
         ActProfScope ps(KID_GEMM_TN, s, 2.0 * M * N * (double)K, 4.0 * ((scatter ? 0.0 : (double)M * K) + (double)N * K + (double)M * N));
-        if (!launch_sgemm_q16_fx(p, 0, mask, dim3((unsigned)nt, 1, (unsigned)splits), s)) return ACT_E_BADARG;
+        if (!launch_sgemm_q16_fx(p, a_kmajor, mask, dim3((unsigned)nt, 1, (unsigned)splits), s)) return ACT_E_BADARG;
         ACT_LAUNCH_CHECK();
         if (splits > 1) {
             launch_splitk_reduce(workspace, splits, M, N, C, ldc, p.epi, s);

@@ -133,8 +133,10 @@ static void launch16(const GemmParams& p, int ak, int bk, dim3 grid, hipStream_t
     else                 hipLaunchKernelGGL((sgemm16_kernel<BM, BN, false, true>), grid, dim3(256), 0, s, p);
 }
 
-void launch_sgemm16(const GemmParams& p, int tile, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s) {
-    if (tile == 0)      launch16<128, 128>(p, a_kmajor, b_kmajor, grid, s);
-    else if (tile == 1) launch16<128, 64>(p, a_kmajor, b_kmajor, grid, s);
-    else                launch16<64, 64>(p, a_kmajor, b_kmajor, grid, s);
+bool launch_sgemm16(const GemmParams& p, int bm, int bn, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s) {
+    if (bm == 128 && bn == 128)     launch16<128, 128>(p, a_kmajor, b_kmajor, grid, s);
+    else if (bm == 128 && bn == 64) launch16<128, 64>(p, a_kmajor, b_kmajor, grid, s);
+    else if (bm == 64 && bn == 64)  launch16<64, 64>(p, a_kmajor, b_kmajor, grid, s);
+    else return false;
+    return true;
 }

@@ -418,22 +418,32 @@ __device__ __forceinline__ void tile_of_workgroup(const GemmParams& p, int bid, 
     tile_m = xi * bm + lm; tile_n = xj * bn + ln;
 }
 
-// launcher of the 16x16x4-MFMA kernels (gemm16.hip); tile: 0 = 128x128, 1 = 128x64, 2 = 64x64.  FULL shapes only.
-void launch_sgemm16(const GemmParams& p, int tile, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s);
-// NT-only kernels with K-contiguous swizzled LDS image and ds_read_b128 operand fetch (gemm_nt16.hip)
-void launch_sgemm_nt16(const GemmParams& p, int tile, dim3 grid, hipStream_t s);
-// NT kernels with 32-deep K tiles (gemm_nt16.hip): tile 0 = 128x128, 1 = 128x64; full tiles only
-void launch_sgemm_nt32(const GemmParams& p, int tile, dim3 grid, hipStream_t s);
-// NT kernels with the hand-scheduled (asm) main loop, 32-deep K tiles (gemm_nt_asm.hip): tile 0 = 128x128, 1 = 128x64, 2 = 64x64; M tail allowed
-void launch_sgemm_nt_asm(const GemmParams& p, int tile, dim3 grid, hipStream_t s);
-// NN / TN kernels with the hand-scheduled main loop (gemm_q_asm.hip): tile 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 128x64 (1..3 NN only); false = no such kernel
-bool launch_sgemm_q_asm(const GemmParams& p, int tile, int a_kmajor, dim3 grid, hipStream_t s);
+// K ranges of a split-K launch: ceil(K / splits) rounded up to whole 32-deep K tiles, then the number of ranges that are not empty
+struct GemmSplit { int k_per_split, splits; };
+inline GemmSplit gemm_split_ranges(int K, int splits) {
+    if (K <= 0) return {0, 1};
+    const int kps = ((K + splits - 1) / splits + 31) / 32 * 32;
+    return {kps, (K + kps - 1) / kps};
+}
+
+// ---- launchers: one per kernel family, each in the file that instantiates the family.  (bm, bn) = workgroup tile; false = the family has no
+// kernel for this tile / layout / fusion (nothing launched).  What a family needs of the shape is checked by the caller (tile table in gemm.hip).
+// 16x16x4-MFMA kernels (gemm16.hip), all four layouts; an M tail needs A K-major
+bool launch_sgemm16(const GemmParams& p, int bm, int bn, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s);
+// NT-only kernels with K-contiguous swizzled LDS image and ds_read_b128 operand fetch (gemm_nt16.hip); pipelined: software-pipelined loop, full tiles only
+bool launch_sgemm_nt16(const GemmParams& p, int bm, int bn, bool pipelined, dim3 grid, hipStream_t s);
+// NT kernels with 32-deep K tiles (gemm_nt16.hip); full tiles only
+bool launch_sgemm_nt32(const GemmParams& p, int bm, int bn, dim3 grid, hipStream_t s);
+// NT kernels with the hand-scheduled (asm) main loop, 32-deep K tiles (gemm_nt_asm.hip); M tail allowed
+bool launch_sgemm_nt_asm(const GemmParams& p, int bm, int bn, dim3 grid, hipStream_t s);
+// NN / TN kernels with the hand-scheduled main loop (gemm_q_asm.hip); TN: 128x128 only
+bool launch_sgemm_q_asm(const GemmParams& p, int bm, int bn, int a_kmajor, dim3 grid, hipStream_t s);
 bool launch_sgemm_q_asm_fx(const GemmParams& p, int a_kmajor, int fx_mask, dim3 grid, hipStream_t s);    // ... with the epilogue-side max-pool backward term (NN, FX_SCATTER_EPI only)
-// quad-fragment kernels for the NN / TN layouts (gemm_q16.hip): tile 0 = 128x128, 1 = 64x128 (NN only); false = no such kernel
-bool launch_sgemm_q16(const GemmParams& p, int tile, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s);
-// NT kernels with fused producer / consumer passes (gemm_nt16_fx.hip); fx_mask = FX_* bits; tile 0 = 128x128, 1 = 128x64.  false = no such kernel
-bool launch_sgemm_nt16_fx(const GemmParams& p, int tile, int fx_mask, dim3 grid, hipStream_t s);
+// quad-fragment kernels for the NN / TN layouts (gemm_q16.hip); TN: 128x128 only
+bool launch_sgemm_q16(const GemmParams& p, int bm, int bn, int a_kmajor, int b_kmajor, dim3 grid, hipStream_t s);
+// NT kernels with fused producer / consumer passes (gemm_nt16_fx.hip); fx_mask = FX_* bits; 128 x bn tiles
+bool launch_sgemm_nt16_fx(const GemmParams& p, int bn, int fx_mask, dim3 grid, hipStream_t s);
 // ... the same on the hand-scheduled main loop (gemm_nt_asm_fx.hip; additionally K % 32 == 0): bit-identical to launch_sgemm_nt16_fx
-bool launch_sgemm_nt_asm_fx(const GemmParams& p, int tile, int fx_mask, dim3 grid, hipStream_t s);
+bool launch_sgemm_nt_asm_fx(const GemmParams& p, int bn, int fx_mask, dim3 grid, hipStream_t s);
 // quad-fragment 128x128 kernels with fused passes (gemm_q16_fx.hip): TN with FX_AFFINE_B (+ FX_SCATTER_A), NN with FX_SCATTER_A and / or FX_SCATTER_EPI
 bool launch_sgemm_q16_fx(const GemmParams& p, int a_kmajor, int fx_mask, dim3 grid, hipStream_t s);

@@ -263,10 +263,10 @@ extern "C" int act_sgemm_tn_grouped_splits(const act_gemm_tn_problem_t* probs, i
     int best = 1; double best_cost = 1e300;
     const int maxs = K / 128 < 32 ? (K / 128 < 1 ? 1 : K / 128) : 32;
     for (int sp = 1; sp <= maxs; ++sp) {
-        int kps = (K + sp - 1) / sp; kps = (kps + 31) / 32 * 32;
-        if ((K + kps - 1) / kps != sp) continue;                        // this count collapses to a smaller one after rounding the ranges
+        const GemmSplit r = gemm_split_ranges(K, sp);
+        if (r.splits != sp) continue;                        // this count collapses to a smaller one after rounding the ranges
         const double rounds = (double)((tiles * sp + 511) / 512);
-        const double cost = rounds * (kps + 64.0);
+        const double cost = rounds * (r.k_per_split + 64.0);
         if (cost < best_cost) { best_cost = cost; best = sp; }
     }
     return best;
@@ -280,8 +280,8 @@ extern "C" int act_sgemm_tn_grouped_f32(const act_gemm_tn_problem_t* probs, int 
     GroupedParams g{};
     g.nprob = nprob; g.K = K;
     if (splits <= 0) splits = act_sgemm_tn_grouped_splits(probs, nprob, K);
-    int kps = (K + splits - 1) / splits; kps = (kps + 31) / 32 * 32; splits = (K + kps - 1) / kps;
-    g.k_per_split = kps; g.splits = splits;
+    const GemmSplit r = gemm_split_ranges(K, splits); splits = r.splits;
+    g.k_per_split = r.k_per_split; g.splits = splits;
     long long off = 0; int tiles = 0; double flops = 0.0, bytes = 0.0;
     long long total4 = 0, total_bias = 0;
     for (int i = 0; i < nprob; ++i) {

@@ -109,39 +109,43 @@ __global__ __launch_bounds__(256, BM * BN <= 128 * 64 ? 3 : 2) void sgemm_nt32_k
     const int wu = __builtin_amdgcn_readfirstlane(wave);
     epilogue_rows<-1, TM, TN, false, false, true>(p, acc, m0 + (wu >> 1) * (BM / 2), n0 + (wu & 1) * (BN / 2), ml, kl);
 }
-void launch_sgemm_nt32(const GemmParams& p, int tile, dim3 grid, hipStream_t s) {
-    if (tile == 0) hipLaunchKernelGGL((sgemm_nt32_kernel<128, 128>), grid, dim3(256), 0, s, p);
-    else           hipLaunchKernelGGL((sgemm_nt32_kernel<128, 64>), grid, dim3(256), 0, s, p);
+bool launch_sgemm_nt32(const GemmParams& p, int bm, int bn, dim3 grid, hipStream_t s) {
+    if (bm == 128 && bn == 128)     hipLaunchKernelGGL((sgemm_nt32_kernel<128, 128>), grid, dim3(256), 0, s, p);
+    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((sgemm_nt32_kernel<128, 64>), grid, dim3(256), 0, s, p);
+    else return false;
+    return true;
 }
 
-// tile: 0 = 128x128, 1 = 64x128, 2 = 64x64, 3 = 128x64 (1..3 NN only: A K-contiguous; 2, 3: 4 x 1 waves).  false: no such kernel.
-void launch_sgemm_nt16(const GemmParams& p, int tile, dim3 grid, hipStream_t s) {
-    if (tile == 3) { hipLaunchKernelGGL((sgemm_nt16_kernel<128, 128, false, 0, true>), grid, dim3(256), 0, s, p); return; }   // pipelined loop: full tiles only
-    if (tile == 4) { hipLaunchKernelGGL((sgemm_nt16_kernel<128, 64, false, 0, true>), grid, dim3(256), 0, s, p); return; }
-    const int bm = tile == 2 ? 64 : 128;
-    if (p.M % bm != 0) {
-        if (tile == 0)      hipLaunchKernelGGL((sgemm_nt16_kernel<128, 128, true>), grid, dim3(256), 0, s, p);
-        else if (tile == 1) hipLaunchKernelGGL((sgemm_nt16_kernel<128, 64, true>), grid, dim3(256), 0, s, p);
-        else                hipLaunchKernelGGL((sgemm_nt16_kernel<64, 64, true>), grid, dim3(256), 0, s, p);
-        return;
+// the three tiles of this file: X(BM, BN) for the one asked for
+#define NT16_TILE(X) \
+    if (bm == 128 && bn == 128)     { X(128, 128) } \
+    else if (bm == 128 && bn == 64) { X(128, 64) } \
+    else if (bm == 64 && bn == 64)  { X(64, 64) } \
+    else return false;
+
+bool launch_sgemm_nt16(const GemmParams& p, int bm, int bn, bool pipelined, dim3 grid, hipStream_t s) {
+    if (pipelined) {                                                  // full tiles only; no 64 x 64 kernel
+        if (bm == 128 && bn == 128)     hipLaunchKernelGGL((sgemm_nt16_kernel<128, 128, false, 0, true>), grid, dim3(256), 0, s, p);
+        else if (bm == 128 && bn == 64) hipLaunchKernelGGL((sgemm_nt16_kernel<128, 64, false, 0, true>), grid, dim3(256), 0, s, p);
+        else return false;
+        return true;
     }
     static const int spec = [] { const char* e = getenv("ACT_GEMM_EPI_SPEC"); return e ? atoi(e) : 1; }();
-    if (!spec) {
-        if (tile == 0)      hipLaunchKernelGGL((sgemm_nt16_kernel<128, 128>), grid, dim3(256), 0, s, p);
-        else if (tile == 1) hipLaunchKernelGGL((sgemm_nt16_kernel<128, 64>), grid, dim3(256), 0, s, p);
-        else                hipLaunchKernelGGL((sgemm_nt16_kernel<64, 64>), grid, dim3(256), 0, s, p);
-        return;
-    }
+#define NT16_MTAIL(BM_, BN_) hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_, true>), grid, dim3(256), 0, s, p);
+#define NT16_ANY(BM_, BN_) hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_>), grid, dim3(256), 0, s, p);
 #define NT16_ACT(BM_, BN_) \
     switch (p.epi.act) { \
         case ACT_EPI_NONE: hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_, false, 0, false, ACT_EPI_NONE>), grid, dim3(256), 0, s, p); break; \
         case ACT_EPI_GELU: hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_, false, 0, false, ACT_EPI_GELU>), grid, dim3(256), 0, s, p); break; \
         case ACT_EPI_RELU: hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_, false, 0, false, ACT_EPI_RELU>), grid, dim3(256), 0, s, p); break; \
-        default:           hipLaunchKernelGGL((sgemm_nt16_kernel<BM_, BN_>), grid, dim3(256), 0, s, p); break; \
+        default:           NT16_ANY(BM_, BN_) break; \
     }
-    if (tile == 0)      { NT16_ACT(128, 128) }
-    else if (tile == 1) { NT16_ACT(128, 64) }
-    else                { NT16_ACT(64, 64) }
+    if (p.M % bm != 0) { NT16_TILE(NT16_MTAIL) }
+    else if (!spec)    { NT16_TILE(NT16_ANY) }
+    else               { NT16_TILE(NT16_ACT) }
+    return true;
 #undef NT16_ACT
+#undef NT16_ANY
+#undef NT16_MTAIL
 }
-
+#undef NT16_TILE

@@ -247,6 +247,19 @@ def stable_split(M, N, K, ws_bytes):
     return s
 
 
+_TILE_BN = {}
+
+
+def tile_bn(tile):
+    """BN of a tile id, from the library's tile table (csrc/gemm.hip through act_gemm_tile_info); read once"""
+    if not _TILE_BN:
+        bn = ctypes.c_int()
+        for t in range(1, 64):
+            if lib.act_gemm_tile_info(t, None, ctypes.byref(bn), None, None) == 0:
+                _TILE_BN[t] = bn.value
+    return _TILE_BN[tile]
+
+
 def stable_candidates(a, b, ak, bk, M, N, K, ws):
     """(tile id, split-K) configurations of ONE tile family at ONE deterministic split-K: every candidate adds the same fp32 products in the same order
     per output element (tests/test_gpu_dense.py: tiles 30 / 31 / 32 / 10 / 11 / 12 / 20 / 21 for NT, the quad-fragment tiles 13..16 for NN), so the
@@ -256,10 +269,9 @@ def stable_candidates(a, b, ak, bk, M, N, K, ws):
         return []
     sp = stable_split(M, N, K, ws.numel() * 4)             # (the library rounds the K range up to a multiple of 32 and recounts the ranges: same for every tile)
     if ak and bk:                                             # NT: hand-scheduled loop first, compiler loop as the alternative; M tails allowed
-        fam = [(30, 128), (31, 64), (32, 64), (10, 128), (11, 64), (12, 64)]
-        return [(t, sp) for t, bn in fam if N % bn == 0]
-    if ak and not bk:                                         # NN: quad-fragment tiles (13: 128x128, 14: 64x128, 16: 128x64, 15: 64x64)
-        return [(t, sp) for t, bn in ((33, 128), (34, 128), (36, 64), (35, 64), (13, 128), (14, 128), (16, 64), (15, 64)) if N % bn == 0]
+        return [(t, sp) for t in (30, 31, 32, 10, 11, 12) if N % tile_bn(t) == 0]
+    if ak and not bk:                                         # NN: quad-fragment tiles, hand-scheduled loop first
+        return [(t, sp) for t in (33, 34, 36, 35, 13, 14, 16, 15) if N % tile_bn(t) == 0]
     if not ak and not bk and M % 128 == 0 and N % 128 == 0:   # TN: the quad-fragment tile, hand-scheduled or compiler-scheduled
         return [(33, sp), (13, sp)]
     return []

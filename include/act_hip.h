@@ -152,12 +152,22 @@ typedef struct {
 int act_sgemm_f32(int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                   float* C, int ldc, const act_gemm_epilogue_t* epilogue, float* workspace, size_t workspace_bytes,
                   act_stream_t stream);
-/* same, with an explicit launch configuration: tile 1 = 128x128, 2 = 128x64, 3 = 64x64 workgroup tile, 4..6 = the same tiles with the
- * software-pipelined (3-stage LDS, mid-tile barrier) main loop, 7..9 = the same tiles on v_mfma_f32_16x16x4_f32,
- * 10..12 = NT-only kernels with ds_read_b128 operand fragments (aligned shapes only), 13 = 128x128 / 14 = 64x128 / 15 = 64x64 / 16 = 128x64
- * quad-fragment kernels of the NN (a_kmajor=1, b_kmajor=0) and TN (0,0; 13 only) layouts (17 = 128x128 / 18 = 128x64: NT with the software-pipelined
- * main loop, full tiles only, bit-identical to 10 / 11; 20 = 128x128 / 21 = 128x64: NT with 32-deep K tiles, full tiles only, bit-identical to 10 / 11): ds_read_b128 along the row-contiguous operand, no transpose (0: built-in cost model), splits >= 1 = split-K factor.  Used by the host-side autotuner (act_amd/kernels.py), results are identical up to
- * the fp32 summation order of split-K. */
+/* same, with an explicit launch configuration (used by the host-side autotuner, act_amd/kernels.py): `tile` names a workgroup tile (BM x BN) of one
+ * kernel family, splits >= 1 = split-K factor (deterministic two-pass; needs the workspace).  The ids, from the tile table in csrc/gemm.hip
+ * (act_gemm_tile_info reads it); "full" = 16-byte aligned operands, M % BM == N % BN == 0, K and every K range % 32 == 0; "M tail" = full but for
+ * M % BM, with A K-major:
+ *    0            built-in cost model: picks the tile of 1..3 and its own split-K (`splits` is ignored); skinny TN products stream instead
+ *    1,  2,  3    128x128, 128x64, 64x64 on v_mfma_f32_32x32x2_f32: all layouts, any shape
+ *    4,  5,  6    the same tiles, software-pipelined (3-stage LDS, mid-tile barrier) when the shape is full, else exactly the kernels of 1..3
+ *    7,  8,  9    the same tiles on v_mfma_f32_16x16x4_f32: all layouts; full or M tail
+ *   10, 11, 12    the same tiles, NT only, ds_read_b128 operand fragments: full or M tail
+ *   13 .. 16      128x128, 64x128, 64x64, 128x64 quad-fragment kernels: 13 NN and TN, 14..16 NN only; full or M tail
+ *   17, 18        128x128, 128x64, NT, software-pipelined: full only; bit-identical to 10, 11
+ *   20, 21        128x128, 128x64, NT, 32-deep K tiles: full only; bit-identical to 10, 11
+ *   30, 31, 32    as 10..12 with the hand-scheduled main loop (bit-identical); additionally the byte offsets inside one K tile must fit 32 bits
+ *   33 .. 36      as 13..16 with the hand-scheduled main loop (bit-identical); same offset bound
+ * ACT_E_BADARG for an id that is not listed, a layout or shape the id does not take, or splits > 1 without room for the partial sums.  Between
+ * families results are identical up to the fp32 summation order (and that of split-K). */
 int act_sgemm_ex_f32(int a_kmajor, int b_kmajor, int M, int N, int K, const float* A, int lda, const float* B, int ldb,
                      float* C, int ldc, const act_gemm_epilogue_t* epilogue, float* workspace, size_t workspace_bytes,
                      int tile, int splits, act_stream_t stream);
@@ -412,9 +422,20 @@ int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, co
  * act_sgemm_f32 (no explicit configuration) first consults this table keyed by (a_kmajor, b_kmajor, M, N, K), then its built-in
  * cost model.  The Python host fills it from the shipped tune file and from first-use timing (act_amd/kernels.py); the composite
  * entry points below therefore launch exactly the configurations the single-GEMM path uses. */
-int act_gemm_tune_set(int a_kmajor, int b_kmajor, int M, int N, int K, int tile, int splits);
+int act_gemm_tune_set(int a_kmajor, int b_kmajor, int M, int N, int K, int tile, int splits);   /* ACT_E_BADARG: tile not 0 and in no row, splits < 0 */
 int act_gemm_tune_get(int a_kmajor, int b_kmajor, int M, int N, int K, int* tile, int* splits);   /* 0 = found, 1 = absent */
 int act_gemm_tune_clear(void);
+/* One row of the tile table behind act_sgemm_ex_f32: 0 = found, 1 = `tile` names no kernel (0, the cost model, is no row).  Out-pointers nullable.
+ * layouts: ACT_GEMM_LAYOUT_* bits, bit 2 * a_kmajor + b_kmajor;  need: ACT_GEMM_NEED_ANY / _FULL_OR_MTAIL / _FULL, possibly | ACT_GEMM_NEED_OFFSET32. */
+#define ACT_GEMM_LAYOUT_TN 1           /* a_kmajor = 0, b_kmajor = 0 */
+#define ACT_GEMM_LAYOUT_TT 2           /* 0, 1 */
+#define ACT_GEMM_LAYOUT_NN 4           /* 1, 0 */
+#define ACT_GEMM_LAYOUT_NT 8           /* 1, 1 */
+#define ACT_GEMM_NEED_ANY           0
+#define ACT_GEMM_NEED_FULL_OR_MTAIL 1
+#define ACT_GEMM_NEED_FULL          2
+#define ACT_GEMM_NEED_OFFSET32      4
+int act_gemm_tile_info(int tile, int* bm, int* bn, int* layouts, int* need);
 
 /* x[r,:] * gate[r / rows_per_scale] -> y   (DropPath gate applied to a gradient, utils/transformer_layers.py:105-120) */
 int act_scale_rows_f32(const float* x, const float* gate, int T, int D, int rows_per_scale, float* y, act_stream_t stream);

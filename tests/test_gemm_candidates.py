@@ -118,3 +118,49 @@ def test_gemm_config_is_one_decision_for_both_host_paths(monkeypatch):
         assert CP._tune_shape(1, 1, 2000, 512, 4096, dev) is True and c_side(1, 1, 2000, 512, 4096) == (11, 1) and len(timed) == 2
     finally:
         CP.reset_tuning()                                       # the C-side table back to the shipped entries
+
+
+# the tile table of csrc/gemm.hip, written out: id -> (BM, BN, layouts as bits 2 * a_kmajor + b_kmajor); 15 = all four, 8 = NT, 4 = NN, 5 = NN and TN
+_TILES = {1: (128, 128, 15), 2: (128, 64, 15), 3: (64, 64, 15), 4: (128, 128, 15), 5: (128, 64, 15), 6: (64, 64, 15),
+          7: (128, 128, 15), 8: (128, 64, 15), 9: (64, 64, 15), 10: (128, 128, 8), 11: (128, 64, 8), 12: (64, 64, 8),
+          13: (128, 128, 5), 14: (64, 128, 4), 15: (64, 64, 4), 16: (128, 64, 4), 17: (128, 128, 8), 18: (128, 64, 8),
+          20: (128, 128, 8), 21: (128, 64, 8), 30: (128, 128, 8), 31: (128, 64, 8), 32: (64, 64, 8),
+          33: (128, 128, 5), 34: (64, 128, 4), 35: (64, 64, 4), 36: (128, 64, 4)}
+# need: 0 any shape, 1 full or M tail, 2 full only; + 4: the 32-bit in-tile offset bound of the hand-scheduled loops
+_NEED = {**{t: 0 for t in range(1, 7)}, **{t: 1 for t in range(7, 17)}, **{t: 2 for t in (17, 18, 20, 21)}, **{t: 5 for t in range(30, 37)}}
+
+
+def _tile_info(lib, tile):
+    import ctypes
+    v = [ctypes.c_int(-9) for _ in range(4)]
+    rc = lib.act_gemm_tile_info(tile, *[ctypes.byref(x) for x in v])
+    assert rc in (0, 1)
+    return tuple(x.value for x in v) if rc == 0 else None
+
+
+def test_tile_info_is_the_table_and_nothing_else():
+    import act_amd.kernels as K
+    got = {t: _tile_info(K.lib, t) for t in range(-4, 130)}
+    assert {t for t, v in got.items() if v is not None} == set(_TILES) == set(range(1, 19)) | {20, 21} | set(range(30, 37))
+    assert {t: got[t][:3] for t in _TILES} == _TILES and {t: got[t][3] for t in _TILES} == _NEED
+    assert K.lib.act_gemm_tile_info(13, None, None, None, None) == 0                  # every out-pointer is optional
+    try:
+        for t in (-1, 19, 22, 29, 37, 64):
+            assert got[t] is None and K.lib.act_gemm_tune_set(1, 1, 1000, 512, 4096, t, 1) == -1      # ACT_E_BADARG
+        assert K.lib.act_gemm_tune_get(1, 1, 1000, 512, 4096, None, None) == 1         # nothing was stored
+        for t in [0] + sorted(_TILES):
+            assert K.lib.act_gemm_tune_set(1, 1, 1000, 512, 4096, t, 1) == 0
+    finally:
+        import act_amd.composite as CP
+        CP.reset_tuning()
+
+
+def test_every_proposed_candidate_is_admitted_for_its_layout():
+    import act_amd.kernels as K
+    layouts = {t: _tile_info(K.lib, t)[2] for t in _TILES}
+    seen = set()
+    for ak, bk, M, N, Kd, ws, ms in _cases():
+        for t, _ in K.gemm_candidates(bool(ak), bool(bk), M, N, Kd, ws, ms):
+            seen.add(t)
+            assert t in layouts and layouts[t] & (1 << (2 * ak + bk)), (t, ak, bk, M, N, Kd)
+    assert seen
