@@ -19,9 +19,8 @@
 // O^T = V^T P^T.  K and V are staged once per (cloud, head) in LDS ([key][hd+4]: conflict-free b128 A-operand
 // reads for K, conflict-free b32 reads for V); Q rows are loaded straight into registers.
 // All backward kernels recompute P from the saved log-sum-exp and write dqkv (and dkv0) in the layout of their inputs.
-#include "common.h"
+#include "attn_frag.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // General operand description: queries come from `q` (Sq rows per cloud), keys/values from up to two row segments
@@ -66,7 +65,7 @@ __global__ __launch_bounds__(256, (JT == 1 ? 3 : 2)) void attn_fwd_kernel(const 
     const int ql = lane & 31, half = lane >> 5;
     const int q = qblock + qt * 32 + ql;
     const float scale = a.scale;
-    const float sc2 = scale * 1.44269504088896340736f;             // scale * log2(e)
+    const float sc2 = scale * ATT_LOG2E;             // scale * log2(e)
 
     // ---- Q operand: lane (q, half) holds Q[q][half*HD/2 + s], s = 0..HD/2-1
     float qreg[HD / 2];
@@ -655,13 +654,7 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(const float* __rest
 }
 
 
-// =================================================================================== register fragment forms of the single-pass backward
-// A wave owns a 32-row block of one (cloud, head) and meets the other side in 32-row tiles.  Operands go into the register form their MFMA wants --
-//   "row form"  lane (row = lane&31, half = lane>>5) holds X[row][half*HD/2 .. +HD/2)   (A or B operand of a head-dimension reduction: the
-//               reduction index of an MFMA is a free permutation as long as A and B agree, so the two halves split the head dimension)
-//   "col form"  lane (c = lane&31, half) holds X[f(r, half)][(HD/32)*c + dt], f(r, half) = (r&3) + 8*(r>>2) + 4*half   (A operand of a reduction over
-//               rows: row f(r, half) is exactly the row the C/D register r of that half-wave belongs to, so P / dS / dS^t are B operands
-//               straight from their accumulator registers)
+// =================================================================================== operands of the single-pass backward (fragment forms: attn_frag.h)
 // Keys come from two row segments (S0 prefix rows of kv0, then the S1 rows of the packed qkv1), as in the kernels above.
 struct AttnRegArgs {
     const float* q;  const float* k0; const float* v0; const float* k1; const float* v1;      // head 0 of row 0 of each operand
@@ -672,7 +665,6 @@ struct AttnRegArgs {
     int B, H, Sq, S0, S1;
     float scale;
 };
-#define ATT_F(r, half) (((r) & 3) + 8 * ((r) >> 2) + 4 * (half))
 
 // Tails without clamps: the LAST 32-row tile of a side is shifted back to end exactly at the last row (rows S-32 .. S-1, all valid) and the
 // rows it shares with the previous tile are masked out of P (keys) or simply not stored (owned rows).  So every tile is a full tile inside ONE
@@ -708,25 +700,6 @@ __device__ __forceinline__ void att_load_col_form(const AttSeg g, int c, int hal
             x[r][0] = v.x; x[r][1] = v.y;
         } else {
             x[r][0] = rb[lane_off];
-        }
-    }
-}
-// store an accumulator set in the o-layout (acc[dt][r] = X^t[d = (HD/32) * f(r, half) + dt][row = lane&31]) as row-major X[row][d], scaled
-template <int HD>
-__device__ __forceinline__ void att_store_o(float* __restrict__ rowp, int half, const f32x16* acc, float mul) {
-    constexpr int NDT = HD / 32;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {                                        // registers 4g .. 4g+3 = rows m = 8g + 4 half + (0..3) -> NDT * 4 consecutive d
-        if constexpr (NDT == 2) {
-            float4 t0, t1;
-            t0.x = acc[0][g * 4 + 0] * mul; t0.y = acc[1][g * 4 + 0] * mul; t0.z = acc[0][g * 4 + 1] * mul; t0.w = acc[1][g * 4 + 1] * mul;
-            t1.x = acc[0][g * 4 + 2] * mul; t1.y = acc[1][g * 4 + 2] * mul; t1.z = acc[0][g * 4 + 3] * mul; t1.w = acc[1][g * 4 + 3] * mul;
-            *reinterpret_cast<float4*>(rowp + 16 * g + 8 * half) = t0;
-            *reinterpret_cast<float4*>(rowp + 16 * g + 8 * half + 4) = t1;
-        } else {
-            float4 t;
-            t.x = acc[0][g * 4 + 0] * mul; t.y = acc[0][g * 4 + 1] * mul; t.z = acc[0][g * 4 + 2] * mul; t.w = acc[0][g * 4 + 3] * mul;
-            *reinterpret_cast<float4*>(rowp + 8 * g + 4 * half) = t;
         }
     }
 }

@@ -8,11 +8,10 @@
 // include/act_hip.h and restated by tests/augment_ref.py.
 // Built with -ffp-contract=off (act_amd/build.py): every product and sum below rounds once, so a fp32 host restatement reproduces the affine ops
 // bit for bit.
-#include "common.h"
+#include "dropout.h"
 
 #define AUG_LDS_MAX_N 8192
 #define AUG_RED 64                    // floats of reduction scratch ahead of the cloud image: [2][16 waves] partial maxima
-#define AUG_DOMAIN 3u                 // Philox counter word c2 (0: gumbel noise, 1: LayerNorm dropout, 2: attention dropout)
 
 namespace {
 
@@ -27,9 +26,9 @@ struct AugArgs {                      // the op table, passed to the kernel BY V
 __device__ __forceinline__ float aug_u01(uint32_t bits) { return (float)(bits >> 8) * 5.9604644775390625e-08f; }              // [0, 1)
 __device__ __forceinline__ float aug_u01_open(uint32_t bits) { return (float)((bits >> 8) + 1u) * 5.9604644775390625e-08f; }   // (0, 1]
 
-// the words of one counter: (slot, cloud, 3, position + 8 * sub); sub 0 = the op's per-cloud draws, sub 1 = its per-point draws
+// the words of one counter: (slot, cloud, PHILOX_DOMAIN_AUGMENT = 3, position + 8 * sub); sub 0 = the op's per-cloud draws, sub 1 = its per-point draws
 __device__ __forceinline__ void aug_philox(uint64_t seed, uint32_t slot, uint32_t cloud, uint32_t pos, uint32_t sub, uint32_t r[4]) {
-    philox4x32_10(slot, cloud, AUG_DOMAIN, pos + 8u * sub, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    philox_draw(seed, slot, cloud, PHILOX_DOMAIN_AUGMENT, pos + 8u * sub, r);
 }
 
 // three per-cloud uniforms of an op: injected [B,3] or the first three words of per-cloud counter `slot`
@@ -44,7 +43,7 @@ template <bool LDS>
 __global__ __launch_bounds__(1024) void augment_kernel(float* pc, int N, AugArgs a, uint64_t seed,
                                                        const uint64_t* __restrict__ seed_dev) {
     extern __shared__ __attribute__((aligned(16))) float aug_smem[];
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;      // device-resident step counter (replayable from a hipGraph), as bert.hip
+    seed = philox_fold_seed(seed, seed_dev);
     const uint32_t b = blockIdx.x;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = nt >> 6;
     const int n3 = 3 * N;

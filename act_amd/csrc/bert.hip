@@ -1,35 +1,26 @@
 // bert.hip -- the two kernels a frozen post-LayerNorm (BERT) layer needs beyond the GEMMs, both with inverted dropout whose keep mask is either a
 // given tensor (parity tests inject the reference's draws) or Philox4x32-10 regenerated wherever it is needed (nothing is stored for the backward):
 //   (a) y = LN(keep o t / (1-p) + res) * gamma + beta, rows of width D, and its backward (dt, dres; the language model is frozen: no dgamma / dbeta)
-//       mask key (seed, row, c/4) + the device-resident counter seed_dev: the convention of prompt_layernorm_fwd_kernel (norm.hip)
+//       mask: dropout.h, domain 1 (dense rows)
 //   (b) attention with dropout on the probabilities: out = (softmax(q k^t scale) o keep / (1-p)) v on the packed qkv [B,S,3,H,hd] of
-//       act_attention_fwd_f32, any S >= 1, hd 32 or 64.  mask key (seed, (b H + h) S + query, key/4): four keeps per Philox call.
-// (b) runs on v_mfma_f32_32x32x2_f32 in the fragment forms of attention.hip's single-pass backward: one wave owns 32 rows of one (cloud, head) and
+//       act_attention_fwd_f32, any S >= 1, hd 32 or 64.  mask: dropout.h, domain 2 (four keeps per Philox call).
+// (b) runs on v_mfma_f32_32x32x2_f32 in the fragment forms of attn_frag.h (the clamped loaders): one wave owns 32 rows of one (cloud, head) and
 // meets the other side in 32-row tiles straight from global memory (no LDS, no barrier); rows past S are clamped on the way in and masked out of P.
 // At p = 0 the layer calls act_attention_fwd_f32 / act_attention_bwd_f32: these kernels are the dropout path only.
-#include "common.h"
-
-#define BLN_MAXV 8            // float4 per lane of a row: D <= 64*4*8 = 2048 (as LN_MAXV, norm.hip)
-#define BERT_F(r, half) (((r) & 3) + 8 * ((r) >> 2) + 4 * (half))      // row of C/D register r of a half-wave (32x32x2 MFMA)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "attn_frag.h"
+#include "dropout.h"
+#include "ln_row.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ (a) dropout + residual + LayerNorm
 // keep / (1-p) of the four channels 4c .. 4c+3 of a row: the given mask, Philox, or 1 (p = 0)
-__device__ __forceinline__ float4 bln_keep4(const float4* __restrict__ mask4, size_t i4, float4 mv, float drop_p, float inv_keep, uint32_t thr,
-                                            uint64_t seed, uint32_t row, uint32_t c) {
+__device__ __forceinline__ float4 bln_keep4(const float4* __restrict__ mask4, float4 mv, float drop_p, const DropoutKey& key, uint32_t row, uint32_t c) {
     float4 k = make_float4(1.f, 1.f, 1.f, 1.f);
     if (drop_p > 0.f) {
         if (mask4) {
-            k.x = mv.x * inv_keep; k.y = mv.y * inv_keep; k.z = mv.z * inv_keep; k.w = mv.w * inv_keep;
-        } else {
-            uint32_t r[4];
-            philox4x32_10(c, row, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-            k.x = (r[0] >> 8) < thr ? 0.f : inv_keep; k.y = (r[1] >> 8) < thr ? 0.f : inv_keep;
-            k.z = (r[2] >> 8) < thr ? 0.f : inv_keep; k.w = (r[3] >> 8) < thr ? 0.f : inv_keep;
-        }
+            k.x = mv.x * key.inv_keep; k.y = mv.y * key.inv_keep; k.z = mv.z * key.inv_keep; k.w = mv.w * key.inv_keep;
+        } else k = dropout_keep4(key, row, c);
     }
     return k;
 }
@@ -42,7 +33,7 @@ __global__ __launch_bounds__(256) void bert_dropout_ln_fwd_kernel(const float* _
                                                                   const float* __restrict__ beta, float* __restrict__ y, float* __restrict__ rstd_out,
                                                                   int T, int D, float eps, float drop_p, uint64_t seed,
                                                                   const uint64_t* __restrict__ seed_dev) {
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;      // device-resident step counter (replayable from a hipGraph)
+    const DropoutKey key = dropout_key(drop_p, seed, seed_dev);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
@@ -50,50 +41,31 @@ __global__ __launch_bounds__(256) void bert_dropout_ln_fwd_kernel(const float* _
     const float4* __restrict__ t4 = reinterpret_cast<const float4*>(t) + (size_t)row * nv;
     const float4* __restrict__ r4 = reinterpret_cast<const float4*>(res) + (size_t)row * nv;
     const float4* __restrict__ m4 = (mask && drop_p > 0.f) ? reinterpret_cast<const float4*>(mask) + (size_t)row * nv : nullptr;
-    const float inv_keep = 1.0f / (1.0f - drop_p);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);              // drop when the top 24 random bits < thr
     int cc[MAXV]; float4 tv[MAXV], rv[MAXV], mv[MAXV];
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) { cc[i] = min(lane + 64 * i, nv - 1); tv[i] = t4[cc[i]]; rv[i] = r4[cc[i]]; }
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) mv[i] = m4 ? m4[cc[i]] : make_float4(1.f, 1.f, 1.f, 1.f);
     float4 v[MAXV];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
-            const float4 k = bln_keep4(m4, 0, mv[i], drop_p, inv_keep, thr, seed, (uint32_t)row, (uint32_t)c);
+            const float4 k = bln_keep4(m4, mv[i], drop_p, key, (uint32_t)row, (uint32_t)c);
             float4 a;
             a.x = fmaf(tv[i].x, k.x, rv[i].x); a.y = fmaf(tv[i].y, k.y, rv[i].y); a.z = fmaf(tv[i].z, k.z, rv[i].z); a.w = fmaf(tv[i].w, k.w, rv[i].w);
             v[i] = a;
-            s += (a.x + a.y) + (a.z + a.w);
         } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float mean = wave_sum_f32(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, e = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (e * e + d * d);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum_f32(q) / (float)D + eps);
+    const float mean = ln_row_mean<MAXV>(v, lane, nv, D);
+    const float rstd = ln_row_rstd<MAXV>(v, mean, lane, nv, D, eps);
     float4* __restrict__ yr = reinterpret_cast<float4*>(y) + (size_t)row * nv;
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
     const float4* __restrict__ b4 = reinterpret_cast<const float4*>(beta);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int c = lane + 64 * i;
-        if (c < nv) {
-            const float4 g = g4[c], b = b4[c];
-            float4 o;
-            o.x = (v[i].x - mean) * rstd * g.x + b.x; o.y = (v[i].y - mean) * rstd * g.y + b.y;
-            o.z = (v[i].z - mean) * rstd * g.z + b.z; o.w = (v[i].w - mean) * rstd * g.w + b.w;
-            yr[c] = o;
-        }
+        if (c < nv) yr[c] = ln_row_norm4(v[i], mean, rstd, g4[c], b4[c]);
     }
     if (lane == 0 && rstd_out) rstd_out[row] = rstd;
 }
@@ -106,7 +78,7 @@ __global__ __launch_bounds__(256) void bert_dropout_ln_bwd_kernel(const float* _
                                                                   const float* __restrict__ beta, const float* __restrict__ rstd,
                                                                   float* __restrict__ dt, float* __restrict__ dres, int T, int D, float drop_p,
                                                                   uint64_t seed, const uint64_t* __restrict__ seed_dev) {
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;
+    const DropoutKey key = dropout_key(drop_p, seed, seed_dev);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
@@ -116,8 +88,6 @@ __global__ __launch_bounds__(256) void bert_dropout_ln_bwd_kernel(const float* _
     const float4* __restrict__ m4 = (mask && drop_p > 0.f) ? reinterpret_cast<const float4*>(mask) + (size_t)row * nv : nullptr;
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
     const float4* __restrict__ b4 = reinterpret_cast<const float4*>(beta);
-    const float inv_keep = 1.0f / (1.0f - drop_p);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
     int cc[MAXV]; float4 dv[MAXV], yv[MAXV], mv[MAXV], gv[MAXV], bv[MAXV];
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) { cc[i] = min(lane + 64 * i, nv - 1); dv[i] = d4[cc[i]]; yv[i] = y4[cc[i]]; gv[i] = g4[cc[i]]; bv[i] = b4[cc[i]]; }
@@ -149,7 +119,7 @@ __global__ __launch_bounds__(256) void bert_dropout_ln_bwd_kernel(const float* _
             o.x = rs * (w[i].x - m1 - h[i].x * m2); o.y = rs * (w[i].y - m1 - h[i].y * m2);
             o.z = rs * (w[i].z - m1 - h[i].z * m2); o.w = rs * (w[i].w - m1 - h[i].w * m2);
             drr[c] = o;
-            const float4 k = bln_keep4(m4, 0, mv[i], drop_p, inv_keep, thr, seed, (uint32_t)row, (uint32_t)c);
+            const float4 k = bln_keep4(m4, mv[i], drop_p, key, (uint32_t)row, (uint32_t)c);
             dtr[c] = make_float4(o.x * k.x, o.y * k.y, o.z * k.z, o.w * k.w);
         }
     }
@@ -163,82 +133,14 @@ struct BertAttnArgs {
     float scale, inv_keep; uint32_t thr;
     uint64_t seed; const uint64_t* seed_dev;
 };
-#define BERT_LOG2E 1.4426950408889634f
-#define BERT_LN2 0.6931471805599453f
-
-// keep / (1-p) of keys key0 .. key0+3 (key0 % 4 == 0) of query row `rowid` = (b H + h) S + query
-__device__ __forceinline__ void attn_keep4(const BertAttnArgs& a, uint64_t seed, uint32_t rowid, int key0, float kf[4]) {
-    if (a.mask) {
-        const uint8_t* __restrict__ m = a.mask + (size_t)rowid * a.S;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) kf[k] = (key0 + k < a.S && m[key0 + k]) ? a.inv_keep : 0.f;
-    } else {
-        uint32_t r[4];
-        philox4x32_10((uint32_t)(key0 >> 2), rowid, 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) kf[k] = (r[k] >> 8) < a.thr ? 0.f : a.inv_keep;
-    }
-}
-// the same for ONE key (a lane that owns a key column and walks queries)
-__device__ __forceinline__ float attn_keep1(const BertAttnArgs& a, uint64_t seed, uint32_t rowid, int key) {
-    if (a.mask) return (key < a.S && a.mask[(size_t)rowid * a.S + key]) ? a.inv_keep : 0.f;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)(key >> 2), rowid, 2u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const int k = key & 3;
-    const uint32_t v = k == 0 ? r[0] : (k == 1 ? r[1] : (k == 2 ? r[2] : r[3]));
-    return (v >> 8) < a.thr ? 0.f : a.inv_keep;
-}
-
-// "row form": lane (row = lane&31, half = lane>>5) holds X[row][half*HD/2 .. +HD/2) (operand of a head-dimension reduction)
-template <int HD>
-__device__ __forceinline__ void bert_load_row_form(const float* __restrict__ rowp, int half, float mul, float* x) {
-    const float* p = rowp + half * (HD / 2);
-#pragma unroll
-    for (int i = 0; i < HD / 8; ++i) {
-        const float4 t = *reinterpret_cast<const float4*>(p + 4 * i);
-        x[4 * i] = t.x * mul; x[4 * i + 1] = t.y * mul; x[4 * i + 2] = t.z * mul; x[4 * i + 3] = t.w * mul;
-    }
-}
-// "col form": lane (c = lane&31, half) holds X[t0 + f(r, half)][(HD/32) c + dt] (A operand of a reduction over rows; rows past S-1 are clamped --
-// their partner in P / dS is zero)
-template <int HD>
-__device__ __forceinline__ void bert_load_col_form(const float* __restrict__ base, int ld, int t0, int S, int c, int half, float (*x)[HD / 32]) {
-    constexpr int NDT = HD / 32;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = min(t0 + BERT_F(r, half), S - 1);
-        const float* p = base + (size_t)row * ld + NDT * c;
-        if constexpr (NDT == 2) { const float2 v = *reinterpret_cast<const float2*>(p); x[r][0] = v.x; x[r][1] = v.y; }
-        else x[r][0] = p[0];
-    }
-}
-// accumulators acc[dt][r] = X^t[d = (HD/32) f(r, half) + dt][row = lane&31] -> row-major X[row][d], scaled
-template <int HD>
-__device__ __forceinline__ void bert_store_o(float* __restrict__ rowp, int half, const f32x16* acc, float mul) {
-    constexpr int NDT = HD / 32;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if constexpr (NDT == 2) {
-            float4 t0, t1;
-            t0.x = acc[0][g * 4 + 0] * mul; t0.y = acc[1][g * 4 + 0] * mul; t0.z = acc[0][g * 4 + 1] * mul; t0.w = acc[1][g * 4 + 1] * mul;
-            t1.x = acc[0][g * 4 + 2] * mul; t1.y = acc[1][g * 4 + 2] * mul; t1.z = acc[0][g * 4 + 3] * mul; t1.w = acc[1][g * 4 + 3] * mul;
-            *reinterpret_cast<float4*>(rowp + 16 * g + 8 * half) = t0;
-            *reinterpret_cast<float4*>(rowp + 16 * g + 8 * half + 4) = t1;
-        } else {
-            float4 t;
-            t.x = acc[0][g * 4 + 0] * mul; t.y = acc[0][g * 4 + 1] * mul; t.z = acc[0][g * 4 + 2] * mul; t.w = acc[0][g * 4 + 3] * mul;
-            *reinterpret_cast<float4*>(rowp + 8 * g + 4 * half) = t;
-        }
-    }
-}
+__device__ __forceinline__ DropoutKey attn_key(const BertAttnArgs& a) { return DropoutKey{philox_fold_seed(a.seed, a.seed_dev), a.thr, a.inv_keep}; }
 
 // forward: grid (ceil(S/128), B*H), a wave = 32 queries.  S^t = K Q^t puts all scores of ONE query into one lane pair (c, c+32), so the online softmax
 // is 16 registers + one cross-half exchange, and P^t is the B operand of O^t = V^t P^t straight from its registers.
 template <int HD>
 __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const BertAttnArgs a) {
     constexpr int NDT = HD / 32, HH = HD / 2;
-    uint64_t seed = a.seed;
-    if (a.seed_dev) seed ^= a.seed_dev[0] * 0x9E3779B97F4A7C15ull;
+    const DropoutKey key = attn_key(a);
     const int lane = threadIdx.x & 63, c = lane & 31, half = lane >> 5;
     const int S = a.S, q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
     if (q0 >= S) return;
@@ -250,7 +152,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const BertAttnArgs a
     const int qrow = min(q0 + c, S - 1);
     const uint32_t rowid = (uint32_t)bh * (uint32_t)S + (uint32_t)qrow;
     float qreg[HH];
-    bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * BERT_LOG2E, qreg);
+    bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * ATT_LOG2E, qreg);
     f32x16 o[NDT];
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -270,7 +172,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const BertAttnArgs a
         float mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            if (k0 + BERT_F(r, half) >= S) st[r] = -INFINITY;
+            if (k0 + ATT_F(r, half) >= S) st[r] = -INFINITY;
             mx = fmaxf(mx, st[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -289,7 +191,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const BertAttnArgs a
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float kf[4];
-            attn_keep4(a, seed, rowid, k0 + 8 * g + 4 * half, kf);
+            dropout_attn_keep4(a.mask, a.S, key, rowid, k0 + 8 * g + 4 * half, kf);
 #pragma unroll
             for (int k = 0; k < 4; ++k) st[4 * g + k] *= kf[k];
         }
@@ -299,8 +201,8 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const BertAttnArgs a
             for (int dt = 0; dt < NDT; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vc[r][dt], st[r], o[dt], 0, 0, 0);
     }
     if (q0 + c < S) {
-        bert_store_o<HD>(a.o + ((size_t)b * S + q0 + c) * (a.H * HD) + h * HD, half, o, 1.0f / l);
-        if (half == 0 && a.lse_out) a.lse_out[(size_t)bh * S + q0 + c] = (m + log2f(l)) * BERT_LN2;
+        att_store_o<HD>(a.o + ((size_t)b * S + q0 + c) * (a.H * HD) + h * HD, half, o, 1.0f / l);
+        if (half == 0 && a.lse_out) a.lse_out[(size_t)bh * S + q0 + c] = (m + log2f(l)) * ATT_LN2;
     }
 }
 
@@ -321,8 +223,7 @@ __global__ __launch_bounds__(256) void bert_attn_delta_kernel(const float* __res
 template <int HD>
 __global__ __launch_bounds__(256) void bert_attn_bwd_dq_kernel(const BertAttnArgs a) {
     constexpr int NDT = HD / 32, HH = HD / 2;
-    uint64_t seed = a.seed;
-    if (a.seed_dev) seed ^= a.seed_dev[0] * 0x9E3779B97F4A7C15ull;
+    const DropoutKey key = attn_key(a);
     const int lane = threadIdx.x & 63, c = lane & 31, half = lane >> 5;
     const int S = a.S, q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
     if (q0 >= S) return;
@@ -334,9 +235,9 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dq_kernel(const BertAttnArg
     const int qrow = min(q0 + c, S - 1);
     const uint32_t rowid = (uint32_t)bh * (uint32_t)S + (uint32_t)qrow;
     float qreg[HH], doreg[HH];
-    bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * BERT_LOG2E, qreg);
+    bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * ATT_LOG2E, qreg);
     bert_load_row_form<HD>(a.dout + ((size_t)b * S + qrow) * ldo + h * HD, half, 1.0f, doreg);
-    const float lse2 = a.lse[(size_t)bh * S + qrow] * BERT_LOG2E, dl = a.delta[(size_t)bh * S + qrow];
+    const float lse2 = a.lse[(size_t)bh * S + qrow] * ATT_LOG2E, dl = a.delta[(size_t)bh * S + qrow];
     f32x16 dq[NDT];
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -360,11 +261,11 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dq_kernel(const BertAttnArg
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             float kf[4];
-            attn_keep4(a, seed, rowid, k0 + 8 * g + 4 * half, kf);
+            dropout_attn_keep4(a.mask, a.S, key, rowid, k0 + 8 * g + 4 * half, kf);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int r = 4 * g + k;
-                const float p = (k0 + BERT_F(r, half) < S) ? exp2f(st[r] - lse2) : 0.f;
+                const float p = (k0 + ATT_F(r, half) < S) ? exp2f(st[r] - lse2) : 0.f;
                 st[r] = p * (dp[r] * kf[k] - dl) * a.scale;              // dS^t
             }
         }
@@ -373,7 +274,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dq_kernel(const BertAttnArg
 #pragma unroll
             for (int dt = 0; dt < NDT; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[r][dt], st[r], dq[dt], 0, 0, 0);
     }
-    if (q0 + c < S) bert_store_o<HD>(a.dqkv + ((size_t)b * S + q0 + c) * ld + h * HD, half, dq, 1.0f);
+    if (q0 + c < S) att_store_o<HD>(a.dqkv + ((size_t)b * S + q0 + c) * ld + h * HD, half, dq, 1.0f);
 }
 
 // dK, dV: a wave = 32 keys (a lane pair = one key column), walks the query tiles: S and dP as [query f(r, half)][key c], so P o keep and dS are the
@@ -381,8 +282,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dq_kernel(const BertAttnArg
 template <int HD>
 __global__ __launch_bounds__(256) void bert_attn_bwd_dkv_kernel(const BertAttnArgs a) {
     constexpr int NDT = HD / 32, HH = HD / 2;
-    uint64_t seed = a.seed;
-    if (a.seed_dev) seed ^= a.seed_dev[0] * 0x9E3779B97F4A7C15ull;
+    const DropoutKey dkey = attn_key(a);
     const int lane = threadIdx.x & 63, c = lane & 31, half = lane >> 5;
     const int S = a.S, k0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
     if (k0 >= S) return;
@@ -409,7 +309,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dkv_kernel(const BertAttnAr
         for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
         {
             float qreg[HH], doreg[HH];
-            bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * BERT_LOG2E, qreg);
+            bert_load_row_form<HD>(qb + (size_t)qrow * ld, half, a.scale * ATT_LOG2E, qreg);
             bert_load_row_form<HD>(dob + (size_t)qrow * ldo, half, 1.0f, doreg);
 #pragma unroll
             for (int i = 0; i < HH; ++i) {
@@ -422,10 +322,10 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dkv_kernel(const BertAttnAr
         bert_load_col_form<HD>(dob, ldo, q0, S, c, half, doc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int qi = q0 + BERT_F(r, half), qic = min(qi, S - 1);
+            const int qi = q0 + ATT_F(r, half), qic = min(qi, S - 1);
             const size_t li = (size_t)bh * S + qic;
-            const float kf = attn_keep1(a, seed, (uint32_t)li, key);
-            const float p = (qi < S && kvalid) ? exp2f(st[r] - a.lse[li] * BERT_LOG2E) : 0.f;
+            const float kf = dropout_attn_keep1(a.mask, a.S, dkey, (uint32_t)li, key);
+            const float p = (qi < S && kvalid) ? exp2f(st[r] - a.lse[li] * ATT_LOG2E) : 0.f;
             st[r] = p * (dp[r] * kf - a.delta[li]) * a.scale;            // dS
             dp[r] = p * kf;                                              // P o keep / (1-p)
         }
@@ -439,8 +339,8 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_dkv_kernel(const BertAttnAr
     }
     if (kvalid) {
         float* __restrict__ rowp = a.dqkv + ((size_t)b * S + key) * ld + h * HD;
-        bert_store_o<HD>(rowp + a.H * HD, half, dk, 1.0f);
-        bert_store_o<HD>(rowp + 2 * a.H * HD, half, dv, 1.0f);
+        att_store_o<HD>(rowp + a.H * HD, half, dk, 1.0f);
+        att_store_o<HD>(rowp + 2 * a.H * HD, half, dv, 1.0f);
     }
 }
 
@@ -453,7 +353,7 @@ bool attn_args_ok(int B, int S, int H, int hd, float p) {
 extern "C" int act_dropout_add_layernorm_fwd_f32(const float* t, const float* res, const float* mask, int T, int D, float drop_p, uint64_t seed,
                                                  const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, float* y, float* rstd,
                                                  act_stream_t stream) {
-    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * BLN_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
+    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
     if (T == 0) return 0;                                               // before the pointers: an empty tensor has none
     if (!t || !res || !gamma || !beta || !y) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
@@ -467,7 +367,7 @@ extern "C" int act_dropout_add_layernorm_fwd_f32(const float* t, const float* re
 extern "C" int act_dropout_add_layernorm_bwd_f32(const float* dy, const float* y, const float* mask, int T, int D, float drop_p, uint64_t seed,
                                                  const uint64_t* seed_dev, const float* gamma, const float* beta, const float* rstd, float* dt,
                                                  float* dres, act_stream_t stream) {
-    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * BLN_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
+    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
     if (T == 0) return 0;
     if (!dy || !y || !gamma || !beta || !rstd || !dt || !dres) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
@@ -486,7 +386,7 @@ extern "C" int act_attention_dropout_fwd_f32(const float* qkv, const uint8_t* ma
     hipStream_t s = (hipStream_t)stream;
     BertAttnArgs a{};
     a.qkv = qkv; a.mask = mask; a.o = out; a.lse_out = lse; a.B = B; a.S = S; a.H = H; a.scale = scale;
-    a.inv_keep = 1.0f / (1.0f - drop_p); a.thr = (uint32_t)(drop_p * 16777216.0f); a.seed = seed; a.seed_dev = seed_dev;
+    a.inv_keep = dropout_inv_keep(drop_p); a.thr = dropout_thr(drop_p); a.seed = seed; a.seed_dev = seed_dev;
     ActProfScope ps(KID_ATTN_FWD, s, 4.0 * B * H * (double)S * S * head_dim, 4.0 * 4.0 * B * S * (double)H * head_dim);
     const dim3 grid((S + 127) / 128, B * H);
     if (head_dim == 64) hipLaunchKernelGGL(bert_attn_fwd_kernel<64>, grid, dim3(256), 0, s, a);
@@ -503,7 +403,7 @@ extern "C" int act_attention_dropout_bwd_f32(const float* qkv, const uint8_t* ma
     hipStream_t s = (hipStream_t)stream;
     BertAttnArgs a{};
     a.qkv = qkv; a.mask = mask; a.out = out; a.dout = dout; a.lse = lse; a.delta = delta; a.dqkv = dqkv; a.B = B; a.S = S; a.H = H; a.scale = scale;
-    a.inv_keep = 1.0f / (1.0f - drop_p); a.thr = (uint32_t)(drop_p * 16777216.0f); a.seed = seed; a.seed_dev = seed_dev;
+    a.inv_keep = dropout_inv_keep(drop_p); a.thr = dropout_thr(drop_p); a.seed = seed; a.seed_dev = seed_dev;
     ActProfScope ps(KID_ATTN_BWD, s, 14.0 * B * H * (double)S * S * head_dim, 4.0 * 8.0 * B * S * (double)H * head_dim);
     const long long n = (long long)B * S * H;
     hipLaunchKernelGGL(bert_attn_delta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, out, dout, delta, B, S, H, head_dim);

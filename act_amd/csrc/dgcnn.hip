@@ -9,7 +9,7 @@
 // The same two kernels with k = 1 and no gather implement the GroupNorm + LeakyReLU head (layer5).
 // Tokenizer: hard gumbel-softmax + one-hot x codebook == argmax_n(logits + G) followed by a row gather, fused with the
 // head's GroupNorm + LeakyReLU so the [B,G,8192] logits are read exactly once and never rewritten.
-#include "common.h"
+#include "dropout.h"
 #include <atomic>
 #include <stdlib.h>
 
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void gumbel_argmax_gather_kernel(const float* 
                                                                    int64_t* __restrict__ index_out, float* __restrict__ out,
                                                                    float* __restrict__ logits_out) {
     __shared__ float sv[4]; __shared__ int si[4]; __shared__ int swin;
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;      // device-resident step counter (replayable from a hipGraph)
+    seed = philox_fold_seed(seed, seed_dev);
     const int row = blockIdx.x, b = row / G;
     const int cpg = C / groups;
     float best = -3.0e38f; int bi = 0;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void gumbel_argmax_gather_kernel(const float* 
             const float4 x = *reinterpret_cast<const float4*>(h + (size_t)row * C + c4);
             const float xs[4] = {x.x, x.y, x.z, x.w};
             uint32_t rnd[4] = {0, 0, 0, 0};
-            if (!noise) philox4x32_10((uint32_t)(c4 >> 2), (uint32_t)row, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+            if (!noise) philox_draw(seed, (uint32_t)(c4 >> 2), (uint32_t)row, PHILOX_DOMAIN_GUMBEL, 0u, rnd);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int c = c4 + u, gi = c / cpg;
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void gumbel_argmax_gather_kernel(const float* 
             const float xs[4] = {x.x, x.y, x.z, x.w}, gs[4] = {ga.x, ga.y, ga.z, ga.w}, bs[4] = {be.x, be.y, be.z, be.w};
             uint32_t rnd[4] = {0, 0, 0, 0};
             float ns[4] = {0.f, 0.f, 0.f, 0.f};
-            if (!noise) philox4x32_10((uint32_t)(c4 >> 2), (uint32_t)row, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+            if (!noise) philox_draw(seed, (uint32_t)(c4 >> 2), (uint32_t)row, PHILOX_DOMAIN_GUMBEL, 0u, rnd);
             else { const float4 nz = *reinterpret_cast<const float4*>(noise + (size_t)row * C + c4); ns[0] = nz.x; ns[1] = nz.y; ns[2] = nz.z; ns[3] = nz.w; }
             float vs[4];
 #pragma unroll
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(256) void gumbel_softmax_fwd_kernel(const float* __
         const float4 x = *reinterpret_cast<const float4*>(logits + (size_t)row * C + c4);
         const float xs[4] = {x.x, x.y, x.z, x.w};
         uint32_t rnd[4] = {0, 0, 0, 0};
-        if (!noise) philox4x32_10((uint32_t)(c4 >> 2), (uint32_t)row, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+        if (!noise) philox_draw(seed, (uint32_t)(c4 >> 2), (uint32_t)row, PHILOX_DOMAIN_GUMBEL, 0u, rnd);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const float g = noise ? noise[(size_t)row * C + c4 + u] : gumbel_from_bits(rnd[u]);

@@ -5,10 +5,10 @@
 //   * cosine distillation loss forward / backward (models/act.py:1243-1254, lightly NegativeCosineSimilarity)
 // One wave per row: a row of D=384/768 floats sits in registers (float4 per lane), statistics come from DPP
 // wave reductions, nothing is staged through LDS.  All kernels are HBM-bound: one read + one write per element.
-#include "common.h"
+// The wave-per-row LayerNorm arithmetic is ln_row.h's; the Philox keep mask of the prompt kernels (domain 1, dense rows) is dropout.h's.
+#include "dropout.h"
+#include "ln_row.h"
 #include <stdlib.h>
-
-#define LN_MAXV 8          // float4 per lane: D <= 64*4*8 = 2048
 
 // (hi, lo) bf16 planes of four consecutive values (round to nearest even; lo = bf16(x - hi)): the operand form of the opt-in split-bf16 GEMM
 // (gemm_bf16x3.hip) -- same rounding as its split_bf16x2_kernel, so a producer that writes planes is bit-identical to producing fp32 and splitting it
@@ -20,6 +20,27 @@ __device__ __forceinline__ void store_planes4(unsigned short* __restrict__ hi, u
     for (int j = 0; j < 4; ++j) { h[j] = ln_bf16_rne(e[j]); l[j] = ln_bf16_rne(e[j] - __uint_as_float(h[j] << 16)); }
     reinterpret_cast<uint2*>(hi)[i4] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
     reinterpret_cast<uint2*>(lo)[i4] = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
+}
+// the row in v -> y and / or its bf16 planes (and xin_out = the row itself), chunk by chunk.  (round 6: batching the gamma / beta loads of
+// layernorm_fwd_kernel the way layernorm_bwd_kernel does costs it two waves per SIMD of occupancy -- 117 VGPRs -- and was 5 % SLOWER: with one row per
+// wave and eight waves per SIMD the chunk-by-chunk round trips are already covered)
+__device__ __forceinline__ void ln_store_row(const float4* v, float mean, float rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             float* __restrict__ y, unsigned short* __restrict__ y_hi, unsigned short* __restrict__ y_lo,
+                                             float* __restrict__ xin_out, int row, int lane, int nv) {
+    float4* __restrict__ yr = reinterpret_cast<float4*>(y) + (size_t)row * nv;
+    float4* __restrict__ xo = xin_out ? reinterpret_cast<float4*>(xin_out) + (size_t)row * nv : nullptr;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
+    const float4* __restrict__ b4 = reinterpret_cast<const float4*>(beta);
+#pragma unroll
+    for (int i = 0; i < LN_ROW_MAXV; ++i) {
+        const int c = lane + 64 * i;
+        if (c < nv) {
+            const float4 o = ln_row_norm4(v[i], mean, rstd, g4[c], b4[c]);
+            if (y) yr[c] = o;
+            if (y_hi) store_planes4(y_hi, y_lo, (size_t)row * nv + c, o);
+            if (xo) xo[c] = v[i];
+        }
+    }
 }
 
 // y = LN(x + pos) * gamma + beta ; optionally stores xin = x + pos (needed for the residual) ; mean/rstd for backward.
@@ -36,49 +57,19 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     const int nv = D >> 2;                                // float4 per row
     const float4* __restrict__ xr = reinterpret_cast<const float4*>(x + (size_t)row * D);
     const float4* __restrict__ pr = pos ? reinterpret_cast<const float4*>(pos + (size_t)row * D) : nullptr;
-    float4 v[LN_MAXV];
-    float s = 0.f;
+    float4 v[LN_ROW_MAXV];
 #pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
+    for (int i = 0; i < LN_ROW_MAXV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
             float4 a = xr[c];
             if (pr) { const float4 b = pr[c]; a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
             v[i] = a;
-            s += (a.x + a.y) + (a.z + a.w);
         } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float mean = wave_sum_f32(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-    const float var = wave_sum_f32(q) / (float)D;
-    const float rstd = rsqrtf(var + eps);
-    float4* __restrict__ yr = reinterpret_cast<float4*>(y + (size_t)row * D);
-    float4* __restrict__ xo = xin_out ? reinterpret_cast<float4*>(xin_out + (size_t)row * D) : nullptr;
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
-    const float4* __restrict__ b4 = reinterpret_cast<const float4*>(beta);
-    // (round 6: batching this kernel's loads the way layernorm_bwd_kernel does costs it two waves per SIMD of occupancy -- 117 VGPRs -- and was 5 % SLOWER: with one
-    //  row per wave and eight waves per SIMD the chunk-by-chunk round trips are already covered)
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float4 g = g4[c], b = b4[c];
-            float4 o;
-            o.x = (v[i].x - mean) * rstd * g.x + b.x; o.y = (v[i].y - mean) * rstd * g.y + b.y;
-            o.z = (v[i].z - mean) * rstd * g.z + b.z; o.w = (v[i].w - mean) * rstd * g.w + b.w;
-            if (y) yr[c] = o;
-            if (y_hi) store_planes4(y_hi, y_lo, (size_t)row * nv + c, o);
-            if (xo) xo[c] = v[i];
-        }
-    }
+    const float mean = ln_row_mean<LN_ROW_MAXV>(v, lane, nv, D);
+    const float rstd = ln_row_rstd<LN_ROW_MAXV>(v, mean, lane, nv, D, eps);
+    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, xin_out, row, lane, nv);
     if (lane == 0) { if (mean_out) mean_out[row] = mean; if (rstd_out) rstd_out[row] = rstd; }
 }
 
@@ -293,7 +284,7 @@ __global__ __launch_bounds__(1024) void mean_kernel(const float* __restrict__ v,
 extern "C" int act_layernorm_fwd_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out,
                                      float* y, float* mean, float* rstd, int T, int D, float eps, act_stream_t stream) {
     if (!x || !gamma || !beta || !y) return ACT_E_NULLPTR;
-    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_MAXV) return ACT_E_BADARG;
+    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV) return ACT_E_BADARG;
     if (T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D * (2 + (pos ? 1 : 0) + (xin_out ? 1 : 0)));
@@ -303,7 +294,7 @@ extern "C" int act_layernorm_fwd_f32(const float* x, const float* pos, const flo
 extern "C" int act_layernorm_fwd_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                             uint16_t* y_hi, uint16_t* y_lo, float* mean, float* rstd, int T, int D, float eps, act_stream_t stream) {
     if (!x || !gamma || !beta || !y_hi || !y_lo) return ACT_E_NULLPTR;
-    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_MAXV || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
+    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
     if (T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D * (2 + (pos ? 1 : 0) + (xin_out ? 1 : 0)));
@@ -312,75 +303,42 @@ extern "C" int act_layernorm_fwd_planes_f32(const float* x, const float* pos, co
 }
 
 // Prompt rows of the prompt-tuned Transformer (models/dvae.py:485-498,556-566), frozen-teacher form: for every cloud b and prompt p
-//   v = dropout(tok[p,:]) + ppos[p,:]   (inverted dropout, keep mask from Philox keyed by (seed, b*P+p, c/4))   ->  LN(v) * gamma + beta
+//   v = dropout(tok[p,:]) + ppos[p,:]   (inverted dropout, keep mask of row b*P+p: dropout.h, domain 1)   ->  LN(v) * gamma + beta
 // one launch instead of expand + dropout + add + LayerNorm, and the [B*P, D] intermediate is never written.
 __global__ __launch_bounds__(256) void prompt_layernorm_fwd_kernel(const float* __restrict__ tok, const float* __restrict__ ppos, int P,
                                                                    float drop_p, uint64_t seed, const uint64_t* __restrict__ seed_dev,
-                                                                   const float* __restrict__ gamma,
-                                                                   const float* __restrict__ beta, float* __restrict__ y, int T, int D,
-                                                                   float eps, unsigned short* __restrict__ y_hi = nullptr,
-                                                                   unsigned short* __restrict__ y_lo = nullptr) {
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;      // device-resident step counter (replayable from a hipGraph)
+                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                   float* __restrict__ y, int T, int D, float eps,
+                                                                   unsigned short* __restrict__ y_hi = nullptr, unsigned short* __restrict__ y_lo = nullptr) {
+    const DropoutKey key = dropout_key(drop_p, seed, seed_dev);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
     const int nv = D >> 2, pr = row % P;
     const float4* __restrict__ xr = reinterpret_cast<const float4*>(tok + (size_t)pr * D);
     const float4* __restrict__ qr = reinterpret_cast<const float4*>(ppos + (size_t)pr * D);
-    const float inv_keep = 1.0f / (1.0f - drop_p);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);              // drop when the top 24 random bits < thr
-    float4 v[LN_MAXV];
-    float s = 0.f;
+    float4 v[LN_ROW_MAXV];
 #pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
+    for (int i = 0; i < LN_ROW_MAXV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
             float4 a = xr[c];
-            if (drop_p > 0.f) {
-                uint32_t r[4];
-                philox4x32_10((uint32_t)c, (uint32_t)row, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                a.x = (r[0] >> 8) < thr ? 0.f : a.x * inv_keep; a.y = (r[1] >> 8) < thr ? 0.f : a.y * inv_keep;
-                a.z = (r[2] >> 8) < thr ? 0.f : a.z * inv_keep; a.w = (r[3] >> 8) < thr ? 0.f : a.w * inv_keep;
-            }
+            if (drop_p > 0.f) a = dropout_apply4(key, (uint32_t)row, (uint32_t)c, a);
             const float4 b = qr[c];
             a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
             v[i] = a;
-            s += (a.x + a.y) + (a.z + a.w);
         } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float mean = wave_sum_f32(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum_f32(q) / (float)D + eps);
-    float4* __restrict__ yr = reinterpret_cast<float4*>(y + (size_t)row * D);
-    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
-    const float4* __restrict__ b4 = reinterpret_cast<const float4*>(beta);
-#pragma unroll
-    for (int i = 0; i < LN_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float4 g = g4[c], b = b4[c];
-            float4 o;
-            o.x = (v[i].x - mean) * rstd * g.x + b.x; o.y = (v[i].y - mean) * rstd * g.y + b.y;
-            o.z = (v[i].z - mean) * rstd * g.z + b.z; o.w = (v[i].w - mean) * rstd * g.w + b.w;
-            if (y) yr[c] = o;
-            if (y_hi) store_planes4(y_hi, y_lo, (size_t)row * nv + c, o);
-        }
-    }
+    const float mean = ln_row_mean<LN_ROW_MAXV>(v, lane, nv, D);
+    const float rstd = ln_row_rstd<LN_ROW_MAXV>(v, mean, lane, nv, D, eps);
+    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, nullptr, row, lane, nv);
 }
 
 extern "C" int act_prompt_layernorm_fwd_planes_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
                                                    const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, uint16_t* y_hi,
                                                    uint16_t* y_lo, act_stream_t stream) {
     if (!tok || !ppos || !gamma || !beta || !y_hi || !y_lo) return ACT_E_NULLPTR;
-    if (B < 0 || P <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_MAXV || drop_p < 0.f || drop_p >= 1.f || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
+    if (B < 0 || P <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || drop_p < 0.f || drop_p >= 1.f || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int T = B * P;
@@ -394,7 +352,7 @@ extern "C" int act_prompt_layernorm_fwd_f32(const float* tok, const float* ppos,
                                             const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, float* y,
                                             act_stream_t stream) {
     if (!tok || !ppos || !gamma || !beta || !y) return ACT_E_NULLPTR;
-    if (B < 0 || P <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
+    if (B < 0 || P <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || drop_p < 0.f || drop_p >= 1.f) return ACT_E_BADARG;
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int T = B * P;
@@ -406,26 +364,20 @@ extern "C" int act_prompt_layernorm_fwd_f32(const float* tok, const float* ppos,
 
 // Prompt rows of a TRAINED prompt layer (Stage I, models/dvae.py:485-498,556-566): y[b*P+p,:] = dropout(tok[p,:]) + ppos[p,:] for every cloud b
 // (one launch instead of expand + dropout + add), and its backward: dppos[p,:] = sum_b dy[b*P+p,:], dtok[p,:] = sum_b dy * keep / (1 - drop_p)
-// in a fixed order over b.  keep: the given 0/1 mask [B*P, D] (parity tests inject the reference's draws) or Philox keyed like
-// prompt_layernorm_fwd_kernel by (seed, row, column/4), regenerated in the backward.
+// in a fixed order over b.  keep: the given 0/1 mask [B*P, D] (parity tests inject the reference's draws) or the Philox mask of
+// prompt_layernorm_fwd_kernel (dropout.h, domain 1; no device counter here), regenerated in the backward.
 __global__ __launch_bounds__(256) void prompt_rows_fwd_kernel(const float* __restrict__ tok, const float* __restrict__ ppos,
                                                               const float* __restrict__ mask, int P, int D, float drop_p, uint64_t seed,
                                                               float* __restrict__ y, long long total4) {
     const int nv = D >> 2;
-    const float inv_keep = 1.0f / (1.0f - drop_p);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
+    const DropoutKey key = dropout_key(drop_p, seed, nullptr);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % nv); const long long row = i / nv; const int pr = (int)(row % P);
         float4 a = reinterpret_cast<const float4*>(tok + (size_t)pr * D)[c];
         if (mask) {
             const float4 m = reinterpret_cast<const float4*>(mask)[i];
-            a.x *= m.x * inv_keep; a.y *= m.y * inv_keep; a.z *= m.z * inv_keep; a.w *= m.w * inv_keep;
-        } else if (drop_p > 0.f) {
-            uint32_t r[4];
-            philox4x32_10((uint32_t)c, (uint32_t)row, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-            a.x = (r[0] >> 8) < thr ? 0.f : a.x * inv_keep; a.y = (r[1] >> 8) < thr ? 0.f : a.y * inv_keep;
-            a.z = (r[2] >> 8) < thr ? 0.f : a.z * inv_keep; a.w = (r[3] >> 8) < thr ? 0.f : a.w * inv_keep;
-        }
+            a.x *= m.x * key.inv_keep; a.y *= m.y * key.inv_keep; a.z *= m.z * key.inv_keep; a.w *= m.w * key.inv_keep;
+        } else if (drop_p > 0.f) a = dropout_apply4(key, (uint32_t)row, (uint32_t)c, a);
         const float4 b = reinterpret_cast<const float4*>(ppos + (size_t)pr * D)[c];
         a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
         reinterpret_cast<float4*>(y)[i] = a;
@@ -438,24 +390,18 @@ __global__ __launch_bounds__(256) void prompt_rows_bwd_kernel(const float* __res
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P * nv) return;
     const int c = i % nv, pr = i / nv;
-    const float inv_keep = 1.0f / (1.0f - drop_p);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);
+    const DropoutKey key = dropout_key(drop_p, seed, nullptr);
     float4 st = make_float4(0.f, 0.f, 0.f, 0.f), sp = st;
 #pragma unroll 4
     for (int b = 0; b < B; ++b) {
         const long long row = (long long)b * P + pr;
         const float4 g = reinterpret_cast<const float4*>(dy + (size_t)row * D)[c];
         sp.x += g.x; sp.y += g.y; sp.z += g.z; sp.w += g.w;
-        float4 k = make_float4(inv_keep, inv_keep, inv_keep, inv_keep);
+        float4 k = make_float4(key.inv_keep, key.inv_keep, key.inv_keep, key.inv_keep);
         if (mask) {
             const float4 m = reinterpret_cast<const float4*>(mask + (size_t)row * D)[c];
             k.x *= m.x; k.y *= m.y; k.z *= m.z; k.w *= m.w;
-        } else if (drop_p > 0.f) {
-            uint32_t r[4];
-            philox4x32_10((uint32_t)c, (uint32_t)row, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-            k.x = (r[0] >> 8) < thr ? 0.f : inv_keep; k.y = (r[1] >> 8) < thr ? 0.f : inv_keep;
-            k.z = (r[2] >> 8) < thr ? 0.f : inv_keep; k.w = (r[3] >> 8) < thr ? 0.f : inv_keep;
-        }
+        } else if (drop_p > 0.f) k = dropout_keep4(key, (uint32_t)row, (uint32_t)c);
         st.x += g.x * k.x; st.y += g.y * k.y; st.z += g.z * k.z; st.w += g.w * k.w;
     }
     reinterpret_cast<float4*>(dtok + (size_t)pr * D)[c] = st;
@@ -500,7 +446,7 @@ extern "C" int act_layernorm_bwd_f32(const float* dy, const float* xin, const fl
                                      const float* dres, float* dx, float* dgamma, float* dbeta, int accumulate_params,
                                      float* workspace, size_t workspace_bytes, int T, int D, act_stream_t stream) {
     if (!dy || !xin || !gamma || !mean || !rstd || !dx) return ACT_E_NULLPTR;
-    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_MAXV) return ACT_E_BADARG;
+    if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV) return ACT_E_BADARG;
     if (T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const int rpb = ln_rows_per_block(T); const int nblk = (T + rpb - 1) / rpb;

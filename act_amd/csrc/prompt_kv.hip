@@ -7,13 +7,13 @@
 //     base[p][n] = sum_j (v0_j - mu0) gamma_j W[n][j],   g[n] = sum_j gamma_j W[n][j],   c[n] = sum_j beta_j W[n][j] + bias[n]
 // (centred on mu0, so a large common offset of the row cancels before anything is multiplied).  base, g and c are one (P+2) x N x D product
 // (composite.hip launches it on the dense GEMM); the kernels here are
-//   1. the row pass: statistics + dropped channels of every row (mask bit for bit the one of prompt_layernorm_fwd_kernel, norm.hip) and the P+2
+//   1. the row pass: statistics + dropped channels of every row (the mask of prompt_layernorm_fwd_kernel: both call dropout.h, domain 1) and the P+2
 //      operand rows of the base product;
 //   2. the correction: one workgroup per (32-column tile of W, band of prompts) holds the tile in LDS as [j][n] and walks the dropped channels of its
 //      rows in increasing j -- no atomics, so runs are bit-identical.
-#include "common.h"
+#include "dropout.h"
+#include "ln_row.h"
 
-#define PKV_MAXV 8            // float4 per lane of a row: D <= 64*4*8 = 2048 (as LN_MAXV, norm.hip)
 #define PKV_TN 32             // columns of W per workgroup
 #define PKV_THREADS 1024
 #define PKV_LDS_BYTES (160 * 1024)
@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
                                                              int LD, float* __restrict__ rstd_out, float* __restrict__ dmu_out,
                                                              int* __restrict__ steps_out, unsigned short* __restrict__ lst,
                                                              float* __restrict__ arows) {
-    if (seed_dev) seed ^= seed_dev[0] * 0x9E3779B97F4A7C15ull;      // device-resident step counter (as prompt_layernorm_fwd_kernel)
+    const DropoutKey key = dropout_key(drop_p, seed, seed_dev);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T + P + 2) return;
     const int nv = D >> 2;
-    const float inv_keep = 1.0f / (1.0f - drop_p);
+    const float inv_keep = key.inv_keep;
     if (row >= T) {
         const int r = row - T;
         float4* __restrict__ o4 = reinterpret_cast<float4*>(arows + (size_t)r * D);
@@ -49,10 +49,9 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
         }
         const float4* __restrict__ xr = reinterpret_cast<const float4*>(tok + (size_t)r * D);
         const float4* __restrict__ qr = reinterpret_cast<const float4*>(ppos + (size_t)r * D);
-        float4 v[PKV_MAXV];
-        float s = 0.f;
+        float4 v[LN_ROW_MAXV];
 #pragma unroll
-        for (int i = 0; i < PKV_MAXV; ++i) {
+        for (int i = 0; i < LN_ROW_MAXV; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
                 float4 a = xr[c];
@@ -60,12 +59,11 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
                 if (drop_p > 0.f) { a.x = __fmul_rn(a.x, inv_keep); a.y = __fmul_rn(a.y, inv_keep); a.z = __fmul_rn(a.z, inv_keep); a.w = __fmul_rn(a.w, inv_keep); }
                 a.x = __fadd_rn(a.x, b.x); a.y = __fadd_rn(a.y, b.y); a.z = __fadd_rn(a.z, b.z); a.w = __fadd_rn(a.w, b.w);
                 v[i] = a;
-                s += (a.x + a.y) + (a.z + a.w);
             } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        const float mean0 = wave_sum_f32(s) / (float)D;
+        const float mean0 = ln_row_mean<LN_ROW_MAXV>(v, lane, nv, D);
 #pragma unroll
-        for (int i = 0; i < PKV_MAXV; ++i) {
+        for (int i = 0; i < LN_ROW_MAXV; ++i) {
             const int c = lane + 64 * i;
             if (c < nv) {
                 const float4 g = g4[c];
@@ -77,23 +75,20 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
     const int pr = row % P;
     const float4* __restrict__ xr = reinterpret_cast<const float4*>(tok + (size_t)pr * D);
     const float4* __restrict__ qr = reinterpret_cast<const float4*>(ppos + (size_t)pr * D);
-    const uint32_t thr = (uint32_t)(drop_p * 16777216.0f);              // drop when the top 24 random bits < thr
-    float4 v[PKV_MAXV];
-    float s = 0.f, ds = 0.f;
+    float4 v[LN_ROW_MAXV];
+    float s = 0.f, ds = 0.f;                                            // the row sum rides along with the dropped sum (ln_row_mean here moves the register count)
     uint32_t dm = 0;                                                    // bit 4 i + k: channel 4 (lane + 64 i) + k is dropped
 #pragma unroll
-    for (int i = 0; i < PKV_MAXV; ++i) {
+    for (int i = 0; i < LN_ROW_MAXV; ++i) {
         const int c = lane + 64 * i;
         if (c < nv) {
             float4 a = xr[c];
             if (drop_p > 0.f) {
-                uint32_t r[4];
-                philox4x32_10((uint32_t)c, (uint32_t)row, 1u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+                const Dropped4 dr = dropout_dropped4(key, (uint32_t)row, (uint32_t)c);
                 const float sx = a.x * inv_keep, sy = a.y * inv_keep, sz = a.z * inv_keep, sw = a.w * inv_keep;
-                const bool dx = (r[0] >> 8) < thr, dy = (r[1] >> 8) < thr, dz = (r[2] >> 8) < thr, dw = (r[3] >> 8) < thr;
-                a.x = dx ? 0.f : sx; a.y = dy ? 0.f : sy; a.z = dz ? 0.f : sz; a.w = dw ? 0.f : sw;
-                ds += ((dx ? sx : 0.f) + (dy ? sy : 0.f)) + ((dz ? sz : 0.f) + (dw ? sw : 0.f));
-                dm |= ((uint32_t)dx | ((uint32_t)dy << 1) | ((uint32_t)dz << 2) | ((uint32_t)dw << 3)) << (4 * i);
+                a.x = dr.x ? 0.f : sx; a.y = dr.y ? 0.f : sy; a.z = dr.z ? 0.f : sz; a.w = dr.w ? 0.f : sw;
+                ds += ((dr.x ? sx : 0.f) + (dr.y ? sy : 0.f)) + ((dr.z ? sz : 0.f) + (dr.w ? sw : 0.f));
+                dm |= ((uint32_t)dr.x | ((uint32_t)dr.y << 1) | ((uint32_t)dr.z << 2) | ((uint32_t)dr.w << 3)) << (4 * i);
             }
             const float4 b = qr[c];
             a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
@@ -102,16 +97,7 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
         } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const float mean = wave_sum_f32(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < PKV_MAXV; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nv) {
-            const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (cc * cc + d * d);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum_f32(q) / (float)D + eps);
+    const float rstd = ln_row_rstd<LN_ROW_MAXV>(v, mean, lane, nv, D, eps);
     const float dsum = wave_sum_f32(ds);
     // compact list, increasing channel: chunk i holds channels 4 (64 i + lane) + k, so the order is i, lane, k
     unsigned short* __restrict__ lr = lst + (size_t)row * LD;
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(256) void prompt_kv_rows_kernel(const float* __rest
     if (drop_p > 0.f) {
         const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
-        for (int i = 0; i < PKV_MAXV; ++i) {
+        for (int i = 0; i < LN_ROW_MAXV; ++i) {
             if (64 * i < nv) {                                         // uniform over the wave: every lane votes
                 const uint32_t bits = (dm >> (4 * i)) & 15u;
                 const unsigned long long b0 = __ballot(bits & 1u), b1 = __ballot(bits & 2u), b2 = __ballot(bits & 4u), b3 = __ballot(bits & 8u);
@@ -243,7 +229,7 @@ int cu_count() {
 }  // namespace
 
 bool act_prompt_kv_shape_ok(int B, int P, int D, int N) {
-    if (B <= 0 || P <= 0 || D <= 0 || N <= 0 || (D & 3) || D > 64 * 4 * PKV_MAXV) return false;
+    if (B <= 0 || P <= 0 || D <= 0 || N <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV) return false;
     return (size_t)(D + 1) * (PKV_TN + 1) * sizeof(float) <= (size_t)PKV_LDS_BYTES;       // the tile and one prompt's coefficients
 }
 
@@ -277,12 +263,12 @@ int act_prompt_kv_correct(const float* tok, int B, int P, int D, int N, float dr
     if (PC > fit) PC = fit;
     const size_t smem = tile_bytes + (size_t)PC * row_bytes;
     // executed work: every dropped channel of every row is one multiply-add per column (the expected count; the drawn one is within a per mille of it)
-    const double nnz = (double)T * D * (double)((uint32_t)(drop_p * 16777216.0f)) / 16777216.0;
+    const double nnz = (double)T * D * (double)dropout_thr(drop_p) / DROPOUT_THR_SCALE;
     ActProfScope ps(KID_PROMPT_KV, s, 2.0 * nnz * N, 4.0 * ((double)tiles * bands * (D + 1) * PKV_TN + (double)T * N) + 2.0 * nnz * tiles);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(prompt_kv_correct_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return (int)e;
     const int vec_store = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(kvp) | reinterpret_cast<uintptr_t>(w.base)) & 15) == 0;
     hipLaunchKernelGGL(prompt_kv_correct_kernel, dim3(tiles, bands), dim3(PKV_THREADS), smem, s, W, bias, tok, gamma, w.base, w.rstd, w.dmu, w.steps, w.lst,
-                       kvp, B, P, D, N, LD, 1.0f / (1.0f - drop_p), PC, vec_store);
+                       kvp, B, P, D, N, LD, dropout_inv_keep(drop_p), PC, vec_store);
     ACT_LAUNCH_CHECK(); return 0;
 }

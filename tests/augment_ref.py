@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from tests.philox_ref import philox4x32_10, _fold_counter
+from tests.philox_ref import philox4x32_10, _fold_counter, PHILOX_DOMAIN_AUGMENT
 
 SCALE, TRANSLATE, SCALE_TRANSLATE, ROTATE_Y, JITTER, DROPOUT, FLIP = 1, 2, 3, 4, 5, 6, 7
 F = np.float32
@@ -23,8 +23,8 @@ def _u01(words):
 def _words(slot, cloud, pos, sub, seed, ctr, log=None):
     slot, cloud = np.broadcast_arrays(np.asarray(slot), np.asarray(cloud))
     if log is not None:
-        log.extend((int(s), int(c), 3, pos + 8 * sub) for s, c in zip(slot.ravel(), cloud.ravel()))
-    return philox4x32_10(slot, cloud, 3, pos + 8 * sub, _fold_counter(seed, ctr))
+        log.extend((int(s), int(c), PHILOX_DOMAIN_AUGMENT, pos + 8 * sub) for s, c in zip(slot.ravel(), cloud.ravel()))
+    return philox4x32_10(slot, cloud, PHILOX_DOMAIN_AUGMENT, pos + 8 * sub, _fold_counter(seed, ctr))
 
 
 def philox_draws(ops, B, N, seed, ctr=None, log=None):
