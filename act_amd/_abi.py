@@ -10,6 +10,7 @@ import ctypes
 
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _u, _u64, _ll, _str = ctypes.c_uint, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_char_p
+_d = ctypes.c_double
 _P = ctypes.POINTER
 
 
@@ -240,6 +241,10 @@ _TABLE = {
     "act_scene_gather": [_vp, _ll, _vp, _vp, _vp, _vp, _i, _ll, _vp, _vp],
     "act_scene_vote": [_vp, _vp, _ll, _ll, _i, _vp, _vp, _vp, _vp],
     "act_scene_finish": [_vp, _vp, _ll, _i, _vp, _vp, _vp],
+    # S3DIS training blocks from resident rooms (csrc/s3dis_sample.hip)
+    "act_s3dis_sample_workspace": (_sz, [_i, _ll]),
+    "act_s3dis_sample_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _ll, _vp, _vp, _vp, _i, _i, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _sz, _vp],
     # Stage-I reconstruction evaluation (csrc/recon_eval.hip)
     "act_recon_eval_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _vp],
     # linear-SVM validation of pretrained features (csrc/svm.hip)

@@ -8,6 +8,7 @@
 // order by construction (per-tile counts, scans, ordered writes); no atomics decide an order.  Votes and confusion counts are integer atomics,
 // which are exact and order-independent.  Built with -ffp-contract=off.
 #include "common.h"
+#include "ws_hash.h"
 
 #define WS_C_MAX 64                 // classes per row (vote / finish)
 #define WS_TILE_MIN 1024            // points per membership tile (one wave walks its tile in chunks of 64)
@@ -174,34 +175,8 @@ extern "C" int act_scene_member_fill(const double* xyz, long long P, const doubl
 }
 
 // ---- keyed row-index build ------------------------------------------------------------------------------------------
-// lowbias32 mixer; every key and draw below is a function of (seed, room, vote, block, position) only.
-__host__ __device__ __forceinline__ uint32_t ws_mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// keyed bijection of [0, n): a 4-round balanced Feistel network on the smallest even bit width >= max(2, ceil(log2 n)), cycle-walked back into
-// [0, n) (the walk ends: a permutation of the wider domain returns to [0, n) within its cycle).
-__device__ __forceinline__ uint32_t ws_feistel(uint32_t x, uint32_t n, uint32_t key) {
-    if (n <= 1) return 0;
-    int bits = 32 - __clz(n - 1);
-    if (bits < 2) bits = 2;
-    bits += bits & 1;
-    const int h = bits >> 1;
-    const uint32_t mask = (1u << h) - 1u;
-    do {
-        uint32_t L = x >> h, R = x & mask;
-        for (uint32_t i = 0; i < 4; ++i) {
-            const uint32_t F = ws_mix32(R ^ ws_mix32(key + i * 0x9e3779b9u)) & mask;
-            const uint32_t nl = R;
-            R = L ^ F;
-            L = nl;
-        }
-        x = (L << h) | R;
-    } while (x >= n);
-    return x;
-}
-
+// ws_mix32 (lowbias32 mixer) and ws_feistel (keyed bijection of [0, n)) live in ws_hash.h; every key and draw below is a function of
+// (seed, room, vote, block, position) only.
 // rows [R] (blocks back to back, block s at [roff[s], roff[s+1]), point_size = roff[s+1] - roff[s]): position j of block s holds
 // pre[perm(j)], pre = the block's members followed by pad = point_size - cnt fills.  Fills: the first pad outputs of a keyed bijection of
 // [0, cnt) when pad <= cnt (without replacement, dataset.py's rule), else hi32(h * cnt) of a 32-bit hash h per fill (with replacement; each

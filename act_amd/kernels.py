@@ -1681,6 +1681,67 @@ def scene_finish(votes, label, cm=None):
     return pred, cm
 
 
+# ---- S3DIS training blocks from resident rooms (csrc/s3dis_sample.hip) ------------------------------------------------------------------------
+_S3DIS_INDEX = (("xyz", torch.float64, 2), ("labels", torch.int32, 1), ("room_off", torch.int64, 1), ("grid_origin", torch.float64, 2),
+                ("grid_dims", torch.int64, 2), ("cell_off", torch.int64, 1), ("cell_pts", torch.int32, 1))
+
+
+def s3dis_sample_workspace(index, B):
+    """int32 workspace of a batch of B items: B * max_window member slots"""
+    n = lib.act_s3dis_sample_workspace(int(B), int(index.max_window))
+    return torch.empty((n + 3) // 4, dtype=torch.int32, device=index.xyz.device)
+
+
+def s3dis_sample(index, room_ids, item_ids, num_point, seed, epoch, center_idx=None, ws=None, validate=True):
+    """one launch: a block of ``num_point`` points for every item (room_ids / item_ids int32 [B] on the device) from the resident rooms of
+    ``index`` (act_amd.datasets.S3DISDevice.build_index) -> (xyz float32 [B,num_point,3], labels int64 [B,num_point], rows int32 [B,num_point],
+    count, center_idx, info int32 [B]).  ``center_idx`` int32 [B] fixes every item's centre point (one attempt, accepted whatever its count).
+    Bad arguments raise ValueError; ``validate`` also reads the ids back (one host synchronisation) and refuses a room id or a centre out of range."""
+    for name, dtype, dim in _S3DIS_INDEX:
+        t = getattr(index, name)
+        if t.dtype != dtype or t.dim() != dim:
+            raise ValueError(f"s3dis_sample: index.{name} must be {dtype} with {dim} dimension(s), got {t.dtype} {tuple(t.shape)}")
+    R, dev = int(index.room_off.numel()) - 1, index.xyz.device
+    if R <= 0 or index.xyz.shape[1] != 3 or index.labels.numel() != index.xyz.shape[0] or index.cell_pts.numel() != index.xyz.shape[0] or \
+            tuple(index.grid_origin.shape) != (R, 2) or tuple(index.grid_dims.shape) != (R, 3):
+        raise ValueError("s3dis_sample: the index's tensors do not describe one set of rooms")
+    if int(num_point) <= 0:
+        raise ValueError(f"s3dis_sample: num_point must be positive, got {num_point}")
+    if not (index.block_size > 0 and index.cell > 0 and index.min_points >= 0 and 0 < index.max_tries <= 65536 and index.max_window > 0):
+        raise ValueError("s3dis_sample: block_size, cell, max_tries and max_window must be positive (max_tries <= 65536), min_points >= 0")
+    ids = [("room_ids", room_ids), ("item_ids", item_ids)] + ([("center_idx", center_idx)] if center_idx is not None else [])
+    for name, t in ids:
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or t.device != dev:
+            raise ValueError(f"s3dis_sample: {name} must be an int32 [B] tensor on {dev}")
+    B = int(room_ids.numel())
+    if B == 0 or any(t.numel() != B for _, t in ids):
+        raise ValueError("s3dis_sample: room_ids, item_ids and center_idx must have one entry per item (B > 0)")
+    if validate:
+        if int(room_ids.min()) < 0 or int(room_ids.max()) >= R:
+            raise ValueError(f"s3dis_sample: room id outside [0, {R})")
+        if center_idx is not None:
+            size = (index.room_off[1:] - index.room_off[:-1])[room_ids.long()]
+            if bool(((center_idx < 0) | (center_idx >= size)).any()):
+                raise ValueError("s3dis_sample: center_idx outside its room")
+    if ws is None:
+        ws = s3dis_sample_workspace(index, B)
+    need = lib.act_s3dis_sample_workspace(B, int(index.max_window))
+    if ws.dtype != torch.int32 or ws.device != dev or ws.numel() * 4 < need:
+        raise ValueError(f"s3dis_sample: the workspace must be int32 on {dev} with at least {need} bytes")
+    room_ids, item_ids = room_ids.contiguous(), item_ids.contiguous()
+    center_idx = center_idx.contiguous() if center_idx is not None else None
+    xyz = torch.empty(B, num_point, 3, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, num_point, dtype=torch.int64, device=dev)
+    rows = torch.empty(B, num_point, dtype=torch.int32, device=dev)
+    count, center, info = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    check(lib.act_s3dis_sample_f32(ptr(index.xyz), ptr(index.labels), ptr(index.room_off), R, ptr(index.grid_origin), ptr(index.grid_dims),
+                                   ptr(index.cell_off), ptr(index.cell_pts), float(index.block_size), float(index.cell), int(index.min_points),
+                                   int(index.max_tries), int(index.max_window), ptr(room_ids), ptr(item_ids), ptr(center_idx), B, int(num_point),
+                                   int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, ptr(xyz), ptr(labels), ptr(rows), ptr(count), ptr(center),
+                                   ptr(info), ptr(ws), ws.numel() * 4, stream()), "act_s3dis_sample_f32")
+    return xyz, labels, rows, count, center, info
+
+
 # ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip): four Chamfer losses, CDL1 / CDL2 with ignore_zeros, F-Score counts, one row per cloud ----
 RECON_FIELDS = 12
 (RECON_SPARSE_L1, RECON_SPARSE_L2, RECON_DENSE_L1, RECON_DENSE_L2, RECON_CDL1, RECON_CDL2, RECON_PRECISION_HITS, RECON_RECALL_HITS, RECON_FSCORE,

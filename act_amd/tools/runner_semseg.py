@@ -4,7 +4,9 @@
     python -m act_amd.tools.runner_semseg --synthetic --max_steps 150
 
 Same arguments and defaults as the reference, plus ``--synthetic`` (generated rooms, act_amd.datasets.S3DISDataset.SyntheticS3DIS), ``--max_steps``
-(stop training after that many steps, then evaluate once), ``--log_every``, ``--seed`` and ``--eval_batches``.  Per step, like the reference:
+(stop training after that many steps, then evaluate once), ``--log_every``, ``--seed``, ``--eval_batches`` and ``--device_sampler`` (blocks sampled
+on the device from resident rooms, act_amd.datasets.S3DISDevice, in place of the two DataLoaders; its draws are keyed hashes, not
+np.random's).  Per step, like the reference:
 isotropic scale U[0.8, 1.25] and shift U[-0.1, 0.1]^3 per cloud (here one launch on the device), the weighted NLL with the train split's
 labelweights, ``optimizer.step()``, gradient clipping at 10, a second ``optimizer.step()``, ``zero_grad`` (main.py:209-223).  No host
 synchronisation per step: loss and correct counts accumulate on the device and are read once per ``--log_every`` steps.  Evaluation accumulates
@@ -47,6 +49,7 @@ def parse_args(argv=None):
     p.add_argument('--eval_batches', type=int, default=0, help='evaluate on at most this many test batches (0: all)')
     p.add_argument('--seed', type=int, default=0)
     p.add_argument('--num_workers', type=int, default=4)
+    p.add_argument('--device_sampler', action='store_true', default=False, help='sample the blocks on the device from resident rooms')
     return p.parse_args(argv)
 
 
@@ -97,6 +100,16 @@ def datasets(args):
             S3DISDataset('test', args.root, args.npoint, args.test_area, rng=np.random.default_rng(args.seed + 1)))
 
 
+class _EpochLoader:
+    """one epoch of a DeviceS3DISBlocks as an iterable of (pts, target) on the device: what ``evaluate`` takes in place of a DataLoader"""
+
+    def __init__(self, blocks, batch_size, seed, shuffle, drop_last, epoch=0):
+        self.blocks, self.batch_size, self.seed, self.shuffle, self.drop_last, self.epoch = blocks, batch_size, seed, shuffle, drop_last, epoch
+
+    def __iter__(self):
+        return self.blocks.epoch(self.batch_size, self.epoch, self.seed, self.shuffle, self.drop_last)
+
+
 @torch.no_grad()
 def evaluate(model, loader, weights, device, max_batches=0):
     """-> (metrics dict, mean loss); one host read of the confusion matrix and the loss sum"""
@@ -108,8 +121,10 @@ def evaluate(model, loader, weights, device, max_batches=0):
     for i, (pts, target) in enumerate(loader):
         if max_batches and i >= max_batches:
             break
-        pts = pts.to(device, torch.float32, non_blocking=True)
-        target = target.to(device, torch.int64, non_blocking=True).reshape(-1)
+        if pts.device != device:
+            pts = pts.to(device, torch.float32, non_blocking=True)
+            target = target.to(device, torch.int64, non_blocking=True)
+        target = target.reshape(-1)
         logp = model(pts.transpose(2, 1))
         loss_sum += crit(logp, target, weights)
         K.confusion(logp.reshape(-1, NUM_CLASSES), target, NUM_CLASSES, out=cm)
@@ -123,12 +138,20 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     device = torch.device('cuda', torch.cuda.current_device())
     train_set, test_set = datasets(args)
-    g = torch.Generator().manual_seed(args.seed)
-    train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=True,
-                                               generator=g, pin_memory=True, persistent_workers=args.num_workers > 0,
-                                               worker_init_fn=_seed_worker)
-    test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers,
-                                              generator=torch.Generator().manual_seed(args.seed + 1), worker_init_fn=_seed_worker)
+    if args.device_sampler:
+        from ..datasets.S3DISDevice import DeviceS3DISBlocks
+        train_blocks, test_blocks = DeviceS3DISBlocks.from_dataset(train_set, device), DeviceS3DISBlocks.from_dataset(test_set, device)
+        room_bytes, index_bytes = (sum(v) for v in zip(train_blocks.resident_bytes(), test_blocks.resident_bytes()))
+        print(f"device sampler: rooms {room_bytes} bytes, index {index_bytes} bytes", flush=True)
+        train_loader = None
+        test_loader = _EpochLoader(test_blocks, args.batch_size, args.seed + 1, shuffle=False, drop_last=False)
+    else:
+        g = torch.Generator().manual_seed(args.seed)
+        train_loader = torch.utils.data.DataLoader(train_set, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers, drop_last=True,
+                                                   generator=g, pin_memory=True, persistent_workers=args.num_workers > 0,
+                                                   worker_init_fn=_seed_worker)
+        test_loader = torch.utils.data.DataLoader(test_set, batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers,
+                                                  generator=torch.Generator().manual_seed(args.seed + 1), worker_init_fn=_seed_worker)
     weights = torch.tensor(np.asarray(train_set.labelweights, dtype=np.float32), device=device)
     print(f"train samples {len(train_set)}, test samples {len(test_set)}, labelweights {np.round(train_set.labelweights, 3).tolist()}", flush=True)
 
@@ -151,9 +174,11 @@ def main(argv=None):
     model.zero_grad(set_to_none=True)
     for epoch in range(args.epoch):
         model.train()
-        for pts, target in train_loader:
-            pts = pts.to(device, torch.float32, non_blocking=True).contiguous()
-            target = target.to(device, torch.int64, non_blocking=True).reshape(-1)
+        for pts, target in (train_blocks.epoch(args.batch_size, epoch, args.seed) if args.device_sampler else train_loader):
+            if not args.device_sampler:
+                pts = pts.to(device, torch.float32, non_blocking=True).contiguous()
+                target = target.to(device, torch.int64, non_blocking=True)
+            target = target.reshape(-1)
             B = pts.shape[0]
             scale = torch.empty(B, 1, device=device).uniform_(0.8, 1.25).expand(B, 3)       # isotropic (provider.random_scale_point_cloud)
             augment(pts, scale=scale)
@@ -177,6 +202,8 @@ def main(argv=None):
                 done = True
                 break
         scheduler.step(epoch)                                             # main.py: after the epoch, with its index
+        if args.device_sampler:
+            test_loader.epoch = epoch
         m, eval_loss = evaluate(model, test_loader, weights, device, args.eval_batches)
         print(f"eval epoch {epoch}: loss {eval_loss:.4f} OA {100 * m['oa']:.2f} mAcc {100 * m['macc']:.2f} mIoU {100 * m['miou']:.2f}", flush=True)
         print("IoU " + " ".join(f"{c}:{100 * v:.1f}" for c, v in zip(CLASSES, m['iou'])), flush=True)

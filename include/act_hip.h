@@ -697,6 +697,25 @@ int act_scene_vote(const float* logp, const int32_t* rows, long long n, long lon
  * outside [0,C) skipped.  C <= 64. */
 int act_scene_finish(const int32_t* votes, const int32_t* label, long long P, int C, int32_t* pred, int64_t* cm, act_stream_t stream);
 
+/* ---- S3DIS training blocks from resident rooms (csrc/s3dis_sample.hip) -----------------------------------------------------------------
+ * semantic_segmentation/dataset.py:119-147, one launch per batch, one workgroup per item.  Rooms back to back: xyz float64 [P_total,3], labels
+ * int32 [P_total], room_off int64 [R+1].  Grid of room r: origin grid_origin[r] = (min x, min y), square cells of side `cell`, grid_dims[r] =
+ * (gx, gy, first cell of the room in cell_off); cell iy*gx + ix; cell_off int64 [cells + 1] offsets into cell_pts int32 [P_total] (point index
+ * within the room, ascending inside a cell).  Item b: room room_ids[b], draws keyed by (seed, epoch, item_ids[b], attempt).  Attempt t takes a
+ * point of the room as centre; members: cx - block_size/2 <= x <= cx + block_size/2, the same in y (float64, inclusive).  The first attempt with
+ * count > min_points is taken; after max_tries (<= 65536) the largest count (earliest on ties) and info = -max_tries, else info = attempts used.
+ * center_in (may be NULL) fixes the centre point of every item: one attempt, accepted whatever its count.  count >= num_point: num_point distinct
+ * members in random order (keyed bijection); else with replacement.  out_xyz float32 [B,num_point,3] = (x - cx, y - cy, z) in float64 rounded
+ * once, out_labels int64 [B,num_point], rows int32 [B,num_point] (point index within the room), count / center_idx / info int32 [B].  ws:
+ * act_s3dis_sample_workspace(B, max_window) bytes, max_window >= the points of any window of overlapped cells.  An item whose room id or
+ * injected centre is out of range reads nothing: rows -1, labels -1, xyz NaN, count 0, info 0. */
+size_t act_s3dis_sample_workspace(int B, long long max_window);
+int act_s3dis_sample_f32(const double* xyz, const int32_t* labels, const long long* room_off, int R, const double* grid_origin,
+                         const long long* grid_dims, const long long* cell_off, const int32_t* cell_pts, double block_size, double cell,
+                         int min_points, int max_tries, long long max_window, const int32_t* room_ids, const int32_t* item_ids,
+                         const int32_t* center_in, int B, int num_point, unsigned seed, unsigned epoch, float* out_xyz, int64_t* out_labels,
+                         int32_t* rows, int32_t* count, int32_t* center_idx, int32_t* info, void* ws, size_t ws_bytes, act_stream_t stream);
+
 /* ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip) ------------------------------------------------------------------------
  * tools/runner_autoencoder.py:219-323 (validate) with utils/metrics.py, one launch per batch, one workgroup per cloud: coarse [B,nc,3],
  * dense [B,nd,3], gt [B,N,3] -> row row0 + b of out (float64 [num_rows, ACT_RECON_FIELDS]):
