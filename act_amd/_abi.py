@@ -245,6 +245,9 @@ _TABLE = {
     "act_s3dis_sample_workspace": (_sz, [_i, _ll]),
     "act_s3dis_sample_f32": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _d, _i, _i, _ll, _vp, _vp, _vp, _i, _i, _u, _u, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _sz, _vp],
+    # object-dataset batches from a resident split (csrc/cloud_sample.hip)
+    "act_cloud_sample_max_points": [],
+    "act_cloud_sample_f32": [_vp, _ll, _i, _i, _vp, _vp, _i, _i, _u, _u, _i, _vp, _vp, _vp],
     # Stage-I reconstruction evaluation (csrc/recon_eval.hip)
     "act_recon_eval_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _i, _vp],
     # linear-SVM validation of pretrained features (csrc/svm.hip)

@@ -1,4 +1,4 @@
-// ws_hash.h -- the keyed draws of the S3DIS kernels (wholescene.hip, s3dis_sample.hip): one 32-bit mixer and one keyed bijection.
+// ws_hash.h -- the keyed draws of the sampling kernels (wholescene.hip, s3dis_sample.hip, cloud_sample.hip): one 32-bit mixer and one keyed bijection.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

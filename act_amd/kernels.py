@@ -1742,6 +1742,44 @@ def s3dis_sample(index, room_ids, item_ids, num_point, seed, epoch, center_idx=N
     return xyz, labels, rows, count, center, info
 
 
+# ---- object-dataset batches from a resident split (csrc/cloud_sample.hip) ----------------------------------------------------------------------
+CLOUD_PERMUTE, CLOUD_NORMALIZE = 1, 2
+
+
+def cloud_sample(clouds, item_ids, draw_ids, n, seed, epoch, permute=True, normalize=True, want_rows=False, validate=True):
+    """one launch: out float32 [B,n,C] from the resident ``clouds`` float32 [M,N,C] (C = 3 or 6, xyz first).  Item b reads cloud item_ids[b]
+    with draws keyed by (seed, epoch, draw_ids[b]) (both int32 [B] on the device).  ``permute``: n distinct rows in random order (else rows
+    0 .. n-1); ``normalize``: numpy's pc_norm of xyz, bit for bit.  ``want_rows`` -> (out, src_rows int32 [B,n]).  Bad arguments raise ValueError;
+    ``validate`` also reads the item ids back (one host synchronisation) and refuses one outside [0, M)."""
+    if not torch.is_tensor(clouds) or not clouds.is_cuda or clouds.dtype != torch.float32 or clouds.dim() != 3:
+        raise ValueError("cloud_sample: clouds must be a float32 [M,N,C] tensor on the GPU")
+    M, N, C = clouds.shape
+    dev = clouds.device
+    if C not in (3, 6) or M < 1 or N < 1:
+        raise ValueError(f"cloud_sample: clouds must be [M,N,3] or [M,N,6] with M, N > 0, got {tuple(clouds.shape)}")
+    n = int(n)
+    if n < 1 or n > N or n > lib.act_cloud_sample_max_points():
+        raise ValueError(f"cloud_sample: n must be in [1, min(N, {lib.act_cloud_sample_max_points()})], got n = {n} with N = {N}")
+    for name, t in (("item_ids", item_ids), ("draw_ids", draw_ids)):
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or t.device != dev:
+            raise ValueError(f"cloud_sample: {name} must be an int32 [B] tensor on {dev}")
+    B = int(item_ids.numel())
+    if B < 1 or draw_ids.numel() != B:
+        raise ValueError("cloud_sample: item_ids and draw_ids must have one entry per item (B > 0)")
+    if validate and (int(item_ids.min()) < 0 or int(item_ids.max()) >= M):
+        raise ValueError(f"cloud_sample: item id outside [0, {M})")
+    clouds, item_ids, draw_ids = clouds.contiguous(), item_ids.contiguous(), draw_ids.contiguous()
+    out = torch.empty(B, n, C, dtype=torch.float32, device=dev)
+    rows = torch.empty(B, n, dtype=torch.int32, device=dev) if want_rows else None
+    flags = (CLOUD_PERMUTE if permute else 0) | (CLOUD_NORMALIZE if normalize else 0)
+    rc = lib.act_cloud_sample_f32(ptr(clouds), M, N, C, ptr(item_ids), ptr(draw_ids), B, n, int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF, flags,
+                                  ptr(out), ptr(rows), stream())
+    if rc == -1:
+        raise ValueError("cloud_sample: act_cloud_sample_f32 refused the shape")
+    check(rc, "act_cloud_sample_f32")
+    return (out, rows) if want_rows else out
+
+
 # ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip): four Chamfer losses, CDL1 / CDL2 with ignore_zeros, F-Score counts, one row per cloud ----
 RECON_FIELDS = 12
 (RECON_SPARSE_L1, RECON_SPARSE_L2, RECON_DENSE_L1, RECON_DENSE_L2, RECON_CDL1, RECON_CDL2, RECON_PRECISION_HITS, RECON_RECALL_HITS, RECON_FSCORE,

@@ -14,9 +14,24 @@ from ..utils.misc import worker_init_fn
 def dataset_builder(args, config):
     """(sampler, DataLoader) of one dataset section of the YAML (tools/builder.py:14-33): the train subset is shuffled and drops its
     ragged last batch; under DDP every rank gets a DistributedSampler shard.  Host batches are pinned so the H2D copy of the next
-    batch overlaps the current step."""
+    batch overlaps the current step.
+
+    ``others.device_resident: True`` (opt-in) keeps the split on the device instead and returns (loader, loader), a
+    datasets.DeviceClouds.DeviceCloudLoader: every batch is one launch of csrc/cloud_sample.hip, ``set_epoch`` is the sampler's, ``num_workers``
+    is not used.  ``others.device_cache`` names the packed .npy file of a file-backed ShapeNet; ``args.seed`` (default 0) keys the draws."""
     dataset = build_dataset_from_cfg(config._base_, config.others)
     is_train = config.others.subset == 'train'
+    if config.others.get('device_resident', False):
+        from ..datasets.DeviceClouds import DeviceClouds, DeviceCloudLoader
+        rank, world = 0, 1
+        if args.distributed:                            # args.rank / args.world_size where the launcher set them, else the process group's
+            rank = args.rank if hasattr(args, 'rank') else torch.distributed.get_rank()
+            world = args.world_size if hasattr(args, 'world_size') else torch.distributed.get_world_size()
+        device = torch.device('cuda', getattr(args, 'local_rank', 0) % max(1, torch.cuda.device_count()))
+        clouds = DeviceClouds.from_dataset(dataset, device=device, cache=config.others.get('device_cache'))
+        loader = DeviceCloudLoader(clouds, config.others.bs, shuffle=is_train, drop_last=is_train, seed=getattr(args, 'seed', 0) or 0,
+                                   rank=rank, world_size=world)
+        return loader, loader
     sampler = torch.utils.data.distributed.DistributedSampler(dataset, shuffle=is_train) if args.distributed else None
     loader = torch.utils.data.DataLoader(
         dataset, batch_size=config.others.bs, sampler=sampler, shuffle=(is_train and sampler is None), drop_last=is_train,

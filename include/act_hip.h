@@ -716,6 +716,20 @@ int act_s3dis_sample_f32(const double* xyz, const int32_t* labels, const long lo
                          const int32_t* center_in, int B, int num_point, unsigned seed, unsigned epoch, float* out_xyz, int64_t* out_labels,
                          int32_t* rows, int32_t* count, int32_t* center_idx, int32_t* info, void* ws, size_t ws_bytes, act_stream_t stream);
 
+/* ---- Object-dataset batches from a resident split (csrc/cloud_sample.hip) ---------------------------------------------------------------
+ * datasets/ShapeNet55Dataset.py:35-51, datasets/ModelNetDataset.py:120-140, one launch per batch, one workgroup per item.  clouds float32
+ * [M,N,C], C = 3 or 6, xyz first.  Item b reads cloud item_ids[b]; its draws are keyed by (seed, epoch, draw_ids[b]) alone.  With
+ * ACT_CLOUD_PERMUTE position j < n takes source row ws_feistel(j, N, key): n distinct rows in random order (a full permutation at n == N);
+ * without it row j.  With ACT_CLOUD_NORMALIZE xyz gets numpy's pc_norm in numpy's order: per coordinate the fp32 sum over j ascending, divided
+ * by (float)n and subtracted; m = max_j sqrtf((x*x + y*y) + z*z); every coordinate / m (m == 0: NaN, as numpy).  Channels 3..5 are copied.
+ * out float32 [B,n,C]; src_rows int32 [B,n] (may be NULL) receives the source rows.  ACT_E_BADARG for B < 1, M < 1, n < 1, n > N,
+ * n > act_cloud_sample_max_points(), C not 3 or 6, an unknown flag.  An item id outside [0,M) reads nothing: out NaN, src_rows -1. */
+#define ACT_CLOUD_PERMUTE   1
+#define ACT_CLOUD_NORMALIZE 2
+int act_cloud_sample_max_points(void);
+int act_cloud_sample_f32(const float* clouds, long long M, int N, int C, const int32_t* item_ids, const int32_t* draw_ids, int B, int n,
+                         unsigned seed, unsigned epoch, int flags, float* out, int32_t* src_rows, act_stream_t stream);
+
 /* ---- Stage-I reconstruction evaluation (csrc/recon_eval.hip) ------------------------------------------------------------------------
  * tools/runner_autoencoder.py:219-323 (validate) with utils/metrics.py, one launch per batch, one workgroup per cloud: coarse [B,nc,3],
  * dense [B,nd,3], gt [B,N,3] -> row row0 + b of out (float64 [num_rows, ACT_RECON_FIELDS]):
