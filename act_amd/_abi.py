@@ -289,6 +289,8 @@ _TABLE = {
     "act_emd_fwd_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp],
     "act_emd_fwd_ex_f32": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "act_emd_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
+    "act_emd_wave_max_points": [],
+    "act_emd_wave_fwd_f32": [_vp, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp, _vp, _vp],
     # PointNet++ set abstraction (csrc/sa.hip)
     "act_ball_query_f32": [_vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp],
     "act_group_rows_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],

@@ -18,6 +18,7 @@
 #include "common.h"
 
 #define EMD_MAX_POINTS 3072
+#define EMD_WAVE_MAX_POINTS 64                       // emd_wave_kernel: one object per lane
 #define EMD_THETA 4.0f
 #define EMD_HDR 16                                   // bytes: cnt[2], max-distance bits, pad
 #define EMD_BYTES_PER_POINT 52
@@ -152,6 +153,99 @@ __global__ __launch_bounds__(1024) void emd_auction_kernel(const float* __restri
     }
 }
 
+// ---- one wave per pair (N <= 64): the Stage-I loss regime, thousands of group patches of 32 points --------------------------------------------
+// Lane j < N holds object j (xyz2[j], price[j], owner[j]) and, as lane i, the coordinates of bidder i; everything lives in registers: no LDS is
+// allocated, there is no barrier and no atomic (the cross-lane traffic is DPP, readlane and, once at the end, a bpermute).  Lanes >= N hold
+// price = +inf, so their value d + price is +inf and they never win.  Gauss-Seidel: ONE bid at a time, by the lowest unassigned bidder.  The set
+// of unassigned bidders is what a ballot over assign[i] < 0 would return; it is kept as that 64-bit mask in scalar registers and updated with
+// the (wave-uniform) bidder and evicted owner, so the bidder index is uniform and its coordinates are three readlanes.
+// Costs and values are rounded exactly as in emd_auction_kernel (sqdist3, one __fadd_rn): tests/emd_wave_ref.py restates the solve bit for bit.
+__global__ __launch_bounds__(256) void emd_wave_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2, int B, int N,
+                                                       float eps_final, float eps_rel, int max_bids, float* __restrict__ dist,
+                                                       int32_t* __restrict__ assignment, int32_t* __restrict__ info,
+                                                       float* __restrict__ eps_used_out) {
+    const int lane = threadIdx.x & 63;
+    const long long pair = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (pair >= B) return;                                                   // wave-uniform: the ragged last workgroup
+    const size_t base = (size_t)pair * N;
+    const float INF = __builtin_inff();
+    const bool valid = lane < N;
+
+    float ax = 0.f, ay = 0.f, az = 0.f, bx = 0.f, by = 0.f, bz = 0.f;
+    if (valid) {
+        const float* p = xyz1 + (base + lane) * 3; ax = p[0]; ay = p[1]; az = p[2];
+        const float* q = xyz2 + (base + lane) * 3; bx = q[0]; by = q[1]; bz = q[2];
+    }
+    float price = valid ? 0.f : INF;
+
+    // max_ij d_ij (exact, any order); NaN costs are dropped by fmaxf as in emd_auction_kernel
+    float dmax = 0.f;
+    for (int i = 0; i < N; ++i) {
+        const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), i));
+        const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), i));
+        const float z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az), i));
+        dmax = fmaxf(dmax, sqdist3(x, y, z, bx, by, bz));
+    }
+    dmax = wave_max_f32(valid ? dmax : 0.f, -1.f);
+    const float eps_used = fmaxf(eps_final, __fmul_rn(eps_rel, dmax));
+    float eps = eps_used;
+    {
+        const float first = dmax * 0.25f;
+        for (int k = 0; k < 64 && eps < first; ++k) eps *= EMD_THETA;
+    }
+
+    const emd_u64 all = N >= 64 ? ~0ull : ((1ull << N) - 1ull);
+    emd_u64 un = all;                                                        // bit i: bidder i is unassigned
+    int owner = -1, bids = 0;
+    bool capped = false;
+    for (;;) {                                                               // one phase: everything unassigned, prices kept
+        un = all; owner = -1;
+        while (un) {
+            if (bids >= max_bids) { capped = true; break; }
+            ++bids;
+            const int i = first_lane(un);
+            const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), i));
+            const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), i));
+            const float z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az), i));
+            const float u = __fadd_rn(sqdist3(x, y, z, bx, by, bz), price);  // lanes >= N: +inf
+            const float m1 = wave_min_f32(u, INF);
+            const emd_u64 eq = __ballot(valid && u == m1);
+            const int jb = eq ? first_lane(eq) : 0;                          // nothing compares equal (NaN coordinates): any object, the cap ends it
+            const float m2 = wave_min_f32(lane == jb ? INF : u, INF);        // best of everything else; +inf when N == 1
+            const float p = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(price), jb));
+            float bid = m2 < INF ? __fadd_rn(__fadd_rn(p, __fsub_rn(m2, m1)), eps) : __fadd_rn(p, eps);
+            if (!(bid > p)) bid = __int_as_float(__float_as_int(p) + 1);     // eps below half an ulp of the price: still strictly up
+            const int prev = __builtin_amdgcn_readlane(owner, jb);
+            price = lane == jb ? bid : price;
+            owner = lane == jb ? i : owner;
+            un &= ~(1ull << i);
+            if (prev >= 0) un |= 1ull << prev;
+        }
+        if (capped || !(eps > eps_used)) break;
+        eps = fmaxf(eps / EMD_THETA, eps_used);
+    }
+
+    if (capped) {                                                            // unassigned bidders take the free objects, both ascending
+        emd_u64 fr = all & ~__ballot(owner >= 0);
+        while (un && fr) {
+            const int i = first_lane(un), j = first_lane(fr);
+            owner = lane == j ? i : owner;
+            un &= un - 1; fr &= fr - 1;
+        }
+    }
+    // object lane j writes the row of its owner: dist[owner] = d(owner, j), assignment[owner] = j (owner is a bijection here)
+    const int src = (unsigned)owner < (unsigned)N ? owner : 0;
+    const float ox = __shfl(ax, src, 64), oy = __shfl(ay, src, 64), oz = __shfl(az, src, 64);
+    if (valid && (unsigned)owner < (unsigned)N) {
+        assignment[base + owner] = lane;
+        dist[base + owner] = sqdist3(ox, oy, oz, bx, by, bz);
+    }
+    if (lane == 0) {
+        info[pair] = capped ? -bids : bids;
+        if (eps_used_out) eps_used_out[pair] = eps_used;
+    }
+}
+
 __global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ xyz1, const float* __restrict__ xyz2,
                                                       const int32_t* __restrict__ assignment, const float* __restrict__ g, long long total,
                                                       int N, float* __restrict__ gx1, float* __restrict__ gx2) {
@@ -193,6 +287,22 @@ extern "C" int act_emd_fwd_ex_f32(const float* xyz1, const float* xyz2, int B, i
 extern "C" int act_emd_fwd_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, int max_rounds, float* dist,
                                int32_t* assignment, int32_t* info, act_stream_t stream) {
     return act_emd_fwd_ex_f32(xyz1, xyz2, B, N, eps_final, max_rounds, dist, assignment, info, nullptr, stream);
+}
+
+extern "C" int act_emd_wave_max_points(void) { return EMD_WAVE_MAX_POINTS; }
+
+extern "C" int act_emd_wave_fwd_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, float eps_rel, int max_bids,
+                                    float* dist, int32_t* assignment, int32_t* info, float* eps_used, act_stream_t stream) {
+    if (B == 0) return 0;
+    if (!xyz1 || !xyz2 || !dist || !assignment || !info) return ACT_E_NULLPTR;
+    if (B < 0 || N <= 0 || N > EMD_WAVE_MAX_POINTS || !(eps_final > 0.f) || __builtin_isinf(eps_final) || !(eps_rel >= 0.f) ||
+        __builtin_isinf(eps_rel) || max_bids < 1) return ACT_E_BADARG;
+    const long long blocks = ((long long)B + 3) / 4;                         // four waves, four pairs, per workgroup
+    if (blocks > 0x7fffffffLL) return ACT_E_BADARG;
+    hipLaunchKernelGGL(emd_wave_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz1, xyz2, B, N, eps_final, eps_rel,
+                       max_bids, dist, assignment, info, eps_used);
+    ACT_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int act_emd_bwd_f32(const float* xyz1, const float* xyz2, const int32_t* assignment, const float* grad_dist, int B, int N,

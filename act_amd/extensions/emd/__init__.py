@@ -19,7 +19,14 @@ reconstruction (CDL1 x1000 of 10 .. 30, i.e. distances of 0.01 .. 0.03, squares 
 For inputs on another scale pass ``eps`` of about 2.5e-6 times the largest squared distance.
 
 ``DEFAULT_MAX_ROUNDS`` = 1,000,000 rounds over all phases.  Unit-sphere clouds need about 1,500 rounds at N = 256, 6,000 at 1,024 and 24,000 at
-2,048; the cap is there so that no input can keep a kernel running, not to be met."""
+2,048; the cap is there so that no input can keep a kernel running, not to be met.
+
+``solver="wave"`` (act_emd_wave_fwd_f32) is the solver for MANY SMALL pairs, the regime of a Stage-I loss over ``B*G`` group patches of
+``group_size`` points: N <= ``wave_max_points()`` = 64, one wavefront per pair, the auction in registers with one bid at a time (Gauss-Seidel,
+lowest unassigned bidder first).  For it ``max_rounds`` caps the BIDS, ``info`` counts bids, and the final eps is
+``eps_used = max(eps, eps_rel * largest squared distance of the pair)``: group patches live on scales from 0.05 to 1 and no absolute eps fits
+them all; ``eps_rel = 2**-18`` is the 2.5e-6 of the paragraph above.  ``sum(dist) <= optimum + N * eps_used`` whenever ``info >= 0``.
+The default solver is ``"workgroup"`` for every N: nothing changes for a caller that does not ask for ``"wave"``."""
 import torch
 
 from ... import _C
@@ -31,6 +38,25 @@ DEFAULT_MAX_ROUNDS = 1000000
 def max_points():
     """the largest N a pair may have (everything the solve touches lives in the LDS of one compute unit)"""
     return int(_C.lib.act_emd_max_points())
+
+
+def wave_max_points():
+    """the largest N a pair may have with ``solver="wave"`` (one object per lane of a wavefront)"""
+    return int(_C.lib.act_emd_wave_max_points())
+
+
+SOLVERS = ("workgroup", "wave")
+
+
+def _check_solver(solver, eps_rel):
+    if solver not in SOLVERS:
+        raise ValueError(f"emd: solver = {solver!r} (supported: {', '.join(map(repr, SOLVERS))})")
+    eps_rel = float(eps_rel)
+    if not (0.0 <= eps_rel < float("inf")):
+        raise ValueError(f"emd: eps_rel = {eps_rel!r} must be finite and not negative")
+    if solver == "workgroup" and eps_rel != 0.0:
+        raise ValueError('emd: eps_rel is an argument of solver="wave"; the workgroup solver takes an absolute eps only')
+    return eps_rel
 
 
 def _check(xyz1, xyz2):
@@ -54,22 +80,37 @@ def _check_counts(n1, n2):
 
 class emd_cuda:          # namespace standing in for the compiled ``emd_cuda`` module
     @staticmethod
-    def forward(xyz1, xyz2, eps=DEFAULT_EPS, max_rounds=DEFAULT_MAX_ROUNDS, want_evals=False):
-        """-> [dist f32 [B,N], assignment int32 [B,N], info int32 [B]] (+ evals int64 [B], the bids made, with ``want_evals``)"""
+    def forward(xyz1, xyz2, eps=DEFAULT_EPS, max_rounds=DEFAULT_MAX_ROUNDS, want_evals=False, solver="workgroup", eps_rel=0.0, want_eps=False):
+        """-> [dist f32 [B,N], assignment int32 [B,N], info int32 [B]] (+ evals int64 [B], the bids made, with ``want_evals``; + eps_used
+        f32 [B] with ``want_eps``).  ``solver="wave"``: N <= ``wave_max_points()``, ``max_rounds`` caps the bids and ``info`` counts them (so
+        ``want_evals`` is refused), ``eps_used = max(eps, eps_rel * largest squared distance)`` per pair.  With the workgroup solver
+        ``eps_used`` is ``eps``."""
         _check(xyz1, xyz2)
         eps, max_rounds = float(eps), int(max_rounds)
         if not (0.0 < eps < float("inf")) or max_rounds < 1:
             raise ValueError(f"emd: eps = {eps!r} must be positive and finite, max_rounds = {max_rounds!r} at least 1")
+        eps_rel = _check_solver(solver, eps_rel)
         xyz1 = xyz1.contiguous(); xyz2 = xyz2.contiguous()
         B, N, _ = xyz1.shape
         dev = xyz1.device
+        if solver == "wave":
+            if N > wave_max_points():
+                raise ValueError(f'emd: solver="wave" takes at most {wave_max_points()} points per cloud, got {N}')
+            if want_evals:
+                raise ValueError('emd: solver="wave" makes one bid at a time, so info already is the number of bids; want_evals has nothing to add')
         dist = torch.empty(B, N, dtype=torch.float32, device=dev)
         assignment = torch.empty(B, N, dtype=torch.int32, device=dev)
         info = torch.empty(B, dtype=torch.int32, device=dev)
+        if solver == "wave":
+            eps_used = torch.empty(B, dtype=torch.float32, device=dev) if want_eps else None
+            _C.check(_C.lib.act_emd_wave_fwd_f32(_C.ptr(xyz1), _C.ptr(xyz2), B, N, eps, eps_rel, max_rounds, _C.ptr(dist), _C.ptr(assignment),
+                                                 _C.ptr(info), _C.ptr(eps_used), _C.stream()), "act_emd_wave_fwd_f32")
+            return [dist, assignment, info] + ([eps_used] if want_eps else [])
         evals = torch.empty(B, dtype=torch.int64, device=dev) if want_evals else None
         _C.check(_C.lib.act_emd_fwd_ex_f32(_C.ptr(xyz1), _C.ptr(xyz2), B, N, eps, max_rounds, _C.ptr(dist), _C.ptr(assignment), _C.ptr(info),
                                            _C.ptr(evals), _C.stream()), "act_emd_fwd_ex_f32")
-        return [dist, assignment, info] + ([evals] if want_evals else [])
+        return [dist, assignment, info] + ([evals] if want_evals else []) + \
+            ([torch.full((B,), eps, dtype=torch.float32, device=dev)] if want_eps else [])
 
     @staticmethod
     def backward(xyz1, xyz2, assignment, grad_dist):
@@ -88,12 +129,12 @@ class emd_cuda:          # namespace standing in for the compiled ``emd_cuda`` m
 
 
 class EMDFunction(torch.autograd.Function):
-    """(xyz1, xyz2, eps, max_rounds) -> (dist, assignment); ``assignment`` is not differentiable.  The matching is piecewise constant in the
+    """(xyz1, xyz2, eps, max_rounds[, info_out, solver, eps_rel]) -> (dist, assignment); ``assignment`` is not differentiable.  The matching is piecewise constant in the
     inputs, so the gradient is that of sum_i g[i] |xyz1[i] - xyz2[a(i)]|^2 with a held fixed.  ``info_out``: a list that receives the solve's
     ``info`` tensor (the modules keep it as ``last_info``)."""
     @staticmethod
-    def forward(ctx, xyz1, xyz2, eps=DEFAULT_EPS, max_rounds=DEFAULT_MAX_ROUNDS, info_out=None):
-        dist, assignment, info = emd_cuda.forward(xyz1, xyz2, eps, max_rounds)
+    def forward(ctx, xyz1, xyz2, eps=DEFAULT_EPS, max_rounds=DEFAULT_MAX_ROUNDS, info_out=None, solver="workgroup", eps_rel=0.0):
+        dist, assignment, info = emd_cuda.forward(xyz1, xyz2, eps, max_rounds, solver=solver, eps_rel=eps_rel)
         if info_out is not None:
             info_out.append(info)
         ctx.save_for_backward(xyz1, xyz2, assignment)
@@ -104,15 +145,18 @@ class EMDFunction(torch.autograd.Function):
     def backward(ctx, grad_dist, _grad_assignment):
         xyz1, xyz2, assignment = ctx.saved_tensors
         gx1, gx2 = emd_cuda.backward(xyz1, xyz2, assignment, grad_dist)
-        return gx1, gx2, None, None, None
+        return gx1, gx2, None, None, None, None, None
 
 
 class emdModule(torch.nn.Module):
     """``emdModule(eps=..., max_rounds=...)``; ``forward(xyz1, xyz2)`` -> (dist [B,N], assignment int32 [B,N]).  The historical call shape
     ``forward(xyz1, xyz2, eps, iters)`` is accepted: ``eps`` is ``eps_final`` and ``iters`` is ``max_rounds`` (not a number of rounds that
-    will be run: the solve ends when it is done).  ``last_info``: the ``info`` tensor of the last call (on the device), None before it."""
-    def __init__(self, eps=None, max_rounds=None):
+    will be run: the solve ends when it is done).  ``last_info``: the ``info`` tensor of the last call (on the device), None before it.
+    ``solver="wave"`` with ``eps_rel``: the one-wave-per-pair solver for N <= 64 (module docstring); ``max_rounds`` then caps the bids."""
+    def __init__(self, eps=None, max_rounds=None, solver="workgroup", eps_rel=0.0):
         super().__init__()
+        self.eps_rel = _check_solver(solver, eps_rel)
+        self.solver = solver
         self.eps = DEFAULT_EPS if eps is None else float(eps)
         self.max_rounds = DEFAULT_MAX_ROUNDS if max_rounds is None else int(max_rounds)
         self.last_info = None
@@ -120,7 +164,7 @@ class emdModule(torch.nn.Module):
     def forward(self, xyz1, xyz2, eps=None, iters=None):
         info = []
         dist, assignment = EMDFunction.apply(xyz1, xyz2, self.eps if eps is None else float(eps),
-                                             self.max_rounds if iters is None else int(iters), info)
+                                             self.max_rounds if iters is None else int(iters), info, self.solver, self.eps_rel)
         self.last_info = info[0]
         return dist, assignment
 

@@ -20,6 +20,30 @@ from .build import MODELS
 knn = KNN(k=4, transpose_mode=False)          # module-level DGCNN graph operator, as in models/dvae.py:23
 
 
+EMD_LOSS_DEFAULTS = dict(weight=1.0, eps=1.0e-12, eps_rel=2.0 ** -18, max_bids=100000)
+
+
+def parse_emd_loss(value, group_size):
+    """model key ``emd_loss``: absent / false -> None; ``True`` -> the defaults; a dict -> the defaults with its entries.  The term runs on the
+    one-wave-per-pair solver of extensions/emd, so ``group_size`` must not exceed its limit (checked here, at construction)."""
+    if not value:
+        return None
+    opts = dict(EMD_LOSS_DEFAULTS)
+    if value is not True:
+        if not isinstance(value, dict):
+            raise ValueError(f"emd_loss: expected True or a dict of {sorted(EMD_LOSS_DEFAULTS)}, got {value!r}")
+        unknown = sorted(set(value) - set(opts))
+        if unknown:
+            raise ValueError(f"emd_loss: unknown keys {unknown} (supported: {sorted(opts)})")
+        opts.update(value)
+    opts = dict(weight=float(opts["weight"]), eps=float(opts["eps"]), eps_rel=float(opts["eps_rel"]), max_bids=int(opts["max_bids"]))
+    from ..extensions.emd import wave_max_points
+    if group_size > wave_max_points():
+        raise ValueError(f"emd_loss: group_size = {group_size}, but the matching of a group runs in one wavefront and takes at most "
+                         f"{wave_max_points()} points")
+    return opts
+
+
 def trunc_normal_(tensor, mean=0.0, std=1.0, a=-2.0, b=2.0):
     return nn.init.trunc_normal_(tensor, mean=mean, std=std, a=a, b=b)
 
@@ -294,19 +318,41 @@ class DiscreteVAE(nn.Module):
         self.dgcnn_2 = DGCNN(encoder_channel=self.tokens_dims, output_channel=self.decoder_dims)
         self.decoder = Decoder(encoder_channel=self.decoder_dims, num_fine=self.group_size)
         self.build_loss_func()
+        self.build_emd_loss(config)
 
     def build_loss_func(self):
         self.loss_func_cdl1 = ChamferDistanceL1()
         self.loss_func_cdl2 = ChamferDistanceL2()
 
+    def build_emd_loss(self, config):
+        """optional model key ``emd_loss`` (``parse_emd_loss``): the line ``# self.loss_func_emd = emd().cuda()`` of models/dvae.py:302,701.
+        ``emd_last_info``: the ``info`` tensor of the last solve; ``emd_capped``: int64 device scalar, += the pairs whose solve hit
+        ``max_bids``.  Neither is read on the host by a training step (the runner reads ``emd_capped`` once per epoch)."""
+        self.emd_loss = parse_emd_loss(config.get("emd_loss", None), self.group_size)
+        if self.emd_loss is not None:
+            self.emd_last_info = None
+            self.register_buffer("emd_capped", torch.zeros((), dtype=torch.int64), persistent=False)      # state_dict keys stay the reference's
+
     # ---- losses (Stage I) ------------------------------------------------------------------------
     def recon_loss(self, ret, gt):
+        """CDL1(coarse, group_gt) + CDL1(fine, group_gt), per group.  With ``emd_loss``: + weight * mean over all B*G*group_size points of
+        sqrt(dist), dist the squared distances of the one-to-one matching of (fine, group_gt) per group; differentiable in ``fine`` with the
+        matching held fixed.  (The square root has no finite slope at 0: a point that coincides with its match gives a NaN gradient, as in
+        ChamferDistanceL1.)  ``coarse`` has group_size / 4 points and gets no such term."""
         whole_coarse, whole_fine, coarse, fine, group_gt, _ = ret
         bs, g, _, _ = coarse.shape
         coarse = coarse.reshape(bs * g, -1, 3).contiguous()
         fine = fine.reshape(bs * g, -1, 3).contiguous()
         group_gt = group_gt.reshape(bs * g, -1, 3).contiguous()
-        return self.loss_func_cdl1(coarse, group_gt) + self.loss_func_cdl1(fine, group_gt)
+        loss = self.loss_func_cdl1(coarse, group_gt) + self.loss_func_cdl1(fine, group_gt)
+        if self.emd_loss is None:
+            return loss
+        from ..extensions.emd import EMDFunction
+        o, info = self.emd_loss, []
+        dist, _ = EMDFunction.apply(fine, group_gt, o["eps"], o["max_bids"], info, "wave", o["eps_rel"])
+        self.emd_last_info = info[0]
+        self.emd_capped += (info[0] < 0).sum()
+        return loss + o["weight"] * torch.mean(torch.sqrt(dist))
 
     def get_loss(self, ret, gt):
         loss_recon = self.recon_loss(ret, gt)

@@ -162,6 +162,13 @@ def run_net(args, config, train_writer=None, val_writer=None, max_steps=None, lo
             scheduler.step(epoch)
         print_log('[Training] EPOCH: %d EpochTime = %.3f (s) Losses = %s lr = %.6f' %
                   (epoch, time.time() - epoch_start, ['%.4f' % l for l in losses.avg()], optimizer.param_groups[0]['lr']), logger=logger)
+        if getattr(base_model.module, 'emd_loss', None):              # model key ``emd_loss``: the epoch's one read of the capped-solve counter
+            capped = int(base_model.module.emd_capped.item())
+            if capped > 0:
+                print_log('[Training] EPOCH: %d WARNING: emd_loss: the bid cap (max_bids = %d) ended the matching of %d group pairs; their '
+                          'term is an upper bound without the N * eps guarantee' % (epoch, base_model.module.emd_loss['max_bids'], capped),
+                          logger=logger)
+            base_model.module.emd_capped.zero_()
         if epoch % args.val_freq == 0 and epoch != 0:
             metrics = validate(base_model, test_dataloader, epoch, cdl1, cdl2, args, config, device, logger=logger)
             if metrics.better_than(best_metrics):

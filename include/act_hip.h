@@ -895,6 +895,19 @@ int act_emd_fwd_f32(const float* xyz1, const float* xyz2, int B, int N, float ep
                     int32_t* info, act_stream_t stream);
 int act_emd_fwd_ex_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, int max_rounds, float* dist, int32_t* assignment,
                        int32_t* info, uint64_t* evals, act_stream_t stream);
+/* The same problem for MANY SMALL pairs (the Stage-I loss: B*G group patches of group_size points), 1 <= N <= act_emd_wave_max_points() = 64:
+ * one wavefront per pair, object j and bidder i in lane j / i, the whole auction in registers (no LDS, no barrier, no atomic), four pairs per
+ * workgroup.  Costs and values are rounded as above.  Gauss-Seidel instead of Jacobi: ONE bid at a time, by the lowest-index unassigned
+ * bidder, on its best object (ties: lower j) at price + (v1 - v2) + eps (N == 1: price + eps; never less than the next float above the
+ * price); the object's owner, if any, becomes unassigned.  The final eps is relative to the pair's scale:
+ *     eps_used = max(eps_final, eps_rel * max_ij d_ij)      (eps_final > 0 and finite, eps_rel >= 0 and finite),
+ * the ladder is eps_used * 4^k entered and descended as above, and sum_i dist[i] <= optimum + N * eps_used in exact arithmetic.
+ * max_bids (>= 1) caps the bids of all phases together; at the cap the unassigned bidders get the free objects, both ascending, so
+ * `assignment` is ALWAYS a bijection.  info int32 [B] = bids made, NEGATED when the cap was hit; eps_used fp32 [B] (may be NULL).
+ * A pair's result depends only on its own inputs and the arguments.  B == 0 is a no-op.  The backward is act_emd_bwd_f32. */
+int act_emd_wave_max_points(void);
+int act_emd_wave_fwd_f32(const float* xyz1, const float* xyz2, int B, int N, float eps_final, float eps_rel, int max_bids, float* dist,
+                         int32_t* assignment, int32_t* info, float* eps_used, act_stream_t stream);
 /* gx1[i] = (2 * (xyz1[i] - xyz2[a(i)])) * grad_dist[i], gx2[a(i)] = -gx1[i] (fp32 [B,N,3] each, the operations in this order, no atomics).
  * Rows of gx2 that `assignment` does not name are zero; an entry outside [0,N) is skipped. */
 int act_emd_bwd_f32(const float* xyz1, const float* xyz2, const int32_t* assignment, const float* grad_dist, int B, int N, float* gx1,
