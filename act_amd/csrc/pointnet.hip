@@ -5,10 +5,23 @@
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------------- column statistics
-// partial[blk][0][c] = sum_r f(r,c), partial[blk][1][c] = sum_r g(r,c) over the block's rows.
-//   MODE 0: f = x,            g = x*x                       (BatchNorm batch statistics)
+// Chan's rule for two sets of rows of one column: (na, ma, qa) <- (na, ma, qa) + (nb, mb, qb), n = row count, m = mean, q = M2 = sum (x - m)^2.
+// An empty set is (0, 0, 0) on either side.
+__device__ __forceinline__ void chan_merge(float& na, float& ma, float& qa, float nb, float mb, float qb) {
+    const float n = na + nb;
+    if (n > 0.f) { const float d = mb - ma, w = nb / n; ma += d * w; qa += qb + (d * d) * (na * w); }
+    na = n;
+}
+
+// One stage-1 part = rows [blk * rows_per_block, +rows_per_block) of every column (the last part is shorter); S = 4 (MODE 0) or 2 (MODE 1) rows
+// of C floats per part: partial[blk][0][c] = sum_r f(r,c), partial[blk][1][c] = sum_r g(r,c) over the part's rows,
+//   MODE 0: f = x - x[0][c],  g = f*f                       (BatchNorm batch statistics, pivoted on row 0 of the tensor)
 //   MODE 1: f = dyh,          g = dyh * xhat                (BatchNorm backward sums), dyh = relu ? dy*(y>0) : dy
-// block = 64 float4-columns?  no: 64 columns x 4 row-lanes like colsum, 4 rows in flight per thread.
+// workgroup = 64 columns x 4 row-lanes like colsum (lane ry takes the part's rows ry, ry + 4, ...), 4 rows in flight per thread.
+// The row-0 pivot keeps E[x^2]-E[x]^2 free of cancellation only while row 0 is a typical sample.  MODE 0 therefore forms, in the same pass, a
+// second pair of sums pivoted on each LANE's own first row, turns them into the lane's (mean, M2) and merges the four lanes by Chan's rule:
+// partial[blk][2][c] = mean, partial[blk][3][c] = M2 of the part's rows -- cancellation confined to the <= rows_per_block / 4 rows of a lane,
+// whichever row comes first.  The finalizer (column_mean_var) uses the row-0 sums wherever they are sound and this pair where they are not.
 template <int MODE>
 __global__ __launch_bounds__(256) void colstats_stage1(const float* __restrict__ x, const float* __restrict__ dy,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
@@ -19,16 +32,18 @@ __global__ __launch_bounds__(256) void colstats_stage1(const float* __restrict__
     const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cx;
     const int r0 = blockIdx.y * rows_per_block, r1 = min(R, r0 + rows_per_block);
+    constexpr int S = MODE == 0 ? 4 : 2;
     float f0 = 0.f, f1 = 0.f, f2 = 0.f, f3 = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f, k0 = 0.f, k1 = 0.f, k2 = 0.f, k3 = 0.f, pl = 0.f;      // (MODE 0) the lane-pivoted sums
     if (c < C) {
         float sc = 0.f, sf = 0.f, mu = 0.f, rs = 0.f, pv = 0.f;
         if (MODE == 1) { sc = scale[c]; sf = shift[c]; mu = mean[c]; rs = rstd[c]; }
-        else pv = x[c];                                  // pivot (row 0) keeps E[x^2]-E[x]^2 free of cancellation
-        auto term = [&](int r, float& f, float& g) {
+        else { pv = x[c]; if (r0 + ry < r1) pl = x[(size_t)(r0 + ry) * C + c]; }       // pivots: row 0 of the tensor, this lane's first row
+        auto term = [&](int r, float& f, float& g, float& h, float& k) {
             // (MODE 1) rows of a group whose dy is all zero add exact zeros to both sums: skipped without changing a bit
             if (MODE == 1 && live && !live[r / live_n]) return;
             const float xv = x[(size_t)r * C + c];
-            if (MODE == 0) { const float t = xv - pv; f += t; g += t * t; }
+            if (MODE == 0) { const float t = xv - pv; f += t; g += t * t; const float u = xv - pl; h += u; k += u * u; }
             else {
                 float d = dy[(size_t)r * C + c];
                 if (relu && !(xv * sc + sf > 0.f)) d = 0.f;
@@ -36,15 +51,28 @@ __global__ __launch_bounds__(256) void colstats_stage1(const float* __restrict__
             }
         };
         int r = r0 + ry;
-        for (; r + 12 < r1; r += 16) { term(r, f0, g0); term(r + 4, f1, g1); term(r + 8, f2, g2); term(r + 12, f3, g3); }
-        for (; r < r1; r += 4) term(r, f0, g0);
+        for (; r + 12 < r1; r += 16) { term(r, f0, g0, h0, k0); term(r + 4, f1, g1, h1, k1); term(r + 8, f2, g2, h2, k2); term(r + 12, f3, g3, h3, k3); }
+        for (; r < r1; r += 4) term(r, f0, g0, h0, k0);
     }
+    __shared__ float lm[2][4][64];                                     // (MODE 0) the lanes' (mean, M2)
+    auto lane_rows = [&](int l) { return r1 - r0 > l ? (float)((r1 - r0 - l + 3) / 4) : 0.f; };
     sh[0][ry][cx] = (f0 + f1) + (f2 + f3);
     sh[1][ry][cx] = (g0 + g1) + (g2 + g3);
+    if (MODE == 0) {                                                    // (sum u, sum u^2) of this lane's rows -> their (mean, M2)
+        const float hs = (h0 + h1) + (h2 + h3), ks = (k0 + k1) + (k2 + k3);
+        const float nl = lane_rows(ry), dm = nl > 0.f ? hs / nl : 0.f;
+        lm[0][ry][cx] = pl + dm; lm[1][ry][cx] = fmaxf(ks - hs * dm, 0.f);
+    }
     __syncthreads();
     if (ry == 0 && c < C) {
-        partial[((size_t)blockIdx.y * 2 + 0) * C + c] = (sh[0][0][cx] + sh[0][1][cx]) + (sh[0][2][cx] + sh[0][3][cx]);
-        partial[((size_t)blockIdx.y * 2 + 1) * C + c] = (sh[1][0][cx] + sh[1][1][cx]) + (sh[1][2][cx] + sh[1][3][cx]);
+        partial[((size_t)blockIdx.y * S + 0) * C + c] = (sh[0][0][cx] + sh[0][1][cx]) + (sh[0][2][cx] + sh[0][3][cx]);
+        partial[((size_t)blockIdx.y * S + 1) * C + c] = (sh[1][0][cx] + sh[1][1][cx]) + (sh[1][2][cx] + sh[1][3][cx]);
+        if (MODE == 0) {                                                // lanes 0, 1, 2, 3 in turn; a lane without rows holds (0, 0, 0)
+            float n = lane_rows(0), m = lm[0][0][cx], q = lm[1][0][cx];
+            for (int l = 1; l < 4; ++l) chan_merge(n, m, q, lane_rows(l), lm[0][l][cx], lm[1][l][cx]);
+            partial[((size_t)blockIdx.y * 4 + 2) * C + c] = m;
+            partial[((size_t)blockIdx.y * 4 + 3) * C + c] = q;
+        }
     }
 }
 
@@ -96,14 +124,14 @@ __global__ __launch_bounds__(256) void colstats_bwd4_kernel(const float* __restr
 }
 
 // BatchNorm finalize: mean, biased var -> scale = gamma*rstd, shift = beta - mean*scale; running stats (momentum, unbiased var)
-// fold the stage-1 partial rows [nparts][2][C]: workgroup = 64 columns x 4 part-lanes, 8 loads in flight per thread, lanes folded
+// fold rows 0 and 1 of the stage-1 partials [nparts][S][C]: workgroup = 64 columns x 4 part-lanes, 8 loads in flight per thread, lanes folded
 // through LDS in a fixed order (a single thread per column walking ~1000 partial rows is a 150 us chain of dependent loads)
-__device__ __forceinline__ void fold_partials(const float* __restrict__ partial, int nparts, int C, int c, int lane, float (*red)[3][64],
+__device__ __forceinline__ void fold_partials(const float* __restrict__ partial, int nparts, int S, int C, int c, int lane, float (*red)[3][64],
                                               float& s, float& q) {
     s = 0.f; q = 0.f;
     if (c < C) {
 #pragma unroll 8
-        for (int p = lane; p < nparts; p += 4) { s += partial[((size_t)p * 2) * C + c]; q += partial[((size_t)p * 2 + 1) * C + c]; }
+        for (int p = lane; p < nparts; p += 4) { s += partial[((size_t)p * S) * C + c]; q += partial[((size_t)p * S + 1) * C + c]; }
     }
     const int cl = threadIdx.x & 63;
     if (lane > 0) { red[0][lane - 1][cl] = s; red[1][lane - 1][cl] = q; }
@@ -113,19 +141,59 @@ __device__ __forceinline__ void fold_partials(const float* __restrict__ partial,
         q = (q + red[1][0][cl]) + (red[1][1][cl] + red[1][2][cl]);
     }
 }
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int C, int R, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
+// Column mean and biased variance from the MODE 0 partials [nparts][4][C].  The row-0 sums give mean = x[0][c] + dm, var = q / R - dm^2; that is
+// sound while the pivot lies within a few standard deviations of the mean.  Where dm^2 > FAR_PIVOT * var in some column of the workgroup, those
+// columns take Chan's combination of the parts' (mean, M2) instead: mean = mean_0 + sum n_p (mean_p - mean_0) / R, then
+// M2 = sum M2_p + n_p (mean_p - mean)^2 (two passes over the partials, nothing cancels; part p holds n_p = min(rows_per_block, R - p rows_per_block)
+// rows).  Both are fixed-order, so two runs give equal bits; just short of the switch (pivot 4.8 standard deviations out) the row-0 form measures 4.7e-6 on the
+// normalised output and 2.7e-6 on running_var at R = 262,144 (bars 2e-5 / 1e-5; tests/test_gpu_pointnet_rows_edges.py::test_either_side_of_the_far_pivot_switch).
+// Returns true in the one thread of column c that holds the result.
+#define FAR_PIVOT 25.f
+__device__ __forceinline__ bool column_mean_var(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int rows_per_block, int C,
+                                                int R, int& c, float& mean, float& var) {
+    __shared__ float red[2][3][64];
+    __shared__ float all[4][64];
+    const int cl = threadIdx.x & 63, lane = threadIdx.x >> 6;
+    c = blockIdx.x * 64 + cl;
+    float s, q;
+    fold_partials(partial, nparts, 4, C, c, lane, red, s, q);
+    const bool mine = lane == 0 && c < C;
+    int far = 0;
+    if (mine) {
+        const float dm = s / (float)R;                  // mean of (x - pivot)
+        mean = x[c] + dm;
+        var = q / (float)R - dm * dm;
+        var = fmaxf(var, 0.f);
+        far = dm * dm > FAR_PIVOT * var;
+    }
+    if (!__syncthreads_or(far)) return mine;
+    auto sum4 = [&](float v) -> float {                 // sum over the four part-lanes of column cl in a fixed order, the same value in every lane
+        __syncthreads();
+        all[lane][cl] = v;
+        __syncthreads();
+        return (all[0][cl] + all[1][cl]) + (all[2][cl] + all[3][cl]);
+    };
+    auto rows = [&](int p) { return (float)min(rows_per_block, R - p * rows_per_block); };
+    const float m0 = c < C ? partial[(size_t)2 * C + c] : 0.f;
+    float a = 0.f;
+    if (c < C) for (int p = lane; p < nparts; p += 4) a += rows(p) * (partial[((size_t)p * 4 + 2) * C + c] - m0);
+    const float cmean = m0 + sum4(a) / (float)R;
+    a = 0.f;
+    if (c < C) for (int p = lane; p < nparts; p += 4) {
+        const float d = partial[((size_t)p * 4 + 2) * C + c] - cmean;
+        a += partial[((size_t)p * 4 + 3) * C + c] + rows(p) * (d * d);
+    }
+    const float cvar = fmaxf(sum4(a) / (float)R, 0.f);
+    if (far) { mean = cmean; var = cvar; }
+    return mine;
+}
+// BatchNorm finalize: mean, biased var -> scale = gamma*rstd, shift = beta - mean*scale; running stats (momentum, unbiased var)
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int rows_per_block, int C, int R,
+                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum, float* __restrict__ running_mean,
                                    float* __restrict__ running_var, float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                    float* __restrict__ scale_out, float* __restrict__ shift_out) {
-    __shared__ float red[2][3][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
-    float s, q;
-    fold_partials(partial, nparts, C, c, lane, red, s, q);
-    if (lane != 0 || c >= C) return;
-    const float dm = s / (float)R;                      // mean of (x - pivot)
-    const float mean = x[c] + dm;
-    float var = q / (float)R - dm * dm;
-    var = fmaxf(var, 0.f);
+    int c; float mean, var;
+    if (!column_mean_var(x, partial, nparts, rows_per_block, C, R, c, mean, var)) return;
     const float rstd = rsqrtf(var + eps);
     const float sc = gamma[c] * rstd;
     mean_out[c] = mean; rstd_out[c] = rstd; scale_out[c] = sc; shift_out[c] = beta[c] - mean * sc;
@@ -140,7 +208,7 @@ __global__ __launch_bounds__(256) void colstats_stage2(const float* __restrict__
     __shared__ float red[2][3][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
     float s, q;
-    fold_partials(partial, nparts, C, c, lane, red, s, q);
+    fold_partials(partial, nparts, 2, C, c, lane, red, s, q);
     if (lane == 0 && c < C) { out0[c] = s; out1[c] = q; }
 }
 
@@ -207,6 +275,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* __restr
 
 // ------------------------------------------------------------------------------------------------ group max-pool
 // in [G*n, C] -> out [G, C] = max over the n rows of a group; arg [G,C] = first row attaining it (torch.max semantics)
+// NaN inputs are outside the contract: `v > best` never selects a NaN (a NaN in row 0 stays, any other is skipped), while torch.max propagates it.
 __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict__ in, int n, int C, long long total,
                                                         float* __restrict__ out, int32_t* __restrict__ arg) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -249,7 +318,8 @@ static int stats_parts(int R, int C) {
     if (parts > 1024) parts = 1024; if (parts < 1) parts = 1;
     return parts;
 }
-extern "C" size_t act_colstats_workspace(int R, int C) { return (size_t)stats_parts(R, C) * 2 * C * sizeof(float); }
+// four rows of C floats per part: the statistics pass leaves two pairs of sums (the backward sums use the first two rows' worth)
+extern "C" size_t act_colstats_workspace(int R, int C) { return (size_t)stats_parts(R, C) * 4 * C * sizeof(float); }
 
 // train-mode BatchNorm statistics of x [R,C] (models/dvae.py:189-200 nn.BatchNorm1d over B*G*n samples per channel):
 // writes mean, rstd, scale = gamma*rstd, shift = beta - mean*scale and updates running stats in place (nullable).
@@ -259,14 +329,14 @@ extern "C" int act_bn_stats_f32(const float* x, int R, int C, const float* gamma
     if (!x || !gamma || !beta || !mean || !rstd || !scale || !shift || !workspace) return ACT_E_NULLPTR;
     if (R <= 0 || C <= 0) return ACT_E_BADARG;
     const int parts = stats_parts(R, C);
-    if (workspace_bytes < (size_t)parts * 2 * C * sizeof(float)) return ACT_E_BADARG;
+    if (workspace_bytes < act_colstats_workspace(R, C)) return ACT_E_BADARG;
     int rpb = (R + parts - 1) / parts; rpb = (rpb + 3) / 4 * 4;
     const int nparts = (R + rpb - 1) / rpb;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_BN_STATS, s, 0.0, 4.0 * R * (double)C);
     hipLaunchKernelGGL(colstats_stage1<0>, dim3((C + 63) / 64, nparts), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                        R, C, rpb, workspace);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, x, workspace, nparts, C, R, gamma, beta, eps, momentum,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, x, workspace, nparts, rpb, C, R, gamma, beta, eps, momentum,
                        running_mean, running_var, mean, rstd, scale, shift);
     ACT_LAUNCH_CHECK(); return 0;
 }
@@ -294,7 +364,7 @@ extern "C" int act_bn_bwd_groups_f32(const float* x, const float* dy, const floa
     if (!x || !dy || !scale || !shift || !mean || !rstd || !dx || !dgamma || !dbeta || !workspace) return ACT_E_NULLPTR;
     if (R <= 0 || C <= 0 || (live && (n <= 0 || R % n))) return ACT_E_BADARG;
     const int parts = stats_parts(R, C);
-    if (workspace_bytes < (size_t)parts * 2 * C * sizeof(float)) return ACT_E_BADARG;
+    if (workspace_bytes < act_colstats_workspace(R, C)) return ACT_E_BADARG;
     int rpb = (R + parts - 1) / parts; rpb = (rpb + 3) / 4 * 4;
     const int nparts = (R + rpb - 1) / rpb;
     hipStream_t s = (hipStream_t)stream;
@@ -369,16 +439,11 @@ extern "C" int act_bn_eval_affine_f32(const float* gamma, const float* beta, con
 }
 
 // ---- pieces of the BatchNorm reductions as separate entry points: SyncBatchNorm (statistics all-reduced across ranks between them) ----
-__global__ __launch_bounds__(256) void meanvar_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int C, int R,
+__global__ __launch_bounds__(256) void meanvar_finalize_kernel(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int rows_per_block, int C, int R,
                                                                float* __restrict__ mean_out, float* __restrict__ var_out) {
-    __shared__ float red[2][3][64];
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
-    float s, q;
-    fold_partials(partial, nparts, C, c, lane, red, s, q);
-    if (lane != 0 || c >= C) return;
-    const float dm = s / (float)R;
-    mean_out[c] = x[c] + dm;
-    var_out[c] = fmaxf(q / (float)R - dm * dm, 0.f);           // biased variance of this rank's rows
+    int c; float mean, var;
+    if (!column_mean_var(x, partial, nparts, rows_per_block, C, R, c, mean, var)) return;
+    mean_out[c] = mean; var_out[c] = var;                               // biased variance of this rank's rows
 }
 // per-column mean and biased variance of x [R,C] (pivoted sums, deterministic)
 extern "C" int act_col_mean_var_f32(const float* x, int R, int C, float* mean, float* var, float* workspace, size_t workspace_bytes,
@@ -386,14 +451,14 @@ extern "C" int act_col_mean_var_f32(const float* x, int R, int C, float* mean, f
     if (!x || !mean || !var || !workspace) return ACT_E_NULLPTR;
     if (R <= 0 || C <= 0) return ACT_E_BADARG;
     const int parts = stats_parts(R, C);
-    if (workspace_bytes < (size_t)parts * 2 * C * sizeof(float)) return ACT_E_BADARG;
+    if (workspace_bytes < act_colstats_workspace(R, C)) return ACT_E_BADARG;
     int rpb = (R + parts - 1) / parts; rpb = (rpb + 3) / 4 * 4;
     const int nparts = (R + rpb - 1) / rpb;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_BN_STATS, s, 0.0, 4.0 * R * (double)C);
     hipLaunchKernelGGL(colstats_stage1<0>, dim3((C + 63) / 64, nparts), dim3(256), 0, s, x, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                        R, C, rpb, workspace);
-    hipLaunchKernelGGL(meanvar_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, x, workspace, nparts, C, R, mean, var);
+    hipLaunchKernelGGL(meanvar_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s, x, workspace, nparts, rpb, C, R, mean, var);
     ACT_LAUNCH_CHECK(); return 0;
 }
 // backward sums of this rank's rows: sum_dy[c] = sum_r dyh, sum_dy_xhat[c] = sum_r dyh * xhat   (dyh = relu ? dy * (x*scale+shift > 0) : dy)
@@ -403,7 +468,7 @@ extern "C" int act_bn_bwd_sums_f32(const float* x, const float* dy, const float*
     if (!x || !dy || !scale || !shift || !mean || !rstd || !sum_dy || !sum_dy_xhat || !workspace) return ACT_E_NULLPTR;
     if (R <= 0 || C <= 0) return ACT_E_BADARG;
     const int parts = stats_parts(R, C);
-    if (workspace_bytes < (size_t)parts * 2 * C * sizeof(float)) return ACT_E_BADARG;
+    if (workspace_bytes < act_colstats_workspace(R, C)) return ACT_E_BADARG;
     int rpb = (R + parts - 1) / parts; rpb = (rpb + 3) / 4 * 4;
     const int nparts = (R + rpb - 1) / rpb;
     hipStream_t s = (hipStream_t)stream;

@@ -308,7 +308,9 @@ int act_softmax_xent_bwd_f32(const float* logits, const int64_t* labels, const f
 
 /* ---- mini-PointNet / FoldingNet row kernels (models/dvae.py:185-275), rows = points, columns = channels ------ */
 /* train-mode BatchNorm1d statistics over all R rows: mean, rstd, scale = gamma*rstd, shift = beta - mean*scale;
- * running stats updated in place when non-NULL (momentum, unbiased variance).  workspace: act_colstats_workspace. */
+ * running stats updated in place when non-NULL (momentum, unbiased variance).  The statistics do not depend on the order of the rows beyond
+ * rounding: sums pivoted on row 0 where that row is a typical sample, per-part (mean, M2) combined by Chan's rule where it is not.
+ * workspace: act_colstats_workspace bytes (four rows of C floats per stage-1 part), for every entry below that takes one. */
 size_t act_colstats_workspace(int R, int C);
 int act_bn_stats_f32(const float* x, int R, int C, const float* gamma, const float* beta, float eps, float momentum,
                      float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
