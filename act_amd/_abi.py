@@ -53,6 +53,10 @@ class VitBf16x3(ctypes.Structure):                     # act_vit_bf16x3_t
     _fields_ = [("w_planes", _vp), ("a_planes", _vp), ("a_planes_elems", _sz)]
 
 
+class VitF16x3(ctypes.Structure):                      # act_vit_f16x3_t
+    _fields_ = [("w_planes", _vp), ("w_inv_scale", _vp), ("a_scale", _vp), ("a_planes", _vp), ("a_planes_elems", _sz)]
+
+
 class PointnetParams(ctypes.Structure):                # act_pointnet_params_t
     _fields_ = [(n, _vp) for n in ("c1_w", "c1_b", "bn1_w", "bn1_b", "c2_w", "c2_b", "c3_w", "c3_b", "bn2_w", "bn2_b", "c4_w", "c4_b",
                                    "bn1_mean", "bn1_var", "bn2_mean", "bn2_var")]
@@ -79,7 +83,8 @@ class AugmentOp(ctypes.Structure):                     # act_augment_op_t
 STRUCTS = {
     "act_gemm_epilogue_t": GemmEpilogue, "act_gemm_tn_problem_t": GemmTnProblem, "act_gemm_fx_t": GemmFx,
     "act_block_params_t": BlockParams, "act_block_grads_t": BlockParams, "act_block_dims_t": BlockDims, "act_block_stack_t": BlockStack,
-    "act_prefix_vit_t": PrefixVit, "act_vit_bf16x3_t": VitBf16x3, "act_pointnet_params_t": PointnetParams,
+    "act_prefix_vit_t": PrefixVit, "act_vit_bf16x3_t": VitBf16x3, "act_vit_f16x3_t": VitF16x3,
+    "act_pointnet_params_t": PointnetParams,
     "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn, "act_augment_op_t": AugmentOp,
 }
 
@@ -177,6 +182,12 @@ _TABLE = {
     "act_prompt_layernorm_fwd_planes_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp],
     "act_attention_fwd_prefix_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "act_sgemm_nt_bf16x3_planes_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _epi, _vp],
+    # default split-f16 products of the frozen teacher (same file, F16 form)
+    "act_split_f16x2_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "act_sgemm_nt_f16x3_supported": [_i, _i, _i],
+    "act_sgemm_nt_f16x3_planes_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp],
+    "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
+    "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
     # GEMM launch-configuration table
     "act_gemm_tune_set": [_i] * 7,
     "act_gemm_tune_get": [_i] * 5 + [_P(_i), _P(_i)],
@@ -210,6 +221,7 @@ _TABLE = {
     "act_prefix_block_fwd_bf16x3_f32": [_dims, _i, _blk, _x3, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp],
     "act_prefix_block_bwd_bf16x3_f32": [_dims, _i, _blk, _x3, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_prefix_vit_fwd_f32": [_P(PrefixVit), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_prefix_vit_fwd_f16x3_f32": [_P(PrefixVit), _P(VitF16x3), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_pointnet_saved_floats": (_sz, [_pnd]),
     "act_pointnet_fwd_f32": [_pnd, _pnp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "act_pointnet_fwd_groups_f32": [_pnd, _pnp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp],

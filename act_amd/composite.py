@@ -11,6 +11,7 @@ launching anything), decided by the function the single-GEMM path asks (kernels.
 registered, so results never depend on the call history.
 """
 import ctypes
+import math
 import os
 import weakref
 
@@ -18,7 +19,7 @@ import torch
 
 from . import _C
 from . import kernels as K
-from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3
+from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3, VitF16x3
 from ._abi import GemmFx          # noqa: F401  (tests and benchmarks build it as CP.GemmFx)
 
 lib, check = _C.lib, _C.check
@@ -294,6 +295,12 @@ _VIT_PLANES = weakref.WeakKeyDictionary()      # tokenizer -> (signature incl. w
 # prompt-tuning graph (PrefixBlockFn: forward products, and -- unless ACT_TEACHER_BF16X3_BWD=0 -- the five input-gradient products of its backward).
 TEACHER_BF16X3 = os.environ.get("ACT_TEACHER_BF16X3", "0") == "1"
 TEACHER_BF16X3_BWD = os.environ.get("ACT_TEACHER_BF16X3_BWD", "1") == "1"
+# DEFAULT ON: the four Linear products per layer (qkv, proj, fc1, fc2 on the patch tokens) of the frozen teacher's INFERENCE forward on the split-f16 kernel
+# (same file, F16 form: two f16 planes with a scaled low plane, 22 significand bits per operand -> fp32-grade, not bit-identical to the f32-input MFMA path;
+# notebook/teacher_f16x3.md).  ACT_TEACHER_F16X3=0 restores the f32-input path bit for bit; ACT_TEACHER_BF16X3=1 wins if both are set.  Stage I's
+# differentiable prefix block, the CLIP / BERT teachers and the student never take it.
+TEACHER_F16X3 = os.environ.get("ACT_TEACHER_F16X3", "1") != "0"
+_VIT_F16 = weakref.WeakKeyDictionary()         # tokenizer -> (signature, planes, inverse row scales, activation scales, pointer arrays)
 
 
 def _stack_leaves(blocks):
@@ -519,6 +526,11 @@ def prefix_vit_forward(tok, tokens, center, drop_p, seed_base, seed_dev):
         check(lib.act_prefix_vit_fwd_bf16x3_f32(args[0], ctypes.byref(x3), *args[1:], _C.stream()), "act_prefix_vit_fwd_bf16x3_f32")
         del keep
         return out
+    if TEACHER_F16X3:
+        x3, keep = _vit_f16_planes(tok, ts, depth, B * G * m.hidden + B * max(G, m.P) * m.D, dev)
+        check(lib.act_prefix_vit_fwd_f16x3_f32(args[0], ctypes.byref(x3), *args[1:], _C.stream()), "act_prefix_vit_fwd_f16x3_f32")
+        del keep
+        return out
     check(lib.act_prefix_vit_fwd_f32(*args, _C.stream()), "act_prefix_vit_fwd_f32")
     return out
 
@@ -561,6 +573,57 @@ def _vit_planes(tok, ts, depth, act_elems, dev):
         cache = _VIT_PLANES[tok] = (sig, planes, parr)
     a_planes = torch.empty(2 * act_elems, dtype=torch.bfloat16, device=dev)
     x3 = VitBf16x3(ctypes.cast(cache[2], _vp), a_planes.data_ptr(), a_planes.numel())
+    return x3, (a_planes, cache)
+
+
+def f16x3_act_scale(bound):
+    """the static activation scale of one Linear of the split-f16 teacher: the largest power of two s with bound * s <= 2^15, where ``bound`` bounds the
+    magnitude of every element of its A operand; 0.0 (that Linear stays on the f32 kernel) when bound > 2^15 or is not finite"""
+    bound = float(bound)
+    if not math.isfinite(bound) or bound > 32768.0:
+        return 0.0
+    if bound < 2.0 ** -15:                       # (an all-but-zero operand: any scale holds; 2^30 keeps 1 / s and the plane values far from the exponent limits)
+        return 2.0 ** 30
+    s = 2.0 ** (math.frexp(32768.0 / bound)[1] - 1)
+    return s if bound * s <= 32768.0 else s / 2
+
+
+def f16x3_vit_bounds(ts, depth, D):
+    """weight-only bounds on the A operand of (qkv, proj, fc1, fc2) of every frozen block, [depth, 4] float64 on the device:
+       LayerNorm output   |y_j| <= sqrt(D) |gamma_j| + |beta_j| =: u_j                       (qkv: u1, fc1: u2)
+       attention output   a convex combination of V rows (tokens and prompts, both LN1 outputs times W_v): max_n sum_j |W_v[n,j]| u1_j + |b_v[n]|
+       GELU(fc1) output   |gelu(x)| <= |x| <= max_n sum_j |W_1[n,j]| u2_j + |b_1[n]|"""
+    rows, rt = [], math.sqrt(D)
+    for i in range(depth):
+        n1w, n1b, wqkv, bqkv, _, _, n2w, n2b, w1, b1 = (None if t is None else t.detach().double() for t in ts[10 + _NPB * i: 20 + _NPB * i])
+        u1, u2 = rt * n1w.abs() + n1b.abs(), rt * n2w.abs() + n2b.abs()
+        v = wqkv[2 * D:].abs() @ u1 + (bqkv[2 * D:].abs() if bqkv is not None else 0)
+        h = w1.abs() @ u2 + (b1.abs() if b1 is not None else 0)
+        rows.append(torch.stack([u1.max(), v.max(), u2.max(), h.max()]))
+    return torch.stack(rows)
+
+
+def _vit_f16_planes(tok, ts, depth, act_elems, dev):
+    """f16 (h1, h2) planes of the four Linear weights of every teacher block with one power-of-two scale per output row, the inverse scales, and the static
+    activation scale of every Linear from the range guard -- all computed ONCE and cached per tokenizer under the (address, version) signature of every block
+    tensor (the guard reads the LayerNorm parameters and biases too).  -> (VitF16x3, keep-alive)"""
+    blk = ts[10:10 + _NPB * depth]
+    sig = tuple((t.data_ptr(), t._version) if t is not None else None for t in blk)
+    cache = _VIT_F16.get(tok)
+    if cache is None or cache[0] != sig:
+        ws_ = [ts[10 + _NPB * i + j] for i in range(depth) for j in (2, 4, 8, 10)]                # qkv_w, proj_w, fc1_w, fc2_w
+        with torch.no_grad():
+            scales = [K.f16x3_row_scales(w) for w in ws_]
+            planes = [K.split_f16x2(w.detach(), 1.0, sc[0]) for w, sc in zip(ws_, scales)]
+            inv = [sc[1].contiguous() for sc in scales]
+            a_scale = [f16x3_act_scale(b) for b in f16x3_vit_bounds(ts, depth, ws_[0].shape[1]).flatten().tolist()]
+        parr = (_vp * len(planes))(*[pl.data_ptr() for pl in planes])
+        iarr = (_vp * len(inv))(*[t.data_ptr() for t in inv])
+        sarr = (ctypes.c_float * len(a_scale))(*a_scale)
+        cache = _VIT_F16[tok] = (sig, planes, inv, a_scale, (parr, iarr, sarr))
+    a_planes = torch.empty(2 * act_elems, dtype=torch.float16, device=dev)
+    parr, iarr, sarr = cache[4]
+    x3 = VitF16x3(ctypes.cast(parr, _vp), ctypes.cast(iarr, _vp), ctypes.cast(sarr, _vp), a_planes.data_ptr(), a_planes.numel())
     return x3, (a_planes, cache)
 
 

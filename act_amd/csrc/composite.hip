@@ -135,7 +135,10 @@ size_t carve_prefix_bwd(float* base, const act_block_dims_t& d, int P, PrefixBwd
 // the launch sequence of one prefix block given the LayerNorm'd prompt rows n1p (shared by the inference stack and the
 // differentiable forward)
 // OPT-IN (act_prefix_vit_fwd_bf16x3_f32): the bf16 (hi, lo) planes of one block's four weights + the scratch its activations are split into
-struct X3Block { const uint16_t *qkv, *proj, *fc1, *fc2; uint16_t* a_planes; size_t a_elems; bool n1p_is_planes; };
+struct X3Block { const uint16_t *qkv, *proj, *fc1, *fc2; uint16_t* a_planes; size_t a_elems; bool n1p_is_planes;
+                 // DEFAULT teacher (act_prefix_vit_fwd_f16x3_f32): the planes are f16 (h1, h2) planes (split_f16.h); inv[j] = 1 / s_B per output row and sa[j] = the
+                 // activation scale s_A of qkv, proj, fc1, fc2.  A Linear whose range guard gave no scale arrives with a null plane pointer: f32 kernel
+                 bool f16; const float* inv[4]; float sa[4]; };
 // scratch layout of the split-bf16 path: [0, 2 TG Hd) the planes of the MLP's hidden activation (written by fc1's epilogue, read by fc2), then ONE region of
 // 2 max(TG, TP) D for the planes of whichever other activation is multiplied next (prompt rows -> n1x -> attention output -> n2: each is consumed by the
 // product that follows it on the stream before the next producer overwrites it)
@@ -155,11 +158,21 @@ int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t
     //  LayerNorm statistics, the pre-GELU values, xin, x1, qkvx, kvp, att and lse, all of which are still written)
     const bool x3_ok = x3 && x3_fits(d, P, x3->a_elems);
     // `pre`: A is already there as planes (hi at pre, lo M*K further); `emit`: write the result as planes there instead of fp32 C
+    // (f16 form: `li` = which of the block's four Linears, for its scales; emitted planes are split at the scale of the NEXT Linear, li + 1)
+    const bool f16 = x3 && x3->f16;
     auto linear = [&](int M, int N, int K, const float* A, const float* W, const uint16_t* W_hi, size_t wplane, float* C, const act_gemm_epilogue_t& e,
-                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr) -> int {
+                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr, int li = 0) -> int {
         if (x3_ok && W_hi && act_sgemm_nt_bf16x3_supported(M, N, K)) {
             if (t_collect) return 0;
             const uint16_t* ah = pre; const uint16_t* al = pre ? pre + (size_t)M * K : nullptr;
+            if (f16) {
+                if (!pre) {
+                    CK(act_split_f16x2_f32(A, M, K, K, x3->sa[li], nullptr, tmp_planes, tmp_planes + (size_t)M * K, s));
+                    ah = tmp_planes; al = tmp_planes + (size_t)M * K;
+                }
+                return act_sgemm_nt_f16x3_planes_f32(M, N, K, ah, al, x3->sa[li], W_hi, W_hi + wplane, x3->inv[li], emit ? nullptr : C, N, emit,
+                                                     emit ? emit + (size_t)M * N : nullptr, emit ? x3->sa[li + 1] : 0.f, &e, s);
+            }
             if (!pre) {
                 CK(act_split_bf16x2_f32(A, M, K, K, tmp_planes, tmp_planes + (size_t)M * K, s));
                 ah = tmp_planes; al = tmp_planes + (size_t)M * K;
@@ -175,30 +188,36 @@ int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t
     // (n1p_is_planes: the caller's prompt LayerNorm already left the rows as planes in the activation region)
     // (kvp_ready: sv.kvp already holds them -- act_prompt_kv_fwd_f32, or the caller's own)
     if (!kvp_ready)
-    CK(linear(TP, 2 * D, D, n1p, w.qkv_w + (size_t)D * D, x3 ? x3->qkv + (size_t)D * D : nullptr, (size_t)3 * D * D, sv.kvp, e,
+    CK(linear(TP, 2 * D, D, n1p, w.qkv_w + (size_t)D * D, (x3 && x3->qkv && !f16) ? x3->qkv + (size_t)D * D : nullptr, (size_t)3 * D * D, sv.kvp, e,
               (x3_ok && x3->n1p_is_planes) ? tmp_planes : nullptr));
     const bool ln1_planes = x3_ok && x3->qkv && act_sgemm_nt_bf16x3_supported(TG, 3 * D, D);          // LayerNorm-1 hands n1x on as planes (xin stays fp32: residual)
-    if (ln1_planes) RUN(act_layernorm_fwd_planes_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean1 : nullptr,
+    if (ln1_planes && f16) RUN(act_layernorm_fwd_f16_planes_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[0],
+                                                                keep ? sv.mean1 : nullptr, keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
+    else if (ln1_planes) RUN(act_layernorm_fwd_planes_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean1 : nullptr,
                                                      keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
     else RUN(act_layernorm_fwd_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, sv.n1x, keep ? sv.mean1 : nullptr, keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
     e = epi0(); e.bias = w.qkv_b;
-    CK(linear(TG, 3 * D, D, sv.n1x, w.qkv_w, x3 ? x3->qkv : nullptr, (size_t)3 * D * D, sv.qkvx, e, ln1_planes ? tmp_planes : nullptr));
+    CK(linear(TG, 3 * D, D, sv.n1x, w.qkv_w, x3 ? x3->qkv : nullptr, (size_t)3 * D * D, sv.qkvx, e, ln1_planes ? tmp_planes : nullptr, nullptr, 0));
     const bool att_planes = x3_ok && x3->proj && act_sgemm_nt_bf16x3_supported(TG, D, D);       // the attention output leaves its kernel as planes
-    if (att_planes) RUN(act_attention_fwd_prefix_planes_f32(sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.lse : nullptr,
+    if (att_planes && f16) RUN(act_attention_fwd_prefix_f16_planes_f32(sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[1],
+                                                                       keep ? sv.lse : nullptr, B, H, hd, attn_scale(hd), s));
+    else if (att_planes) RUN(act_attention_fwd_prefix_planes_f32(sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.lse : nullptr,
                                                             B, H, hd, attn_scale(hd), s));
     else RUN(act_attention_fwd_prefix_f32(sv.kvp, P, sv.qkvx, G, sv.att, keep ? sv.lse : nullptr, B, H, hd, attn_scale(hd), s));
     e = epi0(); e.bias = w.proj_b; e.res = sv.xin; e.ldr = D;
-    CK(linear(TG, D, D, sv.att, w.proj_w, x3 ? x3->proj : nullptr, (size_t)D * D, sv.x1, e, att_planes ? tmp_planes : nullptr));
+    CK(linear(TG, D, D, sv.att, w.proj_w, x3 ? x3->proj : nullptr, (size_t)D * D, sv.x1, e, att_planes ? tmp_planes : nullptr, nullptr, 1));
     const bool ln2_planes = x3_ok && x3->fc1 && act_sgemm_nt_bf16x3_supported(TG, Hd, D);
-    if (ln2_planes) RUN(act_layernorm_fwd_planes_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean2 : nullptr,
+    if (ln2_planes && f16) RUN(act_layernorm_fwd_f16_planes_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[2],
+                                                                keep ? sv.mean2 : nullptr, keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
+    else if (ln2_planes) RUN(act_layernorm_fwd_planes_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean2 : nullptr,
                                                      keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
     else RUN(act_layernorm_fwd_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, sv.n2, keep ? sv.mean2 : nullptr, keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
     e = epi0(); e.bias = w.fc1_b; e.act = ACT_EPI_GELU; e.aux = keep ? sv.hpre : nullptr; e.ldaux = Hd;
-    CK(linear(TG, Hd, D, sv.n2, w.fc1_w, x3 ? x3->fc1 : nullptr, (size_t)Hd * D, sv.a, e, ln2_planes ? tmp_planes : nullptr, mlp_planes ? hid_planes : nullptr));
+    CK(linear(TG, Hd, D, sv.n2, w.fc1_w, x3 ? x3->fc1 : nullptr, (size_t)Hd * D, sv.a, e, ln2_planes ? tmp_planes : nullptr, mlp_planes ? hid_planes : nullptr, 2));
     e = epi0(); e.bias = w.fc2_b; e.res = sv.x1; e.ldr = D;
     // fc2 on the split-bf16 kernel ONLY with its operand already in hid_planes: a lone fc2 would split sv.a [TG, Hd] into tmp_planes, which holds
     // 2 * max(TG, TP) * D elements -- too small whenever Hd > D (reachable with a non-4x mlp_ratio, D % 128 == 0, Hd % 64 == 0, Hd % 128 != 0)
-    CK(linear(TG, D, Hd, sv.a, w.fc2_w, (x3 && mlp_planes) ? x3->fc2 : nullptr, (size_t)D * Hd, out, e, mlp_planes ? hid_planes : nullptr));
+    CK(linear(TG, D, Hd, sv.a, w.fc2_w, (x3 && mlp_planes) ? x3->fc2 : nullptr, (size_t)D * Hd, out, e, mlp_planes ? hid_planes : nullptr, nullptr, 3));
     return 0;
 }
 
@@ -569,19 +588,26 @@ size_t act_prefix_vit_scratch_floats(const act_prefix_vit_t* m) {
     return carve_vit(nullptr, *m, a, b, c, d, e, f, g);
 }
 
-static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const float* tokens, const float* center, float* out, float* scratch,
-                          float* ws, size_t wsb, act_stream_t stream);
+static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
+                          float* scratch, float* ws, size_t wsb, act_stream_t stream);
 int act_prefix_vit_fwd_f32(const act_prefix_vit_t* m, const float* tokens, const float* center, float* out, float* scratch, float* ws,
                            size_t wsb, act_stream_t stream) {
-    return prefix_vit_fwd(m, nullptr, tokens, center, out, scratch, ws, wsb, stream);
+    return prefix_vit_fwd(m, nullptr, nullptr, tokens, center, out, scratch, ws, wsb, stream);
 }
 int act_prefix_vit_fwd_bf16x3_f32(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const float* tokens, const float* center, float* out,
                                   float* scratch, float* ws, size_t wsb, act_stream_t stream) {
     if (!x3 || !x3->w_planes || !x3->a_planes) return ACT_E_NULLPTR;
-    return prefix_vit_fwd(m, x3, tokens, center, out, scratch, ws, wsb, stream);
+    return prefix_vit_fwd(m, x3, nullptr, tokens, center, out, scratch, ws, wsb, stream);
 }
-static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const float* tokens, const float* center, float* out, float* scratch,
-                          float* ws, size_t wsb, act_stream_t stream) {
+// DEFAULT teacher arithmetic (ACT_TEACHER_F16X3, on unless switched off): the four Linear products of every block on the split-f16 kernel wherever it takes the
+// shape and the range guard gave the Linear an activation scale; the prompts' keys / values stay on the sparse f32 path
+int act_prefix_vit_fwd_f16x3_f32(const act_prefix_vit_t* m, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
+                                 float* scratch, float* ws, size_t wsb, act_stream_t stream) {
+    if (!h3 || !h3->w_planes || !h3->w_inv_scale || !h3->a_scale || !h3->a_planes) return ACT_E_NULLPTR;
+    return prefix_vit_fwd(m, nullptr, h3, tokens, center, out, scratch, ws, wsb, stream);
+}
+static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
+                          float* scratch, float* ws, size_t wsb, act_stream_t stream) {
     if (bad_vit(m)) return ACT_E_BADARG;
     if (!tokens || !center || !out || !scratch || !m->blocks || !m->prompt_tok || !m->prompt_pos) return ACT_E_NULLPTR;
     hipStream_t s = (hipStream_t)stream;
@@ -602,12 +628,23 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
     for (int i = 0; i < m->depth; ++i) {
         const act_block_params_t& w = m->blocks[i];
         const uint64_t seed = (m->seed_base + 7919ull * (uint64_t)(i + 1)) & ((1ull << 62) - 1);
-        if (!x3) {              // f32 path: base product once, the dropped terms walked sparsely (the split-bf16 opt-in keeps its planes)
+        X3Block hb{};           // split-f16 default: this block's planes and scales; a Linear without an activation scale (range guard) keeps the f32 kernel
+        if (h3) {
+            hb.a_planes = h3->a_planes; hb.a_elems = h3->a_planes_elems; hb.f16 = true;
+            const uint16_t* pl[4];
+            for (int j = 0; j < 4; ++j) {
+                const float sa = h3->a_scale[4 * i + j];
+                const bool on = sa > 0.f && h3->w_planes[4 * i + j] && h3->w_inv_scale[4 * i + j];
+                pl[j] = on ? h3->w_planes[4 * i + j] : nullptr; hb.inv[j] = h3->w_inv_scale[4 * i + j]; hb.sa[j] = on ? sa : 0.f;
+            }
+            hb.qkv = pl[0]; hb.proj = pl[1]; hb.fc1 = pl[2]; hb.fc2 = pl[3];
+        }
+        if (!x3) {              // prompt keys / values: base product once, the dropped terms walked sparsely (the split-bf16 opt-in keeps its planes)
             const int rc = act_prompt_kv_fwd_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
                                                  m->eps, w.qkv_w + (size_t)D * D, w.qkv_b ? w.qkv_b + D : nullptr, sv.kvp, pkv, pkv_bytes, ws, wsb, stream);
             if (rc == 0) {
                 (void)collecting(1, 1, m->B * m->P, 2 * D, D);          // the dense product stays tuned: the switch can be turned at run time
-                CK(prefix_block_core(d, m->P, w, cur, pos, nullptr, false, sv, nxt, ws, wsb, s, nullptr, true));
+                CK(prefix_block_core(d, m->P, w, cur, pos, nullptr, false, sv, nxt, ws, wsb, s, h3 ? &hb : nullptr, true));
                 float* t = cur; cur = nxt; nxt = t;
                 continue;
             }
@@ -623,7 +660,7 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
         } else
         RUN(act_prompt_layernorm_fwd_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
                                         m->eps, n1p, s));
-        CK(prefix_block_core(d, m->P, w, cur, pos, n1p, false, sv, nxt, ws, wsb, s, x3 ? &xb : nullptr));
+        CK(prefix_block_core(d, m->P, w, cur, pos, n1p, false, sv, nxt, ws, wsb, s, x3 ? &xb : (h3 ? &hb : nullptr)));
         float* t = cur; cur = nxt; nxt = t;
     }
     RUN(act_layernorm_fwd_f32(cur, nullptr, m->norm_w, m->norm_b, nullptr, feat, nullptr, nullptr, TG, D, m->eps, s));

@@ -14,10 +14,20 @@
 // not by the matrix pipe: 128 x 128 tile, 32-deep K tiles, double-buffered LDS (ONE barrier per K tile), global prefetch two K tiles ahead in two register
 // sets.  8192 x 3072 x 768: 282 TFLOP/s-equivalent (shipped f32 kernel: 135), benchmarks/micro/bf16x3_planes.hip -> profiles/r05_micro_bf16x3_planes.txt.
 // A lesson kept in the code: the staging arrays are NATIVE vector types (ext_vector_type); arrays of HIP's `uint4` struct stay in scratch memory.
+//
+// DEFAULT for the frozen teacher's inference forward (F16 form of the same kernel, ACT_TEACHER_F16X3, notebook/teacher_f16x3.md): two f16 planes with a scaled
+// low plane, x s = h1 + 2^-11 h2 (split_f16.h), keep 22 significand bits + the residual's sign instead of 16, at the same bytes, LDS traffic and MFMA count
+// (v_mfma_f32_16x16x32_f16 runs at the bf16 rate).  f16's narrow exponent range is handled with exact powers of two: the weights carry one scale per output
+// row (row max lifted into [2^14, 2^15)), the activations one static scale per Linear derived from a weight-only bound on the operand (composite.py), and the
+// two cross terms h1.h2 + h2.h1 go to a SECOND accumulator that is folded in with 2^-11 in the epilogue, where the scales are divided out again:
+//   v = (acc0 + 2^-11 acc1) * (1 / s_B[n]) * (1 / s_A)   -> bias / GELU / residual exactly as the f32 kernels.   fp32-grade: error against fp64 equal to the
+// f32 kernel's on LayerNorm / GELU / attention operands (tests/test_gpu_f16x3.py holds it to 1.5 x).  Launches are counted under the same profiling id.
 #include "gemm_common.h"
+#include "split_f16.h"
 #include <stdlib.h>
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -45,6 +55,15 @@ __global__ __launch_bounds__(256) void split_bf16x2_kernel(const float* __restri
         reinterpret_cast<uint2*>(lo)[i] = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
     }
 }
+// the f16 form: (h1, h2) planes of x * scale * row_scale[row] (split_f16.h); both scales are powers of two chosen by the caller
+__global__ __launch_bounds__(256) void split_f16x2_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, float scale,
+                                                          const float* __restrict__ row_scale, unsigned short* __restrict__ h1, unsigned short* __restrict__ h2) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / K4; const int c4 = (int)(i - row * K4);
+        const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
+        store_f16_planes4(h1, h2, (size_t)i, v, row_scale ? scale * row_scale[row] : scale);
+    }
+}
 
 constexpr int BK = 32;                      // bf16 per K tile = 64-byte rows
 constexpr int LROW = 40;                    // bf16 per LDS row: 32 + 8 pad (80-byte pitch: conflict-free ds_read_b128 / ds_write_b128)
@@ -55,9 +74,18 @@ struct X3Params {
     unsigned short *Oh, *Ol;                   // optional: the result ALSO / INSTEAD as (hi, lo) bf16 planes [M][N] -- the A operand of the next split-bf16 product
     int M, N, K;
     act_gemm_epilogue_t epi;
+    const float* b_inv; float a_inv, o_scale;  // F16 form: 1 / s_B[n], 1 / s_A, and the scale the planes-out are split at (the next product's s_A)
 };
 
-template <int BM, int BN, int ACT, bool PLANES>
+// one MFMA of two 16-bit fragments (8 per lane), bf16 or f16 by the plane format
+template <bool F16>
+__device__ __forceinline__ f32x4 x3_mfma(const bf16x8& b, const bf16x8& a, const f32x4& c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b), __builtin_bit_cast(f16x8, a), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
+}
+
+// F16: f16 planes, the two cross terms in a second accumulator set (acc[1]), scales divided out in the epilogue; otherwise bf16 planes and one accumulator set
+template <int BM, int BN, int ACT, bool PLANES, bool F16>
 __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params p) {
     constexpr int TM = BM / 32, TN = BN / 32;                 // 16 x 16 tiles per wave (2 x 2 waves)
     constexpr int PA = BM * LROW, PB = BN * LROW;             // bf16 per plane image
@@ -79,11 +107,14 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int K = p.K, ntiles = K / BK, last = ntiles - 1;
 
-    f32x4 acc[TM][TN];
+    constexpr int X = F16 ? 1 : 0;                            // accumulator set of the cross terms
+    f32x4 acc[X + 1][TM][TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int x = 0; x <= X; ++x)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[x][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int srow = tid >> 2, sch = tid & 3;                 // staging: (row, 16-byte chunk) of a [rows][32 bf16] plane tile
     const size_t goa = (size_t)(m0 + srow) * K + sch * 8, gob = (size_t)(n0 + srow) * K + sch * 8;
@@ -114,9 +145,9 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
             _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) bf[s_] = *reinterpret_cast<const bf16x8*>(&Bs_[s_ * PB + b_off + j_ * 16 * LROW]); \
             /* smallest terms first: lo.hi, hi.lo, hi.hi.  The B fragment is the MFMA's FIRST operand: the 16 x 16 result block comes out transposed in the   */ \
             /* register layout (lane (r, g) holds row r, columns 4g .. 4g+3), i.e. every lane owns FOUR CONSECUTIVE COLUMNS of one row -> vector epilogue  */ \
-            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0], af[i_][1], acc[i_][j_], 0, 0, 0); \
-            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[1], af[i_][0], acc[i_][j_], 0, 0, 0); \
-            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[i_][j_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[0], af[i_][0], acc[i_][j_], 0, 0, 0); \
+            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[X][i_][j_] = x3_mfma<F16>(bf[0], af[i_][1], acc[X][i_][j_]);           \
+            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[X][i_][j_] = x3_mfma<F16>(bf[1], af[i_][0], acc[X][i_][j_]);           \
+            _Pragma("unroll") for (int i_ = 0; i_ < TM; ++i_) acc[0][i_][j_] = x3_mfma<F16>(bf[0], af[i_][0], acc[0][i_][j_]);           \
         }                                                                                                                              \
     }
     // loads / stores are unconditional: past the end they re-read the last K tile and fill a stage nobody reads (no divergent code around the staging registers)
@@ -139,6 +170,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
 #undef X3_COMPUTE
     // epilogue: lane (r, g) holds row i*16 + r, columns j*16 + 4g .. 4g+3 of its wave's 64 x 64 block (operands swapped above): one float4 of bias / residual /
     // result and one 8-byte store per plane, per 16 x 16 block; same per-element arithmetic and order as the f32 kernels (epilogue_apply4_act)
+    // F16: v = (acc0 + 2^-11 acc1) / s_B[n] / s_A first -- two multiplications by powers of two, exact -- then the same epilogue
     const bool vec = (((uintptr_t)p.C | (uintptr_t)p.epi.bias | (uintptr_t)p.epi.res | (uintptr_t)p.epi.aux) & 15) == 0 &&
                      ((p.ldc | (p.epi.res ? p.epi.ldr : 0) | (p.epi.aux ? p.epi.ldaux : 0)) & 3) == 0;
 #pragma unroll
@@ -147,7 +179,13 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
         for (int j = 0; j < TN; ++j) {
             const int row = m0 + wm * (BM / 2) + i * 16 + r;
             const int col = n0 + wn * (BN / 2) + j * 16 + g * 4;
-            float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+            float4 v = make_float4(acc[0][i][j][0], acc[0][i][j][1], acc[0][i][j][2], acc[0][i][j][3]);
+            if constexpr (F16) {
+                const float4 bi = *reinterpret_cast<const float4*>(p.b_inv + col);           // 16-byte aligned (launcher), col % 4 == 0
+                constexpr float W = 1.0f / 2048.0f;
+                v.x = __builtin_fmaf(acc[1][i][j][0], W, v.x) * bi.x * p.a_inv; v.y = __builtin_fmaf(acc[1][i][j][1], W, v.y) * bi.y * p.a_inv;
+                v.z = __builtin_fmaf(acc[1][i][j][2], W, v.z) * bi.z * p.a_inv; v.w = __builtin_fmaf(acc[1][i][j][3], W, v.w) * bi.w * p.a_inv;
+            }
             if (vec) v = epilogue_apply4_act<ACT>(p.epi, v, row, col);
             else {
                 v.x = epilogue_apply<ACT>(p.epi, v.x, row, col); v.y = epilogue_apply<ACT>(p.epi, v.y, row, col + 1);
@@ -157,7 +195,9 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
                 float* cp = p.C + (size_t)row * p.ldc + col;
                 if (vec) *reinterpret_cast<float4*>(cp) = v; else { cp[0] = v.x; cp[1] = v.y; cp[2] = v.z; cp[3] = v.w; }
             }
-            if constexpr (PLANES) {
+            if constexpr (PLANES && F16) {
+                store_f16_planes4(p.Oh, p.Ol, ((size_t)row * p.N + col) >> 2, v, p.o_scale);
+            } else if constexpr (PLANES) {
                 const float e[4] = {v.x, v.y, v.z, v.w};
                 unsigned h[4], l[4];
 #pragma unroll
@@ -169,22 +209,22 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
         }
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool F16>
 int launch_x3(const X3Params& p, hipStream_t s) {
     const dim3 grid((p.M / BM) * (p.N / BN));
     const bool planes = p.Oh != nullptr;
     switch (p.epi.act) {
         case ACT_EPI_NONE:
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, true>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, false>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, true, F16>), grid, dim3(256), 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, false, F16>), grid, dim3(256), 0, s, p);
             break;
         case ACT_EPI_GELU:
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, true>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, false>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, true, F16>), grid, dim3(256), 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, false, F16>), grid, dim3(256), 0, s, p);
             break;
         case ACT_EPI_MUL_GELU_GRAD:                                  // (the MLP's backward through GELU: aux = the saved pre-activation)
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, true>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, false>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, true, F16>), grid, dim3(256), 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, false, F16>), grid, dim3(256), 0, s, p);
             break;
         default: return ACT_E_BADARG;
     }
@@ -224,5 +264,37 @@ extern "C" int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    return launch_x3<128, 128>(p, s);
+    return launch_x3<128, 128, false>(p, s);
+}
+
+// ---- the f16 form (default teacher path) --------------------------------------------------------------------------------------------------------------------
+extern "C" int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2,
+                                   act_stream_t stream) {
+    if (!x || !h1 || !h2) return ACT_E_NULLPTR;
+    if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || !(scale > 0.f) || (((uintptr_t)x | (uintptr_t)h1 | (uintptr_t)h2) & 15)) return ACT_E_BADARG;
+    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
+    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(split_f16x2_kernel, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, row_scale, h1, h2);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+
+extern "C" int act_sgemm_nt_f16x3_supported(int M, int N, int K) { return act_sgemm_nt_bf16x3_supported(M, N, K); }
+
+extern "C" int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                             const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                             float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
+    if (!a_h1 || !a_h2 || !b_h1 || !b_h2 || !b_inv_scale || (!C && !out_h1) || ((out_h1 == nullptr) != (out_h2 == nullptr))) return ACT_E_NULLPTR;
+    if (!act_sgemm_nt_f16x3_supported(M, N, K) || (C && ldc < N) || !(a_scale > 0.f) || (out_h1 && !(out_scale > 0.f))) return ACT_E_BADARG;
+    if ((((uintptr_t)a_h1 | (uintptr_t)a_h2 | (uintptr_t)b_h1 | (uintptr_t)b_h2 | (uintptr_t)out_h1 | (uintptr_t)out_h2 | (uintptr_t)b_inv_scale) & 15))
+        return ACT_E_BADARG;
+    X3Params p{};
+    p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = out_h1; p.Ol = out_h2;
+    p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale;
+    if (epilogue) p.epi = *epilogue; else { p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; }
+    if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
+    return launch_x3<128, 128, true>(p, s);
 }

@@ -202,6 +202,65 @@ def gemm_nt_bf16x3(a_planes, b_planes, bias=None, act=EPI_NONE, res=None, out=No
     return out
 
 
+# ---- split-f16 products (same file, F16 form): the DEFAULT arithmetic of the frozen teacher's four Linear products per layer ------------------------
+def f16x3_row_scales(w):
+    """one power of two per row of w [N, K] that lifts the row's largest magnitude into [2^14, 2^15) (1 for an all-zero row) -> (scale [N], 1 / scale [N])"""
+    mx = w.detach().abs().amax(dim=1).float()
+    e = torch.frexp(mx).exponent                                              # max = m * 2^e, m in [0.5, 1)
+    e = torch.where(mx > 0, e, torch.full_like(e, 15))
+    one = torch.ones(e.shape, dtype=torch.float32, device=w.device)
+    return torch.ldexp(one, 15 - e), torch.ldexp(one, e - 15)
+
+
+def split_f16x2(x, scale=1.0, row_scale=None, out=None):
+    """fp32 [R, K] -> f16 planes [2, R, K] of xs = x * scale * row_scale[row] (powers of two): h1 = f16(xs), h2 = f16((xs - h1) * 2^11), round to nearest
+    even, a plane element below 2^-14 written as +0 before the residual is taken (csrc/split_f16.h; tests/f16x3_ref.py restates it)."""
+    x = _f32rows(x, "x")
+    R, Kd = x.shape
+    if out is None:
+        out = torch.empty(2, R, Kd, dtype=torch.float16, device=x.device)
+    check(lib.act_split_f16x2_f32(_C.ptr_rows(x), R, Kd, x.stride(0), float(scale), ptr(_f32c(row_scale)) if row_scale is not None else None,
+                                  ptr(out[0]), ptr(out[1]), stream()), "act_split_f16x2_f32")
+    return out
+
+
+def layernorm_f16_planes(x, gamma, beta, eps, scale, pos=None):
+    """LN(x + pos) * gamma + beta written as f16 planes [2, T, D] at ``scale`` (bit-identical to split_f16x2(layernorm_fwd(...), scale))"""
+    x = _f32c(x)
+    T, D = x.shape
+    planes = torch.empty(2, T, D, dtype=torch.float16, device=x.device)
+    check(lib.act_layernorm_fwd_f16_planes_f32(ptr(x), ptr(_f32c(pos)) if pos is not None else None, ptr(gamma), ptr(beta), None, None, ptr(planes[0]),
+                                               ptr(planes[1]), float(scale), None, None, T, D, float(eps), stream()), "act_layernorm_fwd_f16_planes_f32")
+    return planes
+
+
+def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_NONE, res=None, out=None, planes_out=None, out_scale=1.0):
+    """C[M,N] = epilogue((a . b^T) / a_scale / b_scale[n]) with both operands as f16 planes [2, rows, K] (split_f16x2: a at the scalar ``a_scale``, b at
+    f16x3_row_scales) and the products h1.h1 + 2^-11 (h1.h2 + h2.h1) on the f16 matrix cores, two fp32 accumulators: fp32-grade.  M, N % 128 == 0,
+    K % 64 == 0.  ``planes_out`` [2, M, N] f16: the result also as planes at ``out_scale`` -- the A operand of a following product."""
+    _, M, Kd = a_planes.shape
+    _, N, Kb = b_planes.shape
+    if Kd != Kb or a_planes.dtype != torch.float16 or b_planes.dtype != torch.float16 or not (a_planes.is_contiguous() and b_planes.is_contiguous()):
+        raise _C.ActHipError("gemm_nt_f16x3: contiguous f16 planes [2, rows, K] with equal K expected")
+    if not lib.act_sgemm_nt_f16x3_supported(M, N, Kd):
+        raise _C.ActHipError(f"gemm_nt_f16x3: unsupported shape {M} x {N} x {Kd} (M, N % 128, K % 64)")
+    b_inv_scale = _f32c(b_inv_scale)
+    if b_inv_scale.numel() != N:
+        raise _C.ActHipError("gemm_nt_f16x3: b_inv_scale must hold one value per row of b")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a_planes.device)
+    e = GemmEpilogue(alpha=1.0, act=act, accumulate=0, rows_per_scale=0, ldr=(res.stride(0) if res is not None else 0), ldaux=0, res_row_div=0,
+                     bias=ptr(bias), rowscale=None, res=ptr(res), aux=None)
+    oh, ol = (None, None)
+    if planes_out is not None:
+        if planes_out.dtype != torch.float16 or tuple(planes_out.shape) != (2, M, N) or not planes_out.is_contiguous():
+            raise _C.ActHipError("gemm_nt_f16x3: planes_out must be a contiguous f16 tensor [2, M, N]")
+        oh, ol = ptr(planes_out[0]), ptr(planes_out[1])
+    check(lib.act_sgemm_nt_f16x3_planes_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]), ptr(b_inv_scale),
+                                            ptr(out), out.stride(0), oh, ol, float(out_scale), ctypes.byref(e), stream()), "act_sgemm_nt_f16x3_planes_f32")
+    return out
+
+
 # ---- GEMM autotuner: the step has ~40 distinct (layout, M, N, K) shapes; each is timed once (tile shape x split-K) on first
 # use -- i.e. during the warm-up steps -- and the winner is cached, so steady-state steps never synchronise.
 _GEMM_CACHE = {}

@@ -420,6 +420,24 @@ int act_attention_fwd_prefix_planes_f32(const float* kv0, int S0, const float* q
 int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
                                    float* C, int ldc, uint16_t* out_hi, uint16_t* out_lo, const act_gemm_epilogue_t* epilogue, act_stream_t stream);
 
+/* ---- DEFAULT teacher arithmetic: the same kernel on f16 planes with a scaled low plane ("f16x3", csrc/gemm_bf16x3.hip F16 form, csrc/split_f16.h) ----
+ * x s = h1 + 2^-11 h2 with h1 = f16(x s), h2 = f16((x s - h1) 2^11) (round to nearest even; a plane element below 2^-14 is written as +0 before the
+ * residual is taken), s a power of two that keeps |x s| <= 2^15: 22 significand bits + the residual's sign per operand, fp32-grade products.
+ * C = epilogue( (A_h1.B_h1^T + 2^-11 (A_h1.B_h2^T + A_h2.B_h1^T)) * b_inv_scale[n] / a_scale ), two fp32 accumulators, lo.lo term (2^-22) dropped.
+ * act_split_f16x2_f32: planes of x * scale * row_scale[row] (row_scale nullable).  b_inv_scale [N] = 1 / (B's row scales), 16-byte aligned.
+ * out_h1 / out_h2 (nullable pair): the result also (C != NULL) or only as planes [M][N] of result * out_scale.  Shapes as act_sgemm_nt_bf16x3_supported. */
+int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2, act_stream_t stream);
+int act_sgemm_nt_f16x3_supported(int M, int N, int K);
+int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                  const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2, float out_scale,
+                                  const act_gemm_epilogue_t* epilogue, act_stream_t stream);
+/* the plane producers in this format: bit-identical to producing fp32 and splitting it with act_split_f16x2_f32 at plane_scale */
+int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
+                                     uint16_t* y_h1, uint16_t* y_h2, float plane_scale, float* mean /* nullable */, float* rstd /* nullable */, int T, int D,
+                                     float eps, act_stream_t stream);
+int act_attention_fwd_prefix_f16_planes_f32(const float* kv0, int S0, const float* qkv1, int Sq, float* out, uint16_t* out_h1, uint16_t* out_h2,
+                                            float plane_scale, float* lse, int B, int H, int head_dim, float scale, act_stream_t stream);
+
 /* ---- GEMM launch-configuration table (host side) ------------------------------------------------------------------------
  * act_sgemm_f32 (no explicit configuration) first consults this table keyed by (a_kmajor, b_kmajor, M, N, K), then its built-in
  * cost model.  The Python host fills it from the shipped tune file and from first-use timing (act_amd/kernels.py); the composite
@@ -580,6 +598,20 @@ int act_prefix_block_bwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_
                                     size_t workspace_bytes, act_stream_t stream);
 int act_prefix_vit_fwd_f32(const act_prefix_vit_t* m, const float* tokens, const float* center, float* out, float* scratch,
                            float* workspace, size_t workspace_bytes, act_stream_t stream);
+/* DEFAULT on the host side (ACT_TEACHER_F16X3, 0 restores act_prefix_vit_fwd_f32): the FOUR Linear products of every block (qkv, proj, fc1, fc2 on the patch
+ * tokens) on the split-f16 kernel; the prompts' keys / values stay on act_prompt_kv_fwd_f32.  w_planes[4 i + j] = h1 plane of block i's j-th weight, split
+ * with one power of two per output row (h2 plane rows * cols elements further); w_inv_scale[4 i + j] = the N inverse row scales (device); a_scale[4 i + j]
+ * (HOST) = the static activation scale s_A of that Linear, from a weight-only bound on its operand (bound * s_A <= 2^15: overflow impossible by
+ * construction), or 0: that Linear stays on the f32 kernel, as does any shape the kernel does not take.  a_planes as in act_vit_bf16x3_t. */
+typedef struct {
+    const uint16_t* const* w_planes;          /* [4 * depth] */
+    const float* const* w_inv_scale;          /* [4 * depth] */
+    const float* a_scale;                     /* [4 * depth], host memory */
+    uint16_t* a_planes;
+    size_t a_planes_elems;
+} act_vit_f16x3_t;
+int act_prefix_vit_fwd_f16x3_f32(const act_prefix_vit_t* m, const act_vit_f16x3_t* x3, const float* tokens, const float* center, float* out,
+                                 float* scratch, float* workspace, size_t workspace_bytes, act_stream_t stream);
 
 /* mini-PointNet patch embedding (Encoder, models/dvae.py:185-215) on rows = points: x [BG*n, 3] -> tokens [BG, C].
  * conv 3->128, BN, ReLU, conv 128->256, max over the n points of a group, conv 512->512 on cat(global, local) (the global half
