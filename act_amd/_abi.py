@@ -310,6 +310,11 @@ _TABLE = {
     "act_group_rows_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "act_group_gather_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "act_group_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
+    # PointNet++ feature propagation at any size (csrc/sa.hip)
+    "act_three_nn_any_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "act_three_adj_i32": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "act_interp_rows_any_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_rows_any_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -314,3 +314,167 @@ extern "C" int act_group_gather_bwd_f32(const float* dout, const int32_t* idx, i
     hipLaunchKernelGGL(group_gather_bwd_kernel, dim3(cdiv(N, 256), C, B), dim3(256), 0, s, dout, off, ent, C, N, (int)E, dfeatures);
     ACT_LAUNCH_CHECK(); return 0;
 }
+
+// ---- feature propagation at any size (reference pointnet2_utils.py:262-312; upstream pointnet2_ops three_nn / three_interpolate) --------------
+// Three nearest known points of every unknown point.  One lane per unknown point; the known cloud streams through LDS in tiles of SA_NN_TILE
+// points (every lane reads the same words: broadcast, no bank conflicts), the three best (d2, index) pairs stay in registers.  Same distance,
+// same strict '<' insertion over ascending indices and same weight arithmetic as three_nn_kernel of seg.hip, so at 3 <= m <= 512 the two agree
+// bit for bit.  m < 3: the slots that never fill keep idx 0 and d2 = +inf, so r = 1 / (inf + 1e-8) = 0 and their weight is exactly 0 while the
+// others are normalised over what exists (m == 1: r0 / r0 = 1).
+#define SA_NN_TILE 1024
+__global__ __launch_bounds__(256) void three_nn_any_kernel(const float* __restrict__ unknown, const float* __restrict__ known, int n, int m,
+                                                           int32_t* __restrict__ idx, float* __restrict__ wout, float* __restrict__ d2out) {
+    __shared__ float sc[SA_NN_TILE * 3];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;
+    const size_t p = (size_t)b * n + (live ? i : n - 1);               // idle lanes of the last block walk the last point and write nothing
+    const float px = unknown[p * 3 + 0], py = unknown[p * 3 + 1], pz = unknown[p * 3 + 2];
+    const float* kb = known + (size_t)b * m * 3;
+    float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
+    int i0 = 0, i1 = 0, i2 = 0;
+    for (int t0 = 0; t0 < m; t0 += SA_NN_TILE) {
+        const int cnt = min(SA_NN_TILE, m - t0);
+        __syncthreads();                                                 // the previous tile has been walked
+        for (int j = threadIdx.x; j < cnt * 3; j += 256) sc[j] = kb[(size_t)t0 * 3 + j];
+        __syncthreads();
+        // one point per step.  (Four points per step behind one compare of their minimum measured 30 - 50 % SLOWER: the branch is per wave,
+        // and with 64 lanes some lane has a candidate in almost every group of four, so the wave ran all four insertions almost every time.)
+#pragma unroll 4
+        for (int g = 0; g < cnt; ++g) {
+            const float d = sqdist3(px, py, pz, sc[g * 3 + 0], sc[g * 3 + 1], sc[g * 3 + 2]);
+            if (d < d2) {
+                const int gi = t0 + g;
+                if (d < d1) {
+                    d2 = d1; i2 = i1;
+                    if (d < d0) { d1 = d0; i1 = i0; d0 = d; i0 = gi; }
+                    else { d1 = d; i1 = gi; }
+                } else { d2 = d; i2 = gi; }
+            }
+        }
+    }
+    if (!live) return;
+    const float r0 = __fdiv_rn(1.0f, __fadd_rn(d0, 1e-8f)), r1 = __fdiv_rn(1.0f, __fadd_rn(d1, 1e-8f)), r2 = __fdiv_rn(1.0f, __fadd_rn(d2, 1e-8f));
+    const float s = __fadd_rn(__fadd_rn(r0, r1), r2);
+    idx[p * 3 + 0] = i0; idx[p * 3 + 1] = i1; idx[p * 3 + 2] = i2;
+    wout[p * 3 + 0] = __fdiv_rn(r0, s); wout[p * 3 + 1] = __fdiv_rn(r1, s); wout[p * 3 + 2] = __fdiv_rn(r2, s);
+    if (d2out) { d2out[p * 3 + 0] = d0; d2out[p * 3 + 1] = d1; d2out[p * 3 + 2] = d2; }
+}
+
+extern "C" int act_three_nn_any_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2,
+                                    int32_t* adj_off, int32_t* adj_ent, act_stream_t stream) {
+    if (!unknown || !known || !idx || !weight) return ACT_E_NULLPTR;
+    if ((adj_off == nullptr) != (adj_ent == nullptr)) return ACT_E_NULLPTR;
+    if (B <= 0 || B > 65535 || n <= 0 || m <= 0) return ACT_E_BADARG;
+    if (3LL * n > 0x7fffffffLL) return ACT_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    {
+        ActProfScope ps(KID_ELTWISE, s, 9.0 * B * (double)n * m, 4.0 * B * ((double)n * 9 + (double)m * 3));
+        hipLaunchKernelGGL(three_nn_any_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, s, unknown, known, n, m, idx, weight, d2);
+        ACT_LAUNCH_CHECK();
+    }
+    return adj_off ? build_adjacency(idx, B, m, 3 * n, adj_off, adj_ent, s) : 0;
+}
+
+// the inverse adjacency alone, for caller-supplied indices (three_interpolate): off [B,m+1], ent [B,3n]; an index outside [0,m) is in no list
+extern "C" int act_three_adj_i32(const int32_t* idx, int B, int n, int m, int32_t* adj_off, int32_t* adj_ent, act_stream_t stream) {
+    if (!idx || !adj_off || !adj_ent) return ACT_E_NULLPTR;
+    if (B <= 0 || B > 65535 || n <= 0 || m <= 0 || 3LL * n > 0x7fffffffLL) return ACT_E_BADARG;
+    return build_adjacency(idx, B, m, 3 * n, adj_off, adj_ent, (hipStream_t)stream);
+}
+
+// Row interpolation with skipped slots: Y[b*N+n, :] = sum over the slots k with w[n,k] != 0 and idx[n,k] in [0,G) of w[n,k] * P[b*G + idx[n,k], :],
+// the sum in slot order as w0*a, then fma, then fma (the order of interp_fwd_kernel of seg.hip).  A skipped slot is never read, so a
+// non-finite row behind a weight of exactly 0 cannot reach the result.  V = float4 when C % 4 == 0 and the rows are 16-byte aligned, else float.
+__device__ __forceinline__ float vmul(float w, float v) { return w * v; }
+__device__ __forceinline__ float vfma(float w, float v, float a) { return fmaf(w, v, a); }
+__device__ __forceinline__ float4 vmul(float w, float4 v) { return make_float4(w * v.x, w * v.y, w * v.z, w * v.w); }
+__device__ __forceinline__ float4 vfma(float w, float4 v, float4 a) {
+    return make_float4(fmaf(w, v.x, a.x), fmaf(w, v.y, a.y), fmaf(w, v.z, a.z), fmaf(w, v.w, a.w));
+}
+__device__ __forceinline__ void vzero(float& v) { v = 0.f; }
+__device__ __forceinline__ void vzero(float4& v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
+
+template <typename V>
+__global__ __launch_bounds__(256) void interp_any_fwd_kernel(const V* __restrict__ P, const int32_t* __restrict__ idx, const float* __restrict__ w,
+                                                             int N, int G, int CV, long long R, V* __restrict__ Y) {
+    const long long r = (long long)blockIdx.x * 4 + threadIdx.y;        // row blocks on grid.x (up to 2^31 - 1), channel blocks on grid.y
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    if (r >= R || c >= CV) return;
+    const long long base = (r / N) * G;
+    V y;
+    vzero(y);
+    bool first = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int j = idx[r * 3 + k];
+        const float wk = w[r * 3 + k];
+        if (wk != 0.f && (unsigned)j < (unsigned)G) {
+            const V v = P[(base + j) * CV + c];
+            y = first ? vmul(wk, v) : vfma(wk, v, y);
+            first = false;
+        }
+    }
+    Y[r * CV + c] = y;
+}
+
+static bool vec4_ok(int C, const void* a, const void* b) { return !(C & 3) && !(((uintptr_t)a | (uintptr_t)b) & 15); }
+
+extern "C" int act_interp_rows_any_fwd_f32(const float* P, const int32_t* idx, const float* weight, int B, int N, int G, int C, float* Y,
+                                           act_stream_t stream) {
+    if (!P || !idx || !weight || !Y) return ACT_E_NULLPTR;
+    if (B <= 0 || N <= 0 || G <= 0 || C <= 0) return ACT_E_BADARG;
+    const long long R = (long long)B * N;
+    if (R > (1LL << 27) || C > 64 * 65535) return ACT_E_BADARG;         // 2^25 row blocks of 64 x 4 threads on grid.x, channel blocks on grid.y
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 6.0 * R * C, 4.0 * (R * (double)C * 4 + R * 6));
+    if (vec4_ok(C, P, Y))
+        hipLaunchKernelGGL(interp_any_fwd_kernel<float4>, dim3(cdiv(R, 4), cdiv(C / 4, 64)), dim3(64, 4), 0, s, reinterpret_cast<const float4*>(P),
+                           idx, weight, N, G, C / 4, R, reinterpret_cast<float4*>(Y));
+    else
+        hipLaunchKernelGGL(interp_any_fwd_kernel<float>, dim3(cdiv(R, 4), cdiv(C, 64)), dim3(64, 4), 0, s, P, idx, weight, N, G, C, R, Y);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+
+// dP[b*G+g, :] = sum over the entries e of known point g (increasing e) with w[e] != 0 of w[e] * dY[b*N + e/3, :]: interp_bwd_kernel of seg.hip
+// with the skip, at any C.  Entries are bounded by the adjacency builder (0 <= e < 3N).
+template <typename V>
+__global__ __launch_bounds__(256) void interp_any_bwd_kernel(const V* __restrict__ dY, const int32_t* __restrict__ off, const int32_t* __restrict__ ent,
+                                                             const float* __restrict__ w, int N, int G, int CV, long long RG, V* __restrict__ dP) {
+    const long long rg = (long long)blockIdx.x * 4 + threadIdx.y;
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    if (rg >= RG || c >= CV) return;
+    const long long b = rg / G;
+    const int g = (int)(rg - b * G);
+    const int32_t* ob = off + b * ((long long)G + 1);
+    const int32_t* eb = ent + b * 3LL * N;
+    const float* wb = w + b * 3LL * N;
+    const V* yb = dY + b * (long long)N * CV;
+    V acc;
+    vzero(acc);
+    const int e1 = min(ob[g + 1], 3 * N);                              // a caller's adjacency is never followed out of its arrays
+    for (int i = max(ob[g], 0); i < e1; ++i) {
+        const int e = eb[i];
+        if ((unsigned)e >= 3u * (unsigned)N) continue;
+        const float wt = wb[e];
+        if (wt != 0.f) acc = vfma(wt, yb[(long long)(e / 3) * CV + c], acc);
+    }
+    dP[rg * CV + c] = acc;
+}
+
+extern "C" int act_interp_rows_any_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N,
+                                           int G, int C, float* dP, act_stream_t stream) {
+    if (!dY || !adj_off || !adj_ent || !weight || !dP) return ACT_E_NULLPTR;
+    if (B <= 0 || N <= 0 || G <= 0 || C <= 0 || 3LL * N > 0x7fffffffLL) return ACT_E_BADARG;
+    const long long RG = (long long)B * G;
+    if (RG > (1LL << 27) || C > 64 * 65535) return ACT_E_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 6.0 * B * (double)N * C, 4.0 * ((double)B * N * C * 3 + RG * C + B * (double)N * 6));
+    if (vec4_ok(C, dY, dP))
+        hipLaunchKernelGGL(interp_any_bwd_kernel<float4>, dim3(cdiv(RG, 4), cdiv(C / 4, 64)), dim3(64, 4), 0, s,
+                           reinterpret_cast<const float4*>(dY), adj_off, adj_ent, weight, N, G, C / 4, RG, reinterpret_cast<float4*>(dP));
+    else
+        hipLaunchKernelGGL(interp_any_bwd_kernel<float>, dim3(cdiv(RG, 4), cdiv(C, 64)), dim3(64, 4), 0, s, dY, adj_off, adj_ent, weight, N, G, C,
+                           RG, dP);
+    ACT_LAUNCH_CHECK(); return 0;
+}

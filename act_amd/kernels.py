@@ -2490,3 +2490,99 @@ class GroupingOperationFn(torch.autograd.Function):
 
 def grouping_operation(features, idx):
     return GroupingOperationFn.apply(features, idx)
+
+
+# ---- PointNet++ feature propagation at any size (csrc/sa.hip): general three-NN, adjacency, interpolation with skipped slots -------------------
+def three_nn_any(unknown, known, want_adj=True, want_d2=False):
+    """unknown [B,n,3], known [B,m,3], any n >= 1 and m >= 1 -> (idx int32 [B,n,3], weight [B,n,3], adj_off int32 [B,m+1] | None, adj_ent int32
+    [B,3n] | None), plus d2 [B,n,3] with ``want_d2``: ``three_nn`` without the 3 <= G <= 512 limit, bit-identical to it where both apply.
+    m < 3: the missing slots carry idx 0, d2 = +inf and weight exactly 0 (the reference's S == 2 / S == 1 forms); ``interp_rows_any`` skips
+    them."""
+    unknown = _sa_f32(unknown, "three_nn_any: unknown", (None, None, 3))
+    B, n, _ = unknown.shape
+    known = _sa_f32(known, "three_nn_any: known", (B, None, 3))
+    m = known.shape[1]
+    if B < 1 or n < 1 or m < 1:
+        raise _C.ActHipError(f"three_nn_any: unknown {list(unknown.shape)} / known {list(known.shape)} must not be empty")
+    dev = unknown.device
+    idx = torch.empty(B, n, 3, dtype=torch.int32, device=dev)
+    w = torch.empty(B, n, 3, dtype=torch.float32, device=dev)
+    d2 = torch.empty(B, n, 3, dtype=torch.float32, device=dev) if want_d2 else None
+    off = torch.empty(B, m + 1, dtype=torch.int32, device=dev) if want_adj else None
+    ent = torch.empty(B, 3 * n, dtype=torch.int32, device=dev) if want_adj else None
+    check(lib.act_three_nn_any_f32(ptr(unknown), ptr(known), B, n, m, ptr(idx), ptr(w), ptr(d2), ptr(off), ptr(ent), stream()),
+          "act_three_nn_any_f32")
+    return (idx, w, off, ent, d2) if want_d2 else (idx, w, off, ent)
+
+
+def three_adjacency(idx, m):
+    """idx int [B,n,3] with values in [0,m) -> (adj_off int32 [B,m+1], adj_ent int32 [B,3n]): the inverse adjacency of caller-supplied indices"""
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+        raise _C.ActHipError("three_adjacency: idx: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 3 or idx.shape[2] != 3 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise _C.ActHipError(f"three_adjacency: idx: expected int32 [B, n, 3], got {idx.dtype} {list(idx.shape)}")
+    if int(m) < 1:
+        raise _C.ActHipError(f"three_adjacency: m must be >= 1, got {m}")
+    idx = _i32c(idx)
+    B, n, _ = idx.shape
+    off = torch.empty(B, int(m) + 1, dtype=torch.int32, device=idx.device)
+    ent = torch.empty(B, 3 * n, dtype=torch.int32, device=idx.device)
+    check(lib.act_three_adj_i32(ptr(idx), B, n, int(m), ptr(off), ptr(ent), stream()), "act_three_adj_i32")
+    return off, ent
+
+
+def interp_rows_any_fwd(P, idx, w, B, N, G):
+    """P [B*G,C], any C >= 1 -> Y [B*N,C] = sum over the slots of non-zero weight of w * P[idx]"""
+    P = _sa_f32(P, "interp_rows_any_fwd: P", (B * G, None))
+    w = _sa_f32(w, "interp_rows_any_fwd: weight", (B, N, 3))
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or tuple(idx.shape) != (B, N, 3) or idx.dtype not in (torch.int32, torch.int64):
+        raise _C.ActHipError(f"interp_rows_any_fwd: idx: expected a CUDA int32 [{B}, {N}, 3]")
+    C = P.shape[1]
+    if B < 1 or N < 1 or G < 1 or C < 1:
+        raise _C.ActHipError("interp_rows_any_fwd: B, N, G and C must be >= 1")
+    idx = _i32c(idx)
+    Y = torch.empty(B * N, C, dtype=torch.float32, device=P.device)
+    check(lib.act_interp_rows_any_fwd_f32(ptr(P), ptr(idx), ptr(w), B, N, G, C, ptr(Y), stream()), "act_interp_rows_any_fwd_f32")
+    return Y
+
+
+def interp_rows_any_bwd(dY, off, ent, w, B, N, G):
+    dY = _sa_f32(dY, "interp_rows_any_bwd: dY", (B * N, None))
+    w = _sa_f32(w, "interp_rows_any_bwd: weight", (B, N, 3))
+    for t, name, count in ((off, "adj_off", B * (G + 1)), (ent, "adj_ent", 3 * B * N)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _C.ActHipError(f"interp_rows_any_bwd: {name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+        if t.dtype not in (torch.int32, torch.int64) or t.numel() != count:
+            raise _C.ActHipError(f"interp_rows_any_bwd: {name}: expected {count} int32 entries for B, N, G = {B}, {N}, {G}, got {t.dtype} "
+                                 f"{list(t.shape)}")
+    off, ent = _i32c(off), _i32c(ent)
+    C = dY.shape[1]
+    dP = torch.empty(B * G, C, dtype=torch.float32, device=dY.device)
+    check(lib.act_interp_rows_any_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_any_bwd_f32")
+    return dP
+
+
+class InterpRowsAnyFn(torch.autograd.Function):
+    """InterpRowsFn at any G and C, with caller-supplied or kernel weights: x [B*G,C] -> [B*N,C].  Slots of weight exactly 0 are skipped in both
+    directions.  The backward gathers over the inverse adjacency (built here when ``nn3`` carries none): deterministic, bit-identical run to
+    run.  Indices and weights are constants: the cloud is a leaf."""
+
+    @staticmethod
+    def forward(ctx, x, nn3, B, N, G):
+        idx, w, off, ent = nn3
+        y = interp_rows_any_fwd(x, idx, w, B, N, G)
+        ctx.nn3 = (idx, w, off, ent)
+        ctx.dims = (B, N, G)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, w, off, ent = ctx.nn3
+        if off is None:
+            off, ent = three_adjacency(idx, ctx.dims[2])
+        return interp_rows_any_bwd(dy, off, ent, w, *ctx.dims), None, None, None, None
+
+
+def interp_rows_any(x, nn3, B, N, G):
+    """x [B*G,C] rows of the known points, nn3 = (idx, weight, adj_off | None, adj_ent | None) -> [B*N,C]; differentiable in ``x``"""
+    return InterpRowsAnyFn.apply(x, nn3, B, N, G)

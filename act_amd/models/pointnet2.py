@@ -14,6 +14,10 @@ Deviations from the reference, all documented in README "PointNet++ set abstract
   * distances are the fp32 difference form (dx*dx + dy*dy) + dz*dz, the project's convention, not the expansion form; the threshold is the
     fp32 product radius * radius.
   * a centre with no point in reach (impossible when the centres are cloud points) groups point 0; the reference would index out of range.
+
+The decoder half: ``PointNetFeaturePropagation`` is the Transformer segmentation head's class (models/semseg.py: row layout, xyz as points1,
+3 <= G <= 512 centres); ``PointNetFeaturePropagationAny`` below takes the reference's call shape at any N and S >= 1 (README "PointNet++
+feature propagation and networks").
 """
 import torch
 import torch.nn as nn
@@ -148,3 +152,47 @@ class PointNetSetAbstractionMsg(nn.Module):
             rows = _chain(rows, self.conv_blocks[k], self.bn_blocks[k], self.training, first_weight=w0)
             outs.append(K.group_max(rows, ns).view(B, S, -1))
         return new_xyz.transpose(1, 2), torch.cat(outs, dim=-1).transpose(1, 2)
+
+
+class PointNetFeaturePropagationAny(nn.Module):
+    """pointnet2_utils.PointNetFeaturePropagation with the reference's call shape, at any size: parameters ``mlp_convs.{i}`` (Conv1d) /
+    ``mlp_bns.{i}`` (BatchNorm1d), so reference checkpoints load with ``strict=True``.
+
+        forward(xyz1 [B,3,N], xyz2 [B,3,S], points1 [B,D1,N] or None, points2 [B,D2,S]) -> [B, mlp[-1], N]
+
+    Any N >= 1 and S >= 1: the three nearest of the S known points by K.three_nn_any (difference-form distances, ties to the lower index),
+    inverse-distance weights normalised over the slots that exist (S == 2: two columns; S == 1: the single row repeated), then the MLP on
+    cat(points1, interpolated) as rows with train-mode BatchNorm over all B*N rows.  The weights are constants: the cloud is a leaf."""
+
+    def __init__(self, in_channel, mlp):
+        super().__init__()
+        _check_mlp("PointNetFeaturePropagationAny", mlp)
+        self.mlp_convs = nn.ModuleList()
+        self.mlp_bns = nn.ModuleList()
+        last = in_channel
+        for out in mlp:
+            self.mlp_convs.append(nn.Conv1d(last, out, 1))
+            self.mlp_bns.append(nn.BatchNorm1d(out))
+            last = out
+
+    def forward(self, xyz1, xyz2, points1, points2):
+        name = "PointNetFeaturePropagationAny"
+        if points2 is None:
+            raise _C.ActHipError(f"{name}: points2: expected [B, D2, S], got None")
+        D1 = 0 if points1 is None else (points1.shape[1] if isinstance(points1, torch.Tensor) and points1.dim() == 3 else -1)
+        D2 = points2.shape[1] if isinstance(points2, torch.Tensor) and points2.dim() == 3 else -1
+        cin = self.mlp_convs[0].in_channels
+        if D1 >= 0 and D2 >= 0 and D1 + D2 != cin:
+            raise _C.ActHipError(f"{name}: in_channel: the first conv takes {cin} channels but points1 + points2 carry {D1} + {D2}")
+        x1, p1 = _inputs(name, xyz1, points1, 3 + D1)
+        x2, p2 = _inputs(name, xyz2, points2, 3 + D2)
+        B, N, _ = x1.shape
+        S = x2.shape[1]
+        if x2.shape[0] != B:
+            raise _C.ActHipError(f"{name}: xyz2: expected {B} clouds, got {x2.shape[0]}")
+        nn3 = K.three_nn_any(x1, x2, want_adj=torch.is_grad_enabled() and p2.requires_grad)
+        rows = K.interp_rows_any(p2.reshape(B * S, D2), nn3, B, N, S)
+        if p1 is not None:
+            rows = torch.cat((p1.reshape(B * N, D1), rows), dim=1)
+        rows = _chain(rows, self.mlp_convs, self.mlp_bns, self.training)
+        return rows.view(B, N, -1).transpose(1, 2)

@@ -1,7 +1,7 @@
 """Drop-in for the pointnet2_ops entry points: ``furthest_point_sample`` and ``gather_operation`` (the two ACT uses, utils/misc.py:44-45),
 backed by act_fps_f32 / act_gather_points_f32, and the grouping family of a PointNet++ baseline -- ``ball_query``, ``grouping_operation``,
-``QueryAndGroup``, ``GroupAll`` -- backed by csrc/sa.hip (include/act_hip.h).  ``three_nn`` / ``three_interpolate`` in upstream's form
-(distances, not weights) are not provided: the project's three-NN kernel (kernels.three_nn) returns the normalised weights."""
+``QueryAndGroup``, ``GroupAll`` -- backed by csrc/sa.hip (include/act_hip.h), and ``three_nn`` / ``three_interpolate`` in upstream's form
+(distances and caller-supplied weights) on the general three-NN and interpolation kernels of the same file."""
 import torch
 import torch.nn as nn
 
@@ -128,3 +128,61 @@ class GroupAll(nn.Module):
             return grouped_xyz
         grouped = features.unsqueeze(2)
         return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
+
+
+def three_nn(unknown, known):
+    """upstream's signature: unknown [B,n,3], known [B,m,3] -> (dist [B,n,3] = sqrt(d2), idx int32 [B,n,3]): the three nearest known points in
+    ascending (distance, index) order, equal distances to the lower index.  m < 3: the missing slots carry dist = +inf and idx 0.
+    Non-differentiable."""
+    from .. import kernels as K
+    for t, name in ((unknown, "unknown"), (known, "known")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError(f"three_nn: {name} must be [B, {'n' if name == 'unknown' else 'm'}, 3], got {list(getattr(t, 'shape', ()))}")
+    if unknown.shape[0] != known.shape[0]:
+        raise ValueError(f"three_nn: unknown has {unknown.shape[0]} clouds, known {known.shape[0]}")
+    if unknown.shape[0] < 1 or unknown.shape[1] < 1 or known.shape[1] < 1:
+        raise ValueError(f"three_nn: unknown {list(unknown.shape)} / known {list(known.shape)} must not be empty")
+    _need(unknown, torch.float32, "unknown"); _need(known, torch.float32, "known")
+    idx, _, _, _, d2 = K.three_nn_any(unknown, known, want_adj=False, want_d2=True)
+    return torch.sqrt(d2), idx
+
+
+class ThreeInterpolate(torch.autograd.Function):
+    """upstream three_interpolate: features [B,C,m], idx int32 [B,n,3], weight [B,n,3] -> [B,C,n], out[b,:,i] = sum_k weight[b,i,k] *
+    features[b,:,idx[b,i,k]].  Differentiable in ``features`` only; the backward gathers over an inverse adjacency in ascending entry order (no
+    atomics, bit-identical run to run).  A slot of weight exactly 0 is skipped, not multiplied."""
+
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        from .. import kernels as K
+        if not isinstance(features, torch.Tensor) or features.dim() != 3:
+            raise ValueError(f"three_interpolate: features must be [B, C, m], got {list(getattr(features, 'shape', ()))}")
+        B, C, m = features.shape
+        for t, name in ((idx, "idx"), (weight, "weight")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.shape[0] != B or t.shape[2] != 3:
+                raise ValueError(f"three_interpolate: {name} must be [{B}, n, 3], got {list(getattr(t, 'shape', ()))}")
+        if idx.shape[1] != weight.shape[1]:
+            raise ValueError(f"three_interpolate: idx names {idx.shape[1]} points, weight {weight.shape[1]}")
+        _need(features, torch.float32, "features"); _need(idx, torch.int32, "idx"); _need(weight, torch.float32, "weight")
+        n = idx.shape[1]
+        if B < 1 or C < 1 or m < 1 or n < 1:
+            raise ValueError(f"three_interpolate: features {list(features.shape)} / idx {list(idx.shape)} must not be empty")
+        rows = features.transpose(1, 2).reshape(B * m, C)
+        out = K.interp_rows_any_fwd(rows, idx, weight, B, n, m)
+        ctx.save_for_backward(idx, weight)
+        ctx.dims = (B, n, m)
+        return out.view(B, n, C).transpose(1, 2).contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .. import kernels as K
+        idx, weight = ctx.saved_tensors
+        B, n, m = ctx.dims
+        C = grad_out.shape[1]
+        off, ent = K.three_adjacency(idx, m)
+        d = K.interp_rows_any_bwd(grad_out.transpose(1, 2).reshape(B * n, C), off, ent, weight, B, n, m)
+        return d.view(B, m, C).transpose(1, 2).contiguous(), None, None
+
+
+def three_interpolate(features, idx, weight):
+    return ThreeInterpolate.apply(features, idx, weight)

@@ -2,6 +2,7 @@
 
     python -m act_amd.tools.runner_partseg --root data/ShapeNetPart --ckpts act_pretrain.pth
     python -m act_amd.tools.runner_partseg --synthetic --max_steps 150
+    python -m act_amd.tools.runner_partseg --synthetic --model pointnet2_part_seg_msg      # the PointNet++ MSG baseline; any other --model: the Transformer
 
 Same arguments and defaults as the reference except ``--ckpts``, which defaults to None (the reference's default names a file of its authors'
 machine), plus ``--synthetic`` (generated shapes, act_amd.datasets.ShapeNetPartDataset.SyntheticShapeNetPart), ``--max_steps`` (stop training after
@@ -114,6 +115,14 @@ def evaluate(model, loader, device, max_batches=0):
     return part_metrics(counts[:off].cpu().numpy(), seen.cpu().numpy(), correct.cpu().numpy())
 
 
+def build_model(args):
+    """``--model pointnet2_part_seg_msg``: the PointNet++ MSG baseline (models/pointnet2_nets.py); every other value: the Transformer"""
+    if args.model == 'pointnet2_part_seg_msg':
+        from ..models.pointnet2_nets import pointnet2_part_seg_msg
+        return pointnet2_part_seg_msg(NUM_PARTS, normal_channel=False)
+    return get_model(NUM_PARTS)
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.normal:
@@ -130,7 +139,7 @@ def main(argv=None):
     print(f"The number of training data is: {len(train_set)}", flush=True)
     print(f"The number of test data is: {len(test_set)}", flush=True)
 
-    model = get_model(NUM_PARTS).to(device)
+    model = build_model(args).to(device)
     crit = get_loss()
     if args.ckpts is not None:
         model.load_model_from_ckpt(args.ckpts)

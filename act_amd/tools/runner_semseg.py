@@ -2,6 +2,7 @@
 
     python -m act_amd.tools.runner_semseg --root data/stanford_indoor3d --ckpts act_pretrain.pth
     python -m act_amd.tools.runner_semseg --synthetic --max_steps 150
+    python -m act_amd.tools.runner_semseg --synthetic --model pointnet2_sem_seg            # the PointNet++ SSG baseline; any other --model: the Transformer
 
 Same arguments and defaults as the reference, plus ``--synthetic`` (generated rooms, act_amd.datasets.S3DISDataset.SyntheticS3DIS), ``--max_steps``
 (stop training after that many steps, then evaluate once), ``--log_every``, ``--seed``, ``--eval_batches`` and ``--device_sampler`` (blocks sampled
@@ -133,6 +134,15 @@ def evaluate(model, loader, weights, device, max_batches=0):
     return m, float(loss_sum.item()) / max(n, 1)
 
 
+def build_model(args):
+    """``--model pointnet2_sem_seg``: the PointNet++ SSG baseline (models/pointnet2_nets.py) on the xyz channels the blocks carry; every other
+    value: the Transformer"""
+    if args.model == 'pointnet2_sem_seg':
+        from ..models.pointnet2_nets import pointnet2_sem_seg
+        return pointnet2_sem_seg(NUM_CLASSES, in_channel=3)
+    return get_model(NUM_CLASSES)
+
+
 def main(argv=None):
     args = parse_args(argv)
     torch.manual_seed(args.seed)
@@ -155,7 +165,7 @@ def main(argv=None):
     weights = torch.tensor(np.asarray(train_set.labelweights, dtype=np.float32), device=device)
     print(f"train samples {len(train_set)}, test samples {len(test_set)}, labelweights {np.round(train_set.labelweights, 3).tolist()}", flush=True)
 
-    model = get_model(NUM_CLASSES).to(device)
+    model = build_model(args).to(device)
     crit = get_loss()
     if args.ckpts is not None:
         model.load_model_from_ckpt(args.ckpts)

@@ -970,6 +970,23 @@ int act_group_gather_f32(const float* features, const int32_t* idx, int B, int C
 int act_group_gather_bwd_f32(const float* dout, const int32_t* idx, int B, int C, int N, int S, int nsample, float* dfeatures, void* workspace,
                              size_t workspace_bytes, act_stream_t stream);
 
+/* ---- PointNet++ feature propagation at any size (csrc/sa.hip; reference models/pointnet2_utils.py:262-312, upstream three_nn / three_interpolate) ----
+ * unknown [B,n,3], known [B,m,3], n >= 1, m >= 1, B <= 65535 -> idx int32 [B,n,3], weight fp32 [B,n,3], d2 fp32 [B,n,3] (may be NULL): the three
+ * nearest known points in ascending (difference-form distance, index) order, equal distances to the lower index, and the weights
+ * r_k / ((r0 + r1) + r2), r_k = 1 / (d2_k + 1e-8).  Slots past m (m < 3) get idx 0, d2 +inf and weight exactly 0.  At 3 <= m <= 512 every
+ * output equals act_three_nn_f32's bit for bit.  adj_off int32 [B,m+1] / adj_ent int32 [B,3n] (both or neither): per known point the entries
+ * 3 * unknown + slot that name it, ascending, built without atomics (count, exclusive scan, fill). */
+int act_three_nn_any_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2, int32_t* adj_off,
+                         int32_t* adj_ent, act_stream_t stream);
+/* the same adjacency of caller-supplied indices idx int32 [B,n,3]; an index outside [0,m) is in no list */
+int act_three_adj_i32(const int32_t* idx, int B, int n, int m, int32_t* adj_off, int32_t* adj_ent, act_stream_t stream);
+/* Y [B*N,C] = sum_k weight[.,k] * P[b*G + idx[.,k], :] over the slots with weight != 0 and idx in [0,G): a skipped slot is not read.  Any C >= 1
+ * (float4 lanes when C % 4 == 0 and the rows are 16-byte aligned).  The backward gathers dP [B*G,C] over the adjacency in ascending entry
+ * order, skipping entries of weight 0: bit-identical run to run.  B*N and B*G <= 2^27 rows (row blocks on grid.x), C <= 64 * 65535. */
+int act_interp_rows_any_fwd_f32(const float* P, const int32_t* idx, const float* weight, int B, int N, int G, int C, float* Y, act_stream_t stream);
+int act_interp_rows_any_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
+                                float* dP, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
