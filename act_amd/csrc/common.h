@@ -41,6 +41,10 @@ int act_prompt_kv_correct(const float* tok, int B, int P, int D, int N, float dr
 
 #define ACT_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
+// Single-pass statistics around a pivot element (mean = pivot + dm, var = q / n - dm^2) are kept while dm^2 <= FAR_PIVOT * var; past that the
+// subtraction cancels and the kernels of pointnet.hip and dgcnn.hip switch to a form that does not (each says which at its use).
+#define FAR_PIVOT 25.f
+
 // ---- exact fp32 helpers (one rounding per op, never contracted to FMA) -----------------------------
 __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = __fsub_rn(ax, bx), dy = __fsub_rn(ay, by), dz = __fsub_rn(az, bz);

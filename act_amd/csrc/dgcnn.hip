@@ -44,22 +44,51 @@ __global__ __launch_bounds__(256) void edge_gn_stats_kernel(const float* __restr
         part[((size_t)blockIdx.x * GN_SPLIT + blockIdx.y) * 2 + 1] = (sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3]);
     }
 }
-// stage 2: one thread per (sample, group): fold the partials (fixed order) -> mean, rstd
-__global__ void edge_gn_finalize_kernel(const float* __restrict__ yz, int ldy, int zoff, const int64_t* __restrict__ idx, int G, int k,
-                                        int C, int groups, int nbg, const float* __restrict__ part, float eps,
-                                        float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-    const int bg = blockIdx.x * blockDim.x + threadIdx.x;
-    if (bg >= nbg) return;
+// stage 2: one workgroup per (sample, group): thread 0 folds the partials (fixed order) -> mean, rstd.  var = Q / n - dm^2 cancels once the pivot lies
+// far from the mean (a first element 30 - 1000 deviations out: rstd wrong by 5e-5 - 2.8e-3, notebook/dgcnn_edges.md), so where dm^2 > FAR_PIVOT * var the whole
+// workgroup walks the group a second time around the mean it has just found -- nothing cancels, the order is fixed, and every other group keeps the
+// arithmetic above bit for bit (the workgroup leaves at once).  Serves the slab path, the generic path, the head and the tokenizer.
+__global__ __launch_bounds__(256) void edge_gn_finalize_kernel(const float* __restrict__ yz, int ldy, int zoff, const int64_t* __restrict__ idx,
+                                                               int G, int k, int C, int groups, const float* __restrict__ part, float eps,
+                                                               float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+    __shared__ float sh[2][4];
+    __shared__ float smu; __shared__ int sfar;
+    const int bg = blockIdx.x;
     const int b = bg / groups, gi = bg % groups, cpg = C / groups, c0 = gi * cpg;
-    const int r00 = idx ? (int)idx[(size_t)b * k * G] : 0;
-    const float pv = yz[((size_t)b * G + r00) * ldy + c0] + (zoff >= 0 ? yz[((size_t)b * G) * ldy + zoff + c0] : 0.f);
-    float S = 0.f, Q = 0.f;
-    for (int sp = 0; sp < GN_SPLIT; ++sp) { S += part[((size_t)bg * GN_SPLIT + sp) * 2]; Q += part[((size_t)bg * GN_SPLIT + sp) * 2 + 1]; }
     const float total = (float)G * (float)k * (float)cpg;
-    const float dm = S / total;
-    const float var = fmaxf(Q / total - dm * dm, 0.f);
-    mean_out[bg] = pv + dm;
-    rstd_out[bg] = rsqrtf(var + eps);
+    if (threadIdx.x == 0) {
+        const int r00 = idx ? (int)idx[(size_t)b * k * G] : 0;
+        const float pv = yz[((size_t)b * G + r00) * ldy + c0] + (zoff >= 0 ? yz[((size_t)b * G) * ldy + zoff + c0] : 0.f);
+        float S = 0.f, Q = 0.f;
+        for (int sp = 0; sp < GN_SPLIT; ++sp) { S += part[((size_t)bg * GN_SPLIT + sp) * 2]; Q += part[((size_t)bg * GN_SPLIT + sp) * 2 + 1]; }
+        const float dm = S / total;
+        const float var = fmaxf(Q / total - dm * dm, 0.f);
+        mean_out[bg] = pv + dm;
+        rstd_out[bg] = rsqrtf(var + eps);
+        smu = pv + dm; sfar = dm * dm > FAR_PIVOT * var;
+    }
+    __syncthreads();
+    if (!sfar) return;
+    const float mu0 = smu;
+    const long long n = (long long)G * k * cpg;
+    float s = 0.f, q = 0.f;
+    for (long long i = threadIdx.x; i < n; i += 256) {
+        const int c = (int)(i % cpg); const long long t = i / cpg; const int g = (int)(t % G); const int j = (int)(t / G);
+        const int src = idx ? (int)idx[((size_t)b * k + j) * G + g] : g;
+        float v = yz[((size_t)b * G + src) * ldy + c0 + c];
+        if (zoff >= 0) v += yz[((size_t)b * G + g) * ldy + zoff + c0 + c];
+        v -= mu0;
+        s += v; q += v * v;
+    }
+    s = wave_sum_f32(s); q = wave_sum_f32(q);
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float d2 = ((sh[0][0] + sh[0][1]) + (sh[0][2] + sh[0][3])) / total;
+        const float var = fmaxf(((sh[1][0] + sh[1][1]) + (sh[1][2] + sh[1][3])) / total - d2 * d2, 0.f);
+        mean_out[bg] = mu0 + d2;
+        rstd_out[bg] = rsqrtf(var + eps);
+    }
 }
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
@@ -183,6 +212,7 @@ __global__ __launch_bounds__(EGF_THREADS) void edge_gn_fused_kernel(const float*
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float sh[2][EGF_THREADS / 64];
     __shared__ float stat[2];
+    __shared__ int sfar;
     const int b = blockIdx.x / groups, gi = blockIdx.x % groups;
     const int cpg = C / groups, c0 = gi * cpg, cq = cpg >> 2;
     float* Ys = lds; float* Zs = lds + (size_t)G * cpg; int* Is = reinterpret_cast<int*>(lds + (size_t)2 * G * cpg);     // Is[j][g]
@@ -213,8 +243,31 @@ __global__ __launch_bounds__(EGF_THREADS) void edge_gn_fused_kernel(const float*
         const float dm = S / n, var = fmaxf(Q / n - dm * dm, 0.f);
         stat[0] = pv + dm; stat[1] = rsqrtf(var + eps);
         mean_out[blockIdx.x] = stat[0]; rstd_out[blockIdx.x] = stat[1];
+        sfar = dm * dm > FAR_PIVOT * var;
     }
     __syncthreads();
+    if (sfar) {
+        // far pivot (see edge_gn_finalize_kernel): the slice is in LDS, so the workgroup sums it once more around the mean it has just found
+        const float mu0 = stat[0];
+        s = 0.f; q = 0.f;
+        for (int i = threadIdx.x; i < total; i += EGF_THREADS) {
+            const int g = i / cpg, c = i % cpg;
+            const float z = Zs[i] - mu0;
+            for (int j = 0; j < k; ++j) { const float v = Ys[Is[j * G + g] * cpg + c] + z; s += v; q += v * v; }
+        }
+        s = wave_sum_f32(s); q = wave_sum_f32(q);
+        if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float S = 0.f, Q = 0.f;
+            for (int w = 0; w < EGF_THREADS / 64; ++w) { S += sh[0][w]; Q += sh[1][w]; }
+            const float n = (float)G * (float)k * (float)cpg;
+            const float d2 = S / n, var = fmaxf(Q / n - d2 * d2, 0.f);
+            stat[0] = mu0 + d2; stat[1] = rsqrtf(var + eps);
+            mean_out[blockIdx.x] = stat[0]; rstd_out[blockIdx.x] = stat[1];
+        }
+        __syncthreads();
+    }
     const float mu = stat[0], rs = stat[1];
     for (int i = threadIdx.x; i < total; i += EGF_THREADS) {
         const int g = i / cpg, c = i % cpg;
@@ -326,14 +379,14 @@ extern "C" int act_edge_gn_lrelu_max_f32(const float* yz, int ldy, int zoff, con
                 if (e != hipSuccess) return (int)e;
             }
             hipLaunchKernelGGL(ks, dim3(C / SW, B), dim3(256), smem, s, yz, ldy, zoff, idx, G, C, groups, mean, rstd, gamma, beta, slope, part, out, ldo, ooff);
-            hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3((B * groups + 63) / 64), dim3(64), 0, s, yz, ldy, zoff, idx, G, k, C, groups, B * groups,
+            hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3(B * groups), dim3(256), 0, s, yz, ldy, zoff, idx, G, k, C, groups,
                                part, eps, mean, rstd);
             hipLaunchKernelGGL(ka, dim3(C / SW, B), dim3(256), smem, s, yz, ldy, zoff, idx, G, C, groups, mean, rstd, gamma, beta, slope, part, out, ldo, ooff);
             ACT_LAUNCH_CHECK(); return 0;
         }
     }
     hipLaunchKernelGGL(edge_gn_stats_kernel, dim3(B * groups, GN_SPLIT), dim3(256), 0, s, yz, ldy, zoff, idx, G, k, C, groups, part);
-    hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3((B * groups + 63) / 64), dim3(64), 0, s, yz, ldy, zoff, idx, G, k, C, groups, B * groups,
+    hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3(B * groups), dim3(256), 0, s, yz, ldy, zoff, idx, G, k, C, groups,
                        part, eps, mean, rstd);
     const long long total = (long long)B * G * C;
     hipLaunchKernelGGL(edge_gn_apply_max_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, yz, ldy, zoff, idx, G, k, C, groups, mean, rstd,
@@ -709,7 +762,7 @@ extern "C" int act_gn_gumbel_argmax_gather_f32(const float* h, int B, int G, int
     float* mean = stats; float* rstd = stats + (size_t)B * groups;
     float* part = stats + (size_t)2 * B * groups;
     hipLaunchKernelGGL(edge_gn_stats_kernel, dim3(B * groups, GN_SPLIT), dim3(256), 0, s, h, C, -1, nullptr, G, 1, C, groups, part);
-    hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3((B * groups + 63) / 64), dim3(64), 0, s, h, C, -1, nullptr, G, 1, C, groups, B * groups,
+    hipLaunchKernelGGL(edge_gn_finalize_kernel, dim3(B * groups), dim3(256), 0, s, h, C, -1, nullptr, G, 1, C, groups,
                        part, eps, mean, rstd);
     hipLaunchKernelGGL(gumbel_argmax_gather_kernel, dim3(B * G), dim3(256), 0, s, h, G, C, groups, mean, rstd, gamma, beta, slope, noise, seed,
                        seed_dev, 1.0f / tau, codebook, D, index_out, out, logits_out);

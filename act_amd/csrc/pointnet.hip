@@ -142,13 +142,12 @@ __device__ __forceinline__ void fold_partials(const float* __restrict__ partial,
     }
 }
 // Column mean and biased variance from the MODE 0 partials [nparts][4][C].  The row-0 sums give mean = x[0][c] + dm, var = q / R - dm^2; that is
-// sound while the pivot lies within a few standard deviations of the mean.  Where dm^2 > FAR_PIVOT * var in some column of the workgroup, those
+// sound while the pivot lies within a few standard deviations of the mean.  Where dm^2 > FAR_PIVOT * var (common.h) in some column of the workgroup, those
 // columns take Chan's combination of the parts' (mean, M2) instead: mean = mean_0 + sum n_p (mean_p - mean_0) / R, then
 // M2 = sum M2_p + n_p (mean_p - mean)^2 (two passes over the partials, nothing cancels; part p holds n_p = min(rows_per_block, R - p rows_per_block)
 // rows).  Both are fixed-order, so two runs give equal bits; just short of the switch (pivot 4.8 standard deviations out) the row-0 form measures 4.7e-6 on the
 // normalised output and 2.7e-6 on running_var at R = 262,144 (bars 2e-5 / 1e-5; tests/test_gpu_pointnet_rows_edges.py::test_either_side_of_the_far_pivot_switch).
 // Returns true in the one thread of column c that holds the result.
-#define FAR_PIVOT 25.f
 __device__ __forceinline__ bool column_mean_var(const float* __restrict__ x, const float* __restrict__ partial, int nparts, int rows_per_block, int C,
                                                 int R, int& c, float& mean, float& var) {
     __shared__ float red[2][3][64];
