@@ -75,6 +75,10 @@ class Dgcnn(ctypes.Structure):                         # act_dgcnn_t
                 [(n, _vp) for n in ("w_in", "b_in", "w5")] + [("stacked", _vp * 4), ("gn_w", _vp * 4), ("gn_b", _vp * 4)])
 
 
+class DgcnnF16x3(ctypes.Structure):                    # act_dgcnn_f16x3_t
+    _fields_ = [("w5_planes", _vp), ("w5_inv_scale", _vp), ("a_scale", _f), ("a_planes", _vp), ("a_planes_elems", _sz)]
+
+
 class AugmentOp(ctypes.Structure):                     # act_augment_op_t
     _fields_ = [("kind", _i), ("p0", _f), ("p1", _f), ("p2", _f), ("draws", _vp), ("draws2", _vp)]
 
@@ -85,7 +89,8 @@ STRUCTS = {
     "act_block_params_t": BlockParams, "act_block_grads_t": BlockParams, "act_block_dims_t": BlockDims, "act_block_stack_t": BlockStack,
     "act_prefix_vit_t": PrefixVit, "act_vit_bf16x3_t": VitBf16x3, "act_vit_f16x3_t": VitF16x3,
     "act_pointnet_params_t": PointnetParams,
-    "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn, "act_augment_op_t": AugmentOp,
+    "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn, "act_dgcnn_f16x3_t": DgcnnF16x3,
+    "act_augment_op_t": AugmentOp,
 }
 
 _epi, _probs, _fx = _P(GemmEpilogue), _P(GemmTnProblem), _P(GemmFx)
@@ -229,6 +234,7 @@ _TABLE = {
     "act_pointnet_bwd_f32": [_pnd, _pnp, _vp, _vp, _vp, _P(PointnetGrads), _vp, _vp, _sz, _vp],
     "act_dgcnn_scratch_floats": (_sz, [_P(Dgcnn)]),
     "act_dgcnn_features_f32": [_P(Dgcnn), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_dgcnn_features_f16x3_f32": [_P(Dgcnn), _P(DgcnnF16x3), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     # dense per-point prediction (csrc/seg.hip)
     "act_three_nn_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "act_interp_rows_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],

@@ -19,7 +19,7 @@ import torch
 
 from . import _C
 from . import kernels as K
-from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3, VitF16x3
+from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3, VitF16x3, DgcnnF16x3
 from ._abi import GemmFx          # noqa: F401  (tests and benchmarks build it as CP.GemmFx)
 
 lib, check = _C.lib, _C.check
@@ -301,6 +301,12 @@ TEACHER_BF16X3_BWD = os.environ.get("ACT_TEACHER_BF16X3_BWD", "1") == "1"
 # differentiable prefix block, the CLIP / BERT teachers and the student never take it.
 TEACHER_F16X3 = os.environ.get("ACT_TEACHER_F16X3", "1") != "0"
 _VIT_F16 = weakref.WeakKeyDictionary()         # tokenizer -> (signature, planes, inverse row scales, activation scales, pointer arrays)
+# DEFAULT ON: the head product of the FROZEN dVAE tokenizer's DGCNN (dgcnn_features below: T x Cout x 2304 against the frozen layer5[0] weight, the codebook
+# logits of dgcnn_1) on the same split-f16 kernel, taken for Cout >= 1024 (below that the split pass over cat eats the gain: dgcnn_2's 384-wide head and the
+# four edge-conv products stay on the f32 kernel).  fp32-grade, not bit-identical (notebook/tokenizer_f16x3.md); ACT_TOKENIZER_F16X3=0 restores the f32 path
+# bit for bit.  Stage I trains the tokenizer under autograd and never comes here.
+TOKENIZER_F16X3 = os.environ.get("ACT_TOKENIZER_F16X3", "1") != "0"
+_DGCNN_F16 = weakref.WeakKeyDictionary()       # DGCNN -> (signature, w5 planes, inverse row scales, max|gamma|, max|beta|, couts, groups, {(G, k): a_scale})
 
 
 def _stack_leaves(blocks):
@@ -705,7 +711,8 @@ def pointnet_forward(enc, point_groups, need=None):
 # ---- DGCNN, inference form -------------------------------------------------------------------------------------------------
 def dgcnn_features(dg, f, idx, stacked):
     """``dg`` = models.dvae.DGCNN (frozen / no grad); f [B,G,Cin], idx int64 [B,k,G], stacked = the four [Wa ; Wb-Wa] matrices
-    -> pre-norm head rows [B*G, Cout] (everything up to layer5's GroupNorm), one host call (10 launches)."""
+    -> pre-norm head rows [B*G, Cout] (everything up to layer5's GroupNorm), one host call (10 launches; 11 with the head on split-f16 planes:
+    TOKENIZER_F16X3 and Cout >= 1024)."""
     B, G, Cin = f.shape
     dev = f.device
     w5 = dg.layer5[0].weight
@@ -721,6 +728,46 @@ def dgcnn_features(dg, f, idx, stacked):
     ws = K.workspace(dev)
     f = K._f32c(f)
     args = (ctypes.byref(m), _p(f), _p(idx), _p(h), _p(scratch), _p(ws), ws.numel() * 4)
+    # (the f32 shapes are collected and tuned in either mode: a head the split-f16 kernel does not take falls back to them)
     ensure_tuned(("dgcnn", B, G, Cin, m.Cout), lambda: lib.act_dgcnn_features_f32(*args, _C.stream()), dev)
+    if TOKENIZER_F16X3 and m.Cout >= 1024:
+        x3, keep = _dgcnn_f16_planes(dg, B * G, G, m.k, dev)
+        check(lib.act_dgcnn_features_f16x3_f32(args[0], ctypes.byref(x3), *args[1:], _C.stream()), "act_dgcnn_features_f16x3_f32")
+        del keep
+        return h
     check(lib.act_dgcnn_features_f32(*args, _C.stream()), "act_dgcnn_features_f32")
     return h
+
+
+def f16x3_dgcnn_bound(gmax, bmax, couts, groups, G, k):
+    """weight-only bound on every element of the head's A operand (the concatenated outputs of the four edge-conv tails):
+       GroupNorm over one group of n_l = (cout_l / groups_l) G k values standardises to |x - mean| rstd <= sqrt(n_l - 1) < sqrt(n_l) (biased variance, eps >= 0),
+       so |y| <= sqrt(n_l) max|gamma_l| + max|beta_l|; LeakyReLU (slope <= 1) and the max over k pick or shrink one of those values.
+    gmax / bmax: max|gamma_l| / max|beta_l| per layer (host floats)."""
+    return max(math.sqrt((c // g) * G * k) * gm + bm for gm, bm, c, g in zip(gmax, bmax, couts, groups))
+
+
+def _dgcnn_f16_planes(dg, T, G, k, dev):
+    """f16 (h1, h2) planes of the frozen head weight layer5[0] with one power-of-two scale per output row, the inverse scales and the four max|gamma|, max|beta|
+    of the range guard (read to the host HERE, never per step) -- computed ONCE and cached per DGCNN under the (address, version) signature of the head weight
+    and the four GroupNorm affines (load_state_dict copies in place); the activation scale is host arithmetic from those and the call's (G, k).
+    -> (DgcnnF16x3, keep-alive)"""
+    gns = [layer[1] for layer in (dg.layer1, dg.layer2, dg.layer3, dg.layer4)]
+    w5 = dg.layer5[0].weight
+    sig = tuple((t.data_ptr(), t._version) for t in [w5] + [t for gn in gns for t in (gn.weight, gn.bias)])
+    cache = _DGCNN_F16.get(dg)
+    if cache is None or cache[0] != sig:
+        with torch.no_grad():
+            w = w5.detach().reshape(w5.shape[0], w5.shape[1])
+            scale, inv = K.f16x3_row_scales(w)
+            planes = K.split_f16x2(w, 1.0, scale)
+            inv = inv.contiguous()
+            mx = torch.stack([t.detach().double().abs().max() for gn in gns for t in (gn.weight, gn.bias)]).tolist()
+        cache = _DGCNN_F16[dg] = (sig, planes, inv, mx[0::2], mx[1::2], [gn.num_channels for gn in gns], [gn.num_groups for gn in gns], {})
+    _, planes, inv, gmax, bmax, couts, groups, scales = cache
+    a_scale = scales.get((G, k))
+    if a_scale is None:
+        a_scale = scales[(G, k)] = f16x3_act_scale(f16x3_dgcnn_bound(gmax, bmax, couts, groups, G, k))
+    a_planes = torch.empty(2 * T * planes.shape[2], dtype=torch.float16, device=dev)
+    x3 = DgcnnF16x3(planes.data_ptr(), inv.data_ptr(), a_scale, a_planes.data_ptr(), a_planes.numel())
+    return x3, (a_planes, cache)

@@ -934,8 +934,21 @@ size_t act_dgcnn_scratch_floats(const act_dgcnn_t* m) {
     if (!m || m->B <= 0 || m->G <= 0 || m->groups <= 0) return 0;
     float *a, *b, *c, *d; return carve_dgcnn(nullptr, *m, a, b, c, d);
 }
+static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch, float* ws, size_t wsb,
+                          act_stream_t stream);
 int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* idx, float* h, float* scratch, float* ws, size_t wsb,
                            act_stream_t stream) {
+    return dgcnn_features(m, nullptr, f, idx, h, scratch, ws, wsb, stream);
+}
+// same launch sequence with the head product (T x Cout x 2304, frozen w5) on the split-f16 kernel: `cat` is split at the static scale x3->a_scale and
+// multiplied with the cached planes of w5.  Everything up to `cat` is the f32 entry's, bit for bit; an unusable x3 (null pointer, a_scale <= 0 = the range
+// guard gave no scale, scratch too small, a shape the kernel does not take) runs the f32 head product and equals act_dgcnn_features_f32 bit for bit.
+int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
+                                 float* ws, size_t wsb, act_stream_t stream) {
+    return dgcnn_features(m, x3, f, idx, h, scratch, ws, wsb, stream);
+}
+static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch, float* ws, size_t wsb,
+                          act_stream_t stream) {
     if (!m || !f || !idx || !h || !scratch) return ACT_E_NULLPTR;
     if (m->B <= 0 || m->G <= 0 || m->k <= 0 || m->Cin <= 0 || m->Cout <= 0 || m->groups <= 0) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
@@ -952,6 +965,16 @@ int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* 
         RUN(act_edge_gn_lrelu_max_f32(yz, 2 * cout, cout, idx, m->B, m->G, m->k, cout, m->groups, m->gn_w[l], m->gn_b[l], m->eps, m->slope, stats,
                                      cat, 2304, off, s));
         xin = cat + off; ldx = 2304; off += cout;
+    }
+    const bool x3_ok = x3 && x3->w5_planes && x3->w5_inv_scale && x3->a_planes && x3->a_scale > 0.f && x3->a_planes_elems >= (size_t)2 * T * 2304 &&
+                       act_sgemm_nt_f16x3_supported(T, m->Cout, 2304);
+    if (x3_ok) {
+        if (t_collect) return 0;
+        uint16_t *a1 = x3->a_planes, *a2 = x3->a_planes + (size_t)T * 2304;
+        CK(act_split_f16x2_f32(cat, T, 2304, 2304, x3->a_scale, nullptr, a1, a2, s));
+        const act_gemm_epilogue_t e0 = epi0();
+        return act_sgemm_nt_f16x3_planes_f32(T, m->Cout, 2304, a1, a2, x3->a_scale, x3->w5_planes, x3->w5_planes + (size_t)m->Cout * 2304, x3->w5_inv_scale,
+                                             h, m->Cout, nullptr, nullptr, 0.f, &e0, s);
     }
     CK(gemm_nt(T, m->Cout, 2304, cat, 2304, m->w5, 2304, h, m->Cout, epi0(), ws, wsb, s));
     return 0;

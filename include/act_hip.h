@@ -652,6 +652,21 @@ typedef struct {
 size_t act_dgcnn_scratch_floats(const act_dgcnn_t* m);
 int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* idx, float* h, float* scratch, float* workspace,
                            size_t workspace_bytes, act_stream_t stream);
+/* the same with the head product (T = B*G rows, Cout columns, K = 2304, the frozen w5) on the split-f16 kernel (act_sgemm_nt_f16x3_planes_f32): cat is split
+ * at the static scale a_scale (a power of two with a_scale * max|cat| <= 2^15; the caller derives the bound from the four GroupNorm affines) and multiplied
+ * with the planes of w5 (act_split_f16x2_f32 with the row scales whose inverses are w5_inv_scale [Cout]).  w5_planes = the h1 plane, the h2 plane Cout * 2304
+ * elements behind it; a_planes = scratch for the planes of cat, >= 2 * T * 2304 elements.  Everything up to cat is act_dgcnn_features_f32's, bit for bit.
+ * x3 unusable -- NULL, a NULL pointer in it, a_scale <= 0, a_planes_elems too small, or !act_sgemm_nt_f16x3_supported(T, Cout, 2304) -- runs the f32 head
+ * product: the result then equals act_dgcnn_features_f32 bit for bit. */
+typedef struct {
+    const uint16_t* w5_planes;
+    const float* w5_inv_scale;
+    float a_scale;
+    uint16_t* a_planes;
+    size_t a_planes_elems;
+} act_dgcnn_f16x3_t;
+int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
+                                 float* workspace, size_t workspace_bytes, act_stream_t stream);
 
 /* ---- dense per-point prediction (semantic segmentation head; csrc/seg.hip) --------------------------------------------------
  * semantic_segmentation/models/pointnet2_utils.py:262-315 (PointNetFeaturePropagation) and models/pt.py (log_softmax, nll_loss).
