@@ -191,6 +191,8 @@ _TABLE = {
     "act_split_f16x2_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "act_sgemm_nt_f16x3_supported": [_i, _i, _i],
     "act_sgemm_nt_f16x3_planes_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp],
+    "act_sgemm_nt_f16x3_pick_tile": [_i, _i, _i, _i],
+    "act_sgemm_nt_f16x3_planes_tile_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
     "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
     "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
     # GEMM launch-configuration table

@@ -22,6 +22,15 @@
 // two cross terms h1.h2 + h2.h1 go to a SECOND accumulator that is folded in with 2^-11 in the epilogue, where the scales are divided out again:
 //   v = (acc0 + 2^-11 acc1) * (1 / s_B[n]) * (1 / s_A)   -> bias / GELU / residual exactly as the f32 kernels.   fp32-grade: error against fp64 equal to the
 // f32 kernel's on LayerNorm / GELU / attention operands (tests/test_gpu_f16x3.py holds it to 1.5 x).  Launches are counted under the same profiling id.
+//
+// TILE FORMS (notebook/x3_tiles.md).  The kernel is a template over the tile BM x BN and its wave grid WGM x WGN (64 WGM WGN threads, wave block BM/WGM x BN/WGN):
+//   <128, 128, 2, 2>  4 waves, 64 x 64 per wave, 81,920 B LDS, two workgroups per CU            (bf16: 162 VGPRs, F16: 226 VGPRs) -- the bf16 opt-in and the default
+//   <128, 192, 2, 4>  8 waves, 64 x 48 per wave, 102,400 B LDS, one workgroup per CU, F16 only  (196 VGPRs, no scratch)
+// Both run two waves per SIMD.  The kernel's speed follows how its grid fills the CUs: at M = 8,192, N = 768 (the teacher's proj and fc2) 128 x 128 tiles make 384
+// workgroups for 512 slots -- half of the CUs hold two, half hold one, and the launch lasts as long as the CUs that hold two -- where 128 x 192 makes 256, one per
+// CU, each 1.5 tiles' worth: proj 67.6 -> 56.2 us, fc2 160.0 -> 132.0 us per launch inside the step.  act_sgemm_nt_f16x3_pick_tile (below) picks by shape alone.
+// The order of accumulation of an output element does not depend on the tile (K tiles in sequence, the three products in the same order, the same epilogue):
+// every form gives the same bits (tests/test_gpu_f16x3_tiles.py).
 #include "gemm_common.h"
 #include "split_f16.h"
 #include <stdlib.h>
@@ -84,16 +93,23 @@ __device__ __forceinline__ f32x4 x3_mfma(const bf16x8& b, const bf16x8& a, const
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
 }
 
+// workgroups per CU the kernel is built for: two of the 4-wave form, one of the 8-wave form -- two waves per SIMD either way
+constexpr int x3_wgs_per_cu(int waves) { return waves <= 4 ? 2 : 1; }
+
 // F16: f16 planes, the two cross terms in a second accumulator set (acc[1]), scales divided out in the epilogue; otherwise bf16 planes and one accumulator set
-template <int BM, int BN, int ACT, bool PLANES, bool F16>
-__global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params p) {
-    constexpr int TM = BM / 32, TN = BN / 32;                 // 16 x 16 tiles per wave (2 x 2 waves)
+// WGM x WGN waves, each on a (BM / WGM) x (BN / WGN) block of the tile.  (__launch_bounds__' second argument counts waves per SIMD.)
+template <int BM, int BN, int WGM, int WGN, int ACT, bool PLANES, bool F16>
+__global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WGN / 4) void sgemm_nt_bf16x3_kernel(const X3Params p) {
+    constexpr int NT = 64 * WGM * WGN, RP = NT / 4;           // threads; rows of a plane tile that one staging pass covers
+    constexpr int WM = BM / WGM, WN = BN / WGN;               // the wave's block
+    constexpr int TM = WM / 16, TN = WN / 16;                 // 16 x 16 tiles per wave
     constexpr int PA = BM * LROW, PB = BN * LROW;             // bf16 per plane image
-    constexpr int NA = BM / 64, NB = BN / 64;                 // 16-byte chunks per thread, plane and K tile
+    constexpr int NA = (BM + RP - 1) / RP, NB = (BN + RP - 1) / RP;   // 16-byte chunks per thread, plane and K tile (the last pass may be partial)
     constexpr int STAGE = 2 * (PA + PB);
+    static_assert(WM % 16 == 0 && WN % 16 == 0 && BM % 16 == 0 && BN % 16 == 0, "whole 16 x 16 blocks per wave, whole waves per staging row test");
     __shared__ __attribute__((aligned(16))) unsigned short L[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = wave / WGN, wn = wave % WGN;
     const int tiles_n = p.N / BN, tiles_m = p.M / BM;
     int wg = blockIdx.x;
     {                                                             // XCD-aware remap (workgroup b runs on XCD b % 8) + grouped rasterisation (gemm_common.h)
@@ -123,16 +139,27 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
     u32x4v ra0[2][NA], rb0[2][NB], ra1[2][NA], rb1[2][NB];      // two staging sets (native vectors: arrays of HIP's uint4 struct would sit in scratch)
     const int s_off = srow * LROW + sch * 8;
     const int r = lane & 15, g = lane >> 4;
-    const int a_off = (wm * (BM / 2) + r) * LROW + g * 8, b_off = (wn * (BN / 2) + r) * LROW + g * 8;
+    const int a_off = (wm * WM + r) * LROW + g * 8, b_off = (wn * WN + r) * LROW + g * 8;
+    // staging pass i covers rows i * RP .. of the plane tile.  A last PARTIAL pass (BM or BN no multiple of RP) loads unconditionally from its row clamped into
+    // the tile (ta / tb: that row's offset from this thread's first row) and stores to the LDS only where the row exists -- a test that is uniform per wave
+    // (a wave stages 16 consecutive rows; BM, BN and RP are multiples of 16), so there is still no divergent code around the staging registers
+    const long long ta = (long long)(min(srow + RP * (NA - 1), BM - 1) - srow) * K, tb = (long long)(min(srow + RP * (NB - 1), BN - 1) - srow) * K;
+#define X3_WHOLE(I, ROWS) (RP * ((I) + 1) <= (ROWS))
 #define X3_LOAD(RA, RB, T)                                                                                                             \
     _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                                                 \
-        _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_) RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (size_t)(64 * i_) * K + (T) * BK); \
-        _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_) RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (size_t)(64 * i_) * K + (T) * BK); \
+        _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
+            RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * K : ta) + (T) * BK);      \
+        _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
+            RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (X3_WHOLE(i_, BN) ? (long long)(RP * i_) * K : tb) + (T) * BK);      \
     }
 #define X3_STORE(RA, RB, STG)                                                                                                          \
     _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                                                 \
-        _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_) *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + s_ * PA + s_off + 64 * i_ * LROW]) = RA[s_][i_];           \
-        _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_) *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + 2 * PA + s_ * PB + s_off + 64 * i_ * LROW]) = RB[s_][i_];  \
+        _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
+            if (X3_WHOLE(i_, BM) || srow + RP * i_ < BM)                                                                               \
+                *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + s_ * PA + s_off + RP * i_ * LROW]) = RA[s_][i_];                         \
+        _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
+            if (X3_WHOLE(i_, BN) || srow + RP * i_ < BN)                                                                               \
+                *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + 2 * PA + s_ * PB + s_off + RP * i_ * LROW]) = RB[s_][i_];                \
     }
 #define X3_COMPUTE(STG)                                                                                                                \
     {                                                                                                                                  \
@@ -165,10 +192,11 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
         X3_STORE(ra0, rb0, 0)
         __syncthreads();
     }
+#undef X3_WHOLE
 #undef X3_LOAD
 #undef X3_STORE
 #undef X3_COMPUTE
-    // epilogue: lane (r, g) holds row i*16 + r, columns j*16 + 4g .. 4g+3 of its wave's 64 x 64 block (operands swapped above): one float4 of bias / residual /
+    // epilogue: lane (r, g) holds row i*16 + r, columns j*16 + 4g .. 4g+3 of its wave's WM x WN block (operands swapped above): one float4 of bias / residual /
     // result and one 8-byte store per plane, per 16 x 16 block; same per-element arithmetic and order as the f32 kernels (epilogue_apply4_act)
     // F16: v = (acc0 + 2^-11 acc1) / s_B[n] / s_A first -- two multiplications by powers of two, exact -- then the same epilogue
     const bool vec = (((uintptr_t)p.C | (uintptr_t)p.epi.bias | (uintptr_t)p.epi.res | (uintptr_t)p.epi.aux) & 15) == 0 &&
@@ -177,8 +205,8 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const int row = m0 + wm * (BM / 2) + i * 16 + r;
-            const int col = n0 + wn * (BN / 2) + j * 16 + g * 4;
+            const int row = m0 + wm * WM + i * 16 + r;
+            const int col = n0 + wn * WN + j * 16 + g * 4;
             float4 v = make_float4(acc[0][i][j][0], acc[0][i][j][1], acc[0][i][j][2], acc[0][i][j][3]);
             if constexpr (F16) {
                 const float4 bi = *reinterpret_cast<const float4*>(p.b_inv + col);           // 16-byte aligned (launcher), col % 4 == 0
@@ -209,22 +237,22 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_bf16x3_kernel(const X3Params 
         }
 }
 
-template <int BM, int BN, bool F16>
+template <int BM, int BN, int WGM, int WGN, bool F16>
 int launch_x3(const X3Params& p, hipStream_t s) {
-    const dim3 grid((p.M / BM) * (p.N / BN));
+    const dim3 grid((p.M / BM) * (p.N / BN)), block(64 * WGM * WGN);
     const bool planes = p.Oh != nullptr;
     switch (p.epi.act) {
         case ACT_EPI_NONE:
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, true, F16>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_NONE, false, F16>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_NONE, true, F16>), grid, block, 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_NONE, false, F16>), grid, block, 0, s, p);
             break;
         case ACT_EPI_GELU:
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, true, F16>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_GELU, false, F16>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_GELU, true, F16>), grid, block, 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_GELU, false, F16>), grid, block, 0, s, p);
             break;
         case ACT_EPI_MUL_GELU_GRAD:                                  // (the MLP's backward through GELU: aux = the saved pre-activation)
-            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, true, F16>), grid, dim3(256), 0, s, p);
-            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, ACT_EPI_MUL_GELU_GRAD, false, F16>), grid, dim3(256), 0, s, p);
+            if (planes) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_MUL_GELU_GRAD, true, F16>), grid, block, 0, s, p);
+            else        hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_MUL_GELU_GRAD, false, F16>), grid, block, 0, s, p);
             break;
         default: return ACT_E_BADARG;
     }
@@ -264,7 +292,7 @@ extern "C" int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    return launch_x3<128, 128, false>(p, s);
+    return launch_x3<128, 128, 2, 2, false>(p, s);
 }
 
 // ---- the f16 form (default teacher path) --------------------------------------------------------------------------------------------------------------------
@@ -282,13 +310,52 @@ extern "C" int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float 
 
 extern "C" int act_sgemm_nt_f16x3_supported(int M, int N, int K) { return act_sgemm_nt_bf16x3_supported(M, N, K); }
 
+// Tile by shape alone.  The kernel's time follows how its grid fills the CUs, not the arithmetic; count it in the time one 128 x 128 workgroup takes on a CU
+// of its own.  Two 128 x 128 workgroups that share a CU take 2 units, so a full round of 2 * cus workgroups costs 2, and a last round costs 1 if it leaves every
+// CU at most one workgroup, else 2.  A CU holds one 128 x 192 workgroup, 1.5 units, so every round of cus workgroups costs 1.5, full or not.  Costs are kept
+// in half units.  128 x 192 is taken where it is cheaper by an eighth or more: the count is good to about 10 % (23 shapes, profiles/x3_tiles_micro.txt: grids
+// of up to cus workgroups, 1 against 1.5: 128 x 128 faster by 8 - 17 %; 288 and 384 workgroups, 2 against 1.5: 128 x 192 faster by 21 - 26 %; equal counts:
+// within 6 % either way), and the teacher's qkv product, 1,152 workgroups at 5 against 4.5, was 5 % faster alone and 2 % slower inside the step
+// (profiles/x3_tiles_trace_by_grid_qkv192.txt).  N % 384: 192-wide column tiles within the N % 128 contract.  (K does not enter: both tiles walk the same K loop.)
+extern "C" int act_sgemm_nt_f16x3_pick_tile(int M, int N, int K, int cus) {
+    if (!act_sgemm_nt_f16x3_supported(M, N, K) || cus <= 0) return 0;
+    if (N % 384) return 128;
+    const long long t128 = (long long)(M / 128) * (N / 128), t192 = (long long)(M / 128) * (N / 192);
+    const long long tail = t128 % (2 * cus);
+    const long long c128 = t128 / (2 * cus) * 4 + (tail == 0 ? 0 : tail <= cus ? 2 : 4), c192 = (t192 + cus - 1) / cus * 3;
+    return 8 * c192 <= 7 * c128 ? 192 : 128;
+}
+
+namespace {
+int x3_cu_count() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return v;
+    }();
+    return n;
+}
+bool x3_only_128() {                                               // ACT_X3_TILE=128: every launch on the 128 x 128 tile (A/B runs); read once
+    static const bool v = [] { const char* e = getenv("ACT_X3_TILE"); return e && atoi(e) == 128; }();
+    return v;
+}
+}  // namespace
+
 extern "C" int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
                                              const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
                                              float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
+    return act_sgemm_nt_f16x3_planes_tile_f32(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, 0);
+}
+
+extern "C" int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                                  const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                                  float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
     if (!a_h1 || !a_h2 || !b_h1 || !b_h2 || !b_inv_scale || (!C && !out_h1) || ((out_h1 == nullptr) != (out_h2 == nullptr))) return ACT_E_NULLPTR;
     if (!act_sgemm_nt_f16x3_supported(M, N, K) || (C && ldc < N) || !(a_scale > 0.f) || (out_h1 && !(out_scale > 0.f))) return ACT_E_BADARG;
     if ((((uintptr_t)a_h1 | (uintptr_t)a_h2 | (uintptr_t)b_h1 | (uintptr_t)b_h2 | (uintptr_t)out_h1 | (uintptr_t)out_h2 | (uintptr_t)b_inv_scale) & 15))
         return ACT_E_BADARG;
+    if (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;       // a forced tile that the shape does not take
+    if (tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
     p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = out_h1; p.Ol = out_h2;
     p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale;
@@ -296,5 +363,5 @@ extern "C" int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    return launch_x3<128, 128, true>(p, s);
+    return tile == 192 ? launch_x3<128, 192, 2, 4, true>(p, s) : launch_x3<128, 128, 2, 2, true>(p, s);
 }

@@ -234,10 +234,11 @@ def layernorm_f16_planes(x, gamma, beta, eps, scale, pos=None):
     return planes
 
 
-def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_NONE, res=None, out=None, planes_out=None, out_scale=1.0):
+def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_NONE, res=None, out=None, planes_out=None, out_scale=1.0, tile=0):
     """C[M,N] = epilogue((a . b^T) / a_scale / b_scale[n]) with both operands as f16 planes [2, rows, K] (split_f16x2: a at the scalar ``a_scale``, b at
     f16x3_row_scales) and the products h1.h1 + 2^-11 (h1.h2 + h2.h1) on the f16 matrix cores, two fp32 accumulators: fp32-grade.  M, N % 128 == 0,
-    K % 64 == 0.  ``planes_out`` [2, M, N] f16: the result also as planes at ``out_scale`` -- the A operand of a following product."""
+    K % 64 == 0.  ``planes_out`` [2, M, N] f16: the result also as planes at ``out_scale`` -- the A operand of a following product.  ``tile``: 0 = the
+    library's rule (act_sgemm_nt_f16x3_pick_tile), 128 or 192 = that column width of the tile (tests and A/B runs; the bits do not depend on it)."""
     _, M, Kd = a_planes.shape
     _, N, Kb = b_planes.shape
     if Kd != Kb or a_planes.dtype != torch.float16 or b_planes.dtype != torch.float16 or not (a_planes.is_contiguous() and b_planes.is_contiguous()):
@@ -256,8 +257,9 @@ def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_N
         if planes_out.dtype != torch.float16 or tuple(planes_out.shape) != (2, M, N) or not planes_out.is_contiguous():
             raise _C.ActHipError("gemm_nt_f16x3: planes_out must be a contiguous f16 tensor [2, M, N]")
         oh, ol = ptr(planes_out[0]), ptr(planes_out[1])
-    check(lib.act_sgemm_nt_f16x3_planes_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]), ptr(b_inv_scale),
-                                            ptr(out), out.stride(0), oh, ol, float(out_scale), ctypes.byref(e), stream()), "act_sgemm_nt_f16x3_planes_f32")
+    check(lib.act_sgemm_nt_f16x3_planes_tile_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]),
+                                                 ptr(b_inv_scale), ptr(out), out.stride(0), oh, ol, float(out_scale), ctypes.byref(e), stream(), int(tile)),
+          "act_sgemm_nt_f16x3_planes_tile_f32")
     return out
 
 

@@ -431,6 +431,15 @@ int act_sgemm_nt_f16x3_supported(int M, int N, int K);
 int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
                                   const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2, float out_scale,
                                   const act_gemm_epilogue_t* epilogue, act_stream_t stream);
+/* The product picks its tile from the shape alone: 128 x 128 (4 waves, two workgroups per CU) or, where N % 384 == 0 and the grid then fills the CUs in fewer
+ * tile units, 128 x 192 (8 waves, one workgroup per CU).  Every tile gives the same bits.  act_sgemm_nt_f16x3_pick_tile: that rule as a pure host function of
+ * the shape and the CU count -> 128 or 192 (0: unsupported shape).  ..._planes_tile_f32: the same product with the tile given -- 0: the rule (what the entry
+ * above does), 128, or 192 (N % 192 == 0); any other tile, or one the shape does not take, is ACT_E_BADARG.  ACT_X3_TILE=128 in the environment (read once)
+ * makes the rule answer 128 everywhere. */
+int act_sgemm_nt_f16x3_pick_tile(int M, int N, int K, int cus);
+int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                       const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                       float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile);
 /* the plane producers in this format: bit-identical to producing fp32 and splitting it with act_split_f16x2_f32 at plane_scale */
 int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                      uint16_t* y_h1, uint16_t* y_h2, float plane_scale, float* mean /* nullable */, float* rstd /* nullable */, int T, int D,
