@@ -20,7 +20,7 @@
 // reads for K, conflict-free b32 reads for V); Q rows are loaded straight into registers.
 // All backward kernels recompute P from the saved log-sum-exp and write dqkv (and dkv0) in the layout of their inputs.
 #include "attn_frag.h"
-#include "split_f16.h"
+#include "split_planes.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -34,8 +34,8 @@ struct AttnFwdArgs {
     int B, H, Sq, S0, S1;
     float scale;
     float* out; float* lse;              // out [B, Sq, H*HD]; lse [B, H, Sq] or null
-    unsigned short* out_hi; unsigned short* out_lo;   // optional: out ALSO / ONLY (out == null) as (hi, lo) bf16 planes of the same layout (opt-in split-bf16 teacher)
-    float f16_scale;                     // > 0: the planes are the (h1, h2) f16 planes of out * f16_scale instead (split_f16.h)
+    unsigned short* out_hi; unsigned short* out_lo;   // optional: out ALSO / ONLY (out == null) as planes of the same layout, the A operand of a split-operand projection
+    PlaneFmt fmt;                        // ... in this format (split_planes.h): bf16 for the opt-in teacher, f16 at a scale for the default one
 };
 
 // JT = 32-key tiles per LDS-resident key chunk.  A sequence longer than one chunk runs an online softmax over the chunks -- running
@@ -291,20 +291,7 @@ __global__ __launch_bounds__(256, (JT == 1 ? 3 : 2)) void attn_fwd_kernel(const 
                 t.x = o[dt][g * 4 + 0] * inv_l; t.y = o[dt][g * 4 + 1] * inv_l;
                 t.z = o[dt][g * 4 + 2] * inv_l; t.w = o[dt][g * 4 + 3] * inv_l;
                 if (op) *reinterpret_cast<float4*>(op + dt * 32 + 8 * g + 4 * half) = t;
-                if (a.out_hi && a.f16_scale > 0.f) {               // (h1, h2) f16 planes of out * f16_scale (split_f16.h): the default teacher's projection operand
-                    store_f16_planes4(a.out_hi, a.out_lo, (obase + dt * 32 + 8 * g + 4 * half) >> 2, t, a.f16_scale);
-                } else if (a.out_hi) {                            // same rounding as split_bf16x2_kernel (gemm_bf16x3.hip): bit-identical to splitting `out`
-                    const float e[4] = {t.x, t.y, t.z, t.w};
-                    unsigned hh[4], ll[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        unsigned w_ = __float_as_uint(e[u]); w_ += 0x7FFFu + ((w_ >> 16) & 1u); hh[u] = w_ >> 16;
-                        unsigned x_ = __float_as_uint(e[u] - __uint_as_float(hh[u] << 16)); x_ += 0x7FFFu + ((x_ >> 16) & 1u); ll[u] = x_ >> 16;
-                    }
-                    const size_t oi = obase + dt * 32 + 8 * g + 4 * half;
-                    *reinterpret_cast<uint2*>(a.out_hi + oi) = make_uint2(hh[0] | (hh[1] << 16), hh[2] | (hh[3] << 16));
-                    *reinterpret_cast<uint2*>(a.out_lo + oi) = make_uint2(ll[0] | (ll[1] << 16), ll[2] | (ll[3] << 16));
-                }
+                if (a.out_hi) store_planes4(a.fmt, a.out_hi, a.out_lo, (obase + dt * 32 + 8 * g + 4 * half) >> 2, t);   // the projection's A operand
             }
         if (a.lse && half == 0) a.lse[((size_t)b * H + h) * a.Sq + q] = scale * m + __logf(l);
     }
@@ -984,12 +971,12 @@ static int launch_attn_fwd(const AttnFwdArgs& a, hipStream_t s) {
 
 // forward of every entry point; packed qkv is kv0 = null, S0 = 0.  S <= 16 of the packed entry is handled there (attn_small_fwd_kernel).
 static int attn_forward(const float* kv0, int S0, const float* qkv1, int Sq, float* out, uint16_t* out_hi, uint16_t* out_lo, float* lse,
-                        int B, int H, int head_dim, float scale, hipStream_t s, float f16_scale = 0.f) {
+                        int B, int H, int head_dim, float scale, hipStream_t s, PlaneFmt fmt = PlaneFmt::bf16()) {
     const int D = H * head_dim;
     AttnFwdArgs a{};
     a.q = qkv1; a.k0 = kv0; a.v0 = kv0 ? kv0 + D : nullptr; a.k1 = qkv1 + D; a.v1 = qkv1 + 2 * D;
     a.q_bs = (long long)Sq * 3 * D; a.kv0_bs = (long long)S0 * 2 * D; a.kv1_bs = a.q_bs; a.ldq = 3 * D; a.ld0 = 2 * D; a.ld1 = 3 * D;
-    a.B = B; a.H = H; a.Sq = Sq; a.S0 = S0; a.S1 = Sq; a.scale = scale; a.out = out; a.lse = lse; a.out_hi = out_hi; a.out_lo = out_lo; a.f16_scale = f16_scale;
+    a.B = B; a.H = H; a.Sq = Sq; a.S0 = S0; a.S1 = Sq; a.scale = scale; a.out = out; a.lse = lse; a.out_hi = out_hi; a.out_lo = out_lo; a.fmt = fmt;
     return head_dim == 64 ? launch_attn_fwd<64>(a, s) : launch_attn_fwd<32>(a, s);
 }
 
@@ -1062,7 +1049,7 @@ extern "C" int act_attention_fwd_prefix_f16_planes_f32(const float* kv0, int S0,
     if (B == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_ATTN_FWD, s, 4.0 * B * H * (double)Sq * (S0 + Sq) * head_dim, 4.0 * B * (double)H * head_dim * (4.0 * Sq + 2.0 * S0));
-    return attn_forward(kv0, S0, qkv1, Sq, out, out_h1, out_h2, lse, B, H, head_dim, scale, s, plane_scale);
+    return attn_forward(kv0, S0, qkv1, Sq, out, out_h1, out_h2, lse, B, H, head_dim, scale, s, PlaneFmt::f16(plane_scale));
 }
 
 extern "C" int act_attention_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,

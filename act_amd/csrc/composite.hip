@@ -8,6 +8,7 @@
 // `side_stream` that `stream` waits for before the function returns.  Buffers handed to the side stream are caller-owned slabs
 // that outlive the call on `stream` order, so the caller's allocator never sees a cross-stream hazard.
 #include "common.h"
+#include "split_planes.h"
 #include <atomic>
 #include <mutex>
 #include <unordered_map>
@@ -132,14 +133,69 @@ size_t carve_prefix_bwd(float* base, const act_block_dims_t& d, int P, PrefixBwd
     return c.used;
 }
 
-// the launch sequence of one prefix block given the LayerNorm'd prompt rows n1p (shared by the inference stack and the
-// differentiable forward)
-// OPT-IN (act_prefix_vit_fwd_bf16x3_f32): the bf16 (hi, lo) planes of one block's four weights + the scratch its activations are split into
-struct X3Block { const uint16_t *qkv, *proj, *fc1, *fc2; uint16_t* a_planes; size_t a_elems; bool n1p_is_planes;
-                 // DEFAULT teacher (act_prefix_vit_fwd_f16x3_f32): the planes are f16 (h1, h2) planes (split_f16.h); inv[j] = 1 / s_B per output row and sa[j] = the
-                 // activation scale s_A of qkv, proj, fc1, fc2.  A Linear whose range guard gave no scale arrives with a null plane pointer: f32 kernel
-                 bool f16; const float* inv[4]; float sa[4]; };
-// scratch layout of the split-bf16 path: [0, 2 TG Hd) the planes of the MLP's hidden activation (written by fc1's epilogue, read by fc2), then ONE region of
+// ---- split-operand products (gemm_bf16x3.hip): the one place of this file that switches on the plane format (split_planes.h) ---------------------------------
+// One frozen Linear whose weight is given as planes: w1 = its first plane (hi / h1), w2 = its second (lo / h2); null = this Linear stays on the f32 kernel (no
+// planes given, or the range guard of the f16 form gave no activation scale).  a_fmt = the format its A operand is split in: bf16 for the opt-in path, f16 at
+// this Linear's static activation scale s_A for the default one, which also needs inv = 1 / s_B per output row.
+struct X3Linear { const uint16_t *w1, *w2; const float* inv; PlaneFmt a_fmt; };
+inline X3Linear x3_linear_of(const uint16_t* planes, size_t plane_elems, PlaneFmt a_fmt, const float* inv = nullptr) {
+    return X3Linear{planes, planes ? planes + plane_elems : nullptr, inv, a_fmt};
+}
+// "is this shape taken": the Linear has planes and the kernel of its format takes M x N x K
+inline bool x3_takes(const X3Linear& l, int M, int N, int K) {
+    return l.w1 && (l.a_fmt.is_f16() ? act_sgemm_nt_f16x3_supported(M, N, K) : act_sgemm_nt_bf16x3_supported(M, N, K));
+}
+// A [M, K] -> planes at dst (second plane M K elements further)
+int x3_split(PlaneFmt fmt, const float* A, int M, int K, uint16_t* dst, hipStream_t s) {
+    if (fmt.is_f16()) return act_split_f16x2_f32(A, M, K, K, fmt.f16_scale, nullptr, dst, dst + (size_t)M * K, s);
+    return act_split_bf16x2_f32(A, M, K, K, dst, dst + (size_t)M * K, s);
+}
+// C [M, N] = epi(a . W^T) with a = the planes of A in l.a_fmt; `emit`: the result leaves as planes in emit_fmt there INSTEAD of fp32 C -- the A operand of the
+// next Linear, so emit_fmt is that Linear's a_fmt
+int x3_multiply(const X3Linear& l, int M, int N, int K, const uint16_t* a, float* C, uint16_t* emit, PlaneFmt emit_fmt, const act_gemm_epilogue_t& e,
+                hipStream_t s) {
+    const uint16_t* a2 = a + (size_t)M * K; uint16_t* emit2 = emit ? emit + (size_t)M * N : nullptr;
+    if (l.a_fmt.is_f16())
+        return act_sgemm_nt_f16x3_planes_f32(M, N, K, a, a2, l.a_fmt.f16_scale, l.w1, l.w2, l.inv, emit ? nullptr : C, N, emit, emit2,
+                                             emit ? emit_fmt.f16_scale : 0.f, &e, s);
+    return act_sgemm_nt_bf16x3_planes_f32(M, N, K, a, a2, l.w1, l.w2, emit ? nullptr : C, N, emit, emit2, &e, s);
+}
+// split-and-multiply: A is split into `stage` first unless its planes are already there, at `pre`.  (Nothing is recorded while the GEMM shapes are collected:
+// these products are not tuned.)
+int x3_linear(const X3Linear& l, int M, int N, int K, const float* A, const uint16_t* pre, uint16_t* stage, float* C, uint16_t* emit, PlaneFmt emit_fmt,
+              const act_gemm_epilogue_t& e, hipStream_t s) {
+    if (t_collect) return 0;
+    if (!pre) CK(x3_split(l.a_fmt, A, M, K, stage, s));
+    return x3_multiply(l, M, N, K, pre ? pre : stage, C, emit, emit_fmt, e, s);
+}
+// LayerNorm / prefix attention whose result leaves as planes at dst (second plane T D elements further) for the Linear that multiplies it next
+int x3_layernorm(PlaneFmt fmt, const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, uint16_t* dst, float* mean, float* rstd,
+                 int T, int D, float eps, hipStream_t s) {
+    uint16_t* dst2 = dst + (size_t)T * D;
+    if (fmt.is_f16()) return act_layernorm_fwd_f16_planes_f32(x, pos, gamma, beta, xin_out, nullptr, dst, dst2, fmt.f16_scale, mean, rstd, T, D, eps, s);
+    return act_layernorm_fwd_planes_f32(x, pos, gamma, beta, xin_out, nullptr, dst, dst2, mean, rstd, T, D, eps, s);
+}
+int x3_attention(PlaneFmt fmt, const float* kvp, int P, const float* qkvx, int G, float* att, uint16_t* dst, float* lse, int B, int H, int hd, hipStream_t s) {
+    uint16_t* dst2 = dst + (size_t)B * G * H * hd;
+    if (fmt.is_f16()) return act_attention_fwd_prefix_f16_planes_f32(kvp, P, qkvx, G, att, dst, dst2, fmt.f16_scale, lse, B, H, hd, attn_scale(hd), s);
+    return act_attention_fwd_prefix_planes_f32(kvp, P, qkvx, G, att, dst, dst2, lse, B, H, hd, attn_scale(hd), s);
+}
+
+// The planes of one frozen block: its four Linears and `kv`, the K,V rows of the qkv Linear applied to the prompt rows (bf16 opt-in only: the default teacher's
+// prompt keys / values stay on the f32 path), + the scratch its activations are split into.
+// (n1p_is_planes: the caller's prompt LayerNorm already left the prompt rows as planes in the activation region)
+struct X3Block { X3Linear kv, qkv, proj, fc1, fc2; uint16_t* a_planes; size_t a_elems; bool n1p_is_planes; };
+// OPT-IN (act_prefix_vit_fwd_bf16x3_f32): w_planes[0..3] = the hi planes of qkv_w, proj_w, fc1_w, fc2_w, the lo plane behind each
+inline X3Block x3_block_bf16(const act_block_dims_t& d, const uint16_t* const* w_planes, uint16_t* a_planes, size_t a_elems) {
+    const size_t D = d.D, Hd = d.hidden; const PlaneFmt bf = PlaneFmt::bf16();
+    X3Block b{};
+    b.qkv = x3_linear_of(w_planes[0], 3 * D * D, bf); b.proj = x3_linear_of(w_planes[1], D * D, bf);
+    b.fc1 = x3_linear_of(w_planes[2], Hd * D, bf); b.fc2 = x3_linear_of(w_planes[3], D * Hd, bf);
+    if (b.qkv.w1) b.kv = X3Linear{b.qkv.w1 + D * D, b.qkv.w2 + D * D, nullptr, bf};                 // rows D .. 3D of both plane images
+    b.a_planes = a_planes; b.a_elems = a_elems;
+    return b;
+}
+// scratch layout of the split-operand path: [0, 2 TG Hd) the planes of the MLP's hidden activation (written by fc1's epilogue, read by fc2), then ONE region of
 // 2 max(TG, TP) D for the planes of whichever other activation is multiplied next (prompt rows -> n1x -> attention output -> n2: each is consumed by the
 // product that follows it on the stream before the next producer overwrites it)
 inline bool x3_fits(const act_block_dims_t& d, int P, size_t a_elems) {
@@ -147,77 +203,54 @@ inline bool x3_fits(const act_block_dims_t& d, int P, size_t a_elems) {
     return a_elems >= 2 * TG * d.hidden + 2 * (TG > TP ? TG : TP) * d.D;
 }
 
+// the launch sequence of one prefix block given the LayerNorm'd prompt rows n1p (shared by the inference stack and the
+// differentiable forward)
 int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t& w, const float* x, const float* pos, const float* n1p,
                       bool keep, PrefixSaved& sv, float* out, float* ws, size_t wsb, hipStream_t s, const X3Block* x3 = nullptr, bool kvp_ready = false) {
     const int B = d.B, G = d.S, D = d.D, H = d.heads, hd = D / H, Hd = d.hidden, TG = B * G, TP = B * P;
-    // C = epi(A . W^T): on the f32-input MFMA kernels -- or, for the frozen teacher with the split-bf16 switch on and a shape the kernel takes, A is split into
-    // (hi, lo) bf16 planes and multiplied with the weight's planes (W_hi = the sub-block of the plane image; lo plane `wplane` elements behind it)
-    uint16_t* hid_planes = x3 ? x3->a_planes : nullptr;
-    uint16_t* tmp_planes = x3 ? x3->a_planes + (size_t)2 * TG * Hd : nullptr;
-    // (keep: the differentiable forward of Stage-I prompt tuning.  Its backward never needs n1x / n2 / a in fp32 -- the block weights are frozen, no dW --, only the
-    //  LayerNorm statistics, the pre-GELU values, xin, x1, qkvx, kvp, att and lse, all of which are still written)
-    const bool x3_ok = x3 && x3_fits(d, P, x3->a_elems);
-    // `pre`: A is already there as planes (hi at pre, lo M*K further); `emit`: write the result as planes there instead of fp32 C
-    // (f16 form: `li` = which of the block's four Linears, for its scales; emitted planes are split at the scale of the NEXT Linear, li + 1)
-    const bool f16 = x3 && x3->f16;
-    auto linear = [&](int M, int N, int K, const float* A, const float* W, const uint16_t* W_hi, size_t wplane, float* C, const act_gemm_epilogue_t& e,
-                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr, int li = 0) -> int {
-        if (x3_ok && W_hi && act_sgemm_nt_bf16x3_supported(M, N, K)) {
-            if (t_collect) return 0;
-            const uint16_t* ah = pre; const uint16_t* al = pre ? pre + (size_t)M * K : nullptr;
-            if (f16) {
-                if (!pre) {
-                    CK(act_split_f16x2_f32(A, M, K, K, x3->sa[li], nullptr, tmp_planes, tmp_planes + (size_t)M * K, s));
-                    ah = tmp_planes; al = tmp_planes + (size_t)M * K;
-                }
-                return act_sgemm_nt_f16x3_planes_f32(M, N, K, ah, al, x3->sa[li], W_hi, W_hi + wplane, x3->inv[li], emit ? nullptr : C, N, emit,
-                                                     emit ? emit + (size_t)M * N : nullptr, emit ? x3->sa[li + 1] : 0.f, &e, s);
-            }
-            if (!pre) {
-                CK(act_split_bf16x2_f32(A, M, K, K, tmp_planes, tmp_planes + (size_t)M * K, s));
-                ah = tmp_planes; al = tmp_planes + (size_t)M * K;
-            }
-            return act_sgemm_nt_bf16x3_planes_f32(M, N, K, ah, al, W_hi, W_hi + wplane, emit ? nullptr : C, N, emit, emit ? emit + (size_t)M * N : nullptr, &e, s);
-        }
+    // the frozen teacher's planes, where given and where the scratch holds the activations; otherwise `none`: every Linear on the f32-input MFMA kernels
+    static const X3Block none{};
+    const X3Block& b = (x3 && x3_fits(d, P, x3->a_elems)) ? *x3 : none;
+    // scratch (x3_fits): the planes of the MLP's hidden activation at the start of a_planes, behind them tmp = the planes of the activation that is multiplied next
+    uint16_t* tmp =b.a_planes ? b.a_planes + (size_t)2 * TG * Hd : nullptr;
+    // where the A operand of each Linear arrives as planes (null: as fp32, the Linear is on the f32 kernel): the kernel before it then writes planes there and no
+    // fp32.  The MLP pair hands the hidden activation on as planes only when BOTH products take the split-operand kernel
+    uint16_t* qkv_in = x3_takes(b.qkv, TG, 3 * D, D) ? tmp : nullptr;
+    uint16_t* proj_in = x3_takes(b.proj, TG, D, D) ? tmp : nullptr;
+    uint16_t* fc1_in = x3_takes(b.fc1, TG, Hd, D) ? tmp : nullptr;
+    uint16_t* fc2_in = (fc1_in && x3_takes(b.fc2, TG, D, Hd)) ? b.a_planes : nullptr;
+    // fc2 on the split-operand kernel ONLY with its operand already there as planes: a lone fc2 would split sv.a [TG, Hd] into tmp, which holds
+    // 2 * max(TG, TP) * D elements -- too small whenever Hd > D (ADVICE round 5: reachable with a non-4x mlp_ratio, D % 128 == 0, Hd % 64 == 0, Hd % 128 != 0)
+    const X3Linear fc2 = fc2_in ? b.fc2 : X3Linear{};
+    // C = epi(A . W^T) of Linear l: on the split-operand kernel where l has planes and the shape is taken (`pre`: A's planes are already there, else A is split
+    // into tmp; `emit`: the result leaves as planes there, in the format of the Linear `next` that multiplies it, instead of fp32 C), else on the f32 kernel
+    auto linear = [&](const X3Linear& l, int M, int N, int K, const float* A, const float* W, float* C, const act_gemm_epilogue_t& e,
+                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr, const X3Linear* next = nullptr) -> int {
+        if (x3_takes(l, M, N, K)) return x3_linear(l, M, N, K, A, pre, tmp, C, emit, next ? next->a_fmt : PlaneFmt::bf16(), e, s);
         return gemm_nt(M, N, K, A, K, W, K, C, N, e, ws, wsb, s);
     };
-    // the MLP pair goes through planes only when BOTH products take the split-bf16 kernel
-    const bool mlp_planes = x3_ok && x3->fc1 && x3->fc2 && act_sgemm_nt_bf16x3_supported(TG, Hd, D) && act_sgemm_nt_bf16x3_supported(TG, D, Hd);
+    // (keep: the differentiable forward of Stage-I prompt tuning.  Its backward never needs n1x / n2 / a in fp32 -- the block weights are frozen, no dW --, only the
+    //  LayerNorm statistics, the pre-GELU values, xin, x1, qkvx, kvp, att and lse, all of which are still written)
+    float *mean1 = keep ? sv.mean1 : nullptr, *rstd1 = keep ? sv.rstd1 : nullptr, *mean2 = keep ? sv.mean2 : nullptr, *rstd2 = keep ? sv.rstd2 : nullptr;
+    float* lse = keep ? sv.lse : nullptr;
     act_gemm_epilogue_t e = epi0();
     e.bias = w.qkv_b ? w.qkv_b + D : nullptr;                                                   // K,V rows of the qkv Linear
-    // (n1p_is_planes: the caller's prompt LayerNorm already left the rows as planes in the activation region)
     // (kvp_ready: sv.kvp already holds them -- act_prompt_kv_fwd_f32, or the caller's own)
-    if (!kvp_ready)
-    CK(linear(TP, 2 * D, D, n1p, w.qkv_w + (size_t)D * D, (x3 && x3->qkv && !f16) ? x3->qkv + (size_t)D * D : nullptr, (size_t)3 * D * D, sv.kvp, e,
-              (x3_ok && x3->n1p_is_planes) ? tmp_planes : nullptr));
-    const bool ln1_planes = x3_ok && x3->qkv && act_sgemm_nt_bf16x3_supported(TG, 3 * D, D);          // LayerNorm-1 hands n1x on as planes (xin stays fp32: residual)
-    if (ln1_planes && f16) RUN(act_layernorm_fwd_f16_planes_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[0],
-                                                                keep ? sv.mean1 : nullptr, keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
-    else if (ln1_planes) RUN(act_layernorm_fwd_planes_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean1 : nullptr,
-                                                     keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
-    else RUN(act_layernorm_fwd_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, sv.n1x, keep ? sv.mean1 : nullptr, keep ? sv.rstd1 : nullptr, TG, D, d.eps, s));
+    if (!kvp_ready) CK(linear(b.kv, TP, 2 * D, D, n1p, w.qkv_w + (size_t)D * D, sv.kvp, e, b.n1p_is_planes ? tmp : nullptr));
+    RUN(qkv_in ? x3_layernorm(b.qkv.a_fmt, x, pos, w.norm1_w, w.norm1_b, sv.xin, qkv_in, mean1, rstd1, TG, D, d.eps, s)          // planes for qkv (xin stays fp32: residual)
+               : act_layernorm_fwd_f32(x, pos, w.norm1_w, w.norm1_b, sv.xin, sv.n1x, mean1, rstd1, TG, D, d.eps, s));           // f32
     e = epi0(); e.bias = w.qkv_b;
-    CK(linear(TG, 3 * D, D, sv.n1x, w.qkv_w, x3 ? x3->qkv : nullptr, (size_t)3 * D * D, sv.qkvx, e, ln1_planes ? tmp_planes : nullptr, nullptr, 0));
-    const bool att_planes = x3_ok && x3->proj && act_sgemm_nt_bf16x3_supported(TG, D, D);       // the attention output leaves its kernel as planes
-    if (att_planes && f16) RUN(act_attention_fwd_prefix_f16_planes_f32(sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[1],
-                                                                       keep ? sv.lse : nullptr, B, H, hd, attn_scale(hd), s));
-    else if (att_planes) RUN(act_attention_fwd_prefix_planes_f32(sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.lse : nullptr,
-                                                            B, H, hd, attn_scale(hd), s));
-    else RUN(act_attention_fwd_prefix_f32(sv.kvp, P, sv.qkvx, G, sv.att, keep ? sv.lse : nullptr, B, H, hd, attn_scale(hd), s));
+    CK(linear(b.qkv, TG, 3 * D, D, sv.n1x, w.qkv_w, sv.qkvx, e, qkv_in));                                                        // f32: the attention reads fp32
+    RUN(proj_in ? x3_attention(b.proj.a_fmt, sv.kvp, P, sv.qkvx, G, keep ? sv.att : nullptr, proj_in, lse, B, H, hd, s)          // planes for proj
+                : act_attention_fwd_prefix_f32(sv.kvp, P, sv.qkvx, G, sv.att, lse, B, H, hd, attn_scale(hd), s));               // f32
     e = epi0(); e.bias = w.proj_b; e.res = sv.xin; e.ldr = D;
-    CK(linear(TG, D, D, sv.att, w.proj_w, x3 ? x3->proj : nullptr, (size_t)D * D, sv.x1, e, att_planes ? tmp_planes : nullptr, nullptr, 1));
-    const bool ln2_planes = x3_ok && x3->fc1 && act_sgemm_nt_bf16x3_supported(TG, Hd, D);
-    if (ln2_planes && f16) RUN(act_layernorm_fwd_f16_planes_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, x3->sa[2],
-                                                                keep ? sv.mean2 : nullptr, keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
-    else if (ln2_planes) RUN(act_layernorm_fwd_planes_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, nullptr, tmp_planes, tmp_planes + (size_t)TG * D, keep ? sv.mean2 : nullptr,
-                                                     keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
-    else RUN(act_layernorm_fwd_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, sv.n2, keep ? sv.mean2 : nullptr, keep ? sv.rstd2 : nullptr, TG, D, d.eps, s));
+    CK(linear(b.proj, TG, D, D, sv.att, w.proj_w, sv.x1, e, proj_in));                                                           // f32: x1 is the residual stream
+    RUN(fc1_in ? x3_layernorm(b.fc1.a_fmt, sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, fc1_in, mean2, rstd2, TG, D, d.eps, s)  // planes for fc1
+               : act_layernorm_fwd_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, sv.n2, mean2, rstd2, TG, D, d.eps, s));    // f32
     e = epi0(); e.bias = w.fc1_b; e.act = ACT_EPI_GELU; e.aux = keep ? sv.hpre : nullptr; e.ldaux = Hd;
-    CK(linear(TG, Hd, D, sv.n2, w.fc1_w, x3 ? x3->fc1 : nullptr, (size_t)Hd * D, sv.a, e, ln2_planes ? tmp_planes : nullptr, mlp_planes ? hid_planes : nullptr, 2));
+    CK(linear(b.fc1, TG, Hd, D, sv.n2, w.fc1_w, sv.a, e, fc1_in, fc2_in, &fc2));                                                 // planes for fc2, else f32
     e = epi0(); e.bias = w.fc2_b; e.res = sv.x1; e.ldr = D;
-    // fc2 on the split-bf16 kernel ONLY with its operand already in hid_planes: a lone fc2 would split sv.a [TG, Hd] into tmp_planes, which holds
-    // 2 * max(TG, TP) * D elements -- too small whenever Hd > D (ADVICE round 5: reachable with a non-4x mlp_ratio, D % 128 == 0, Hd % 64 == 0, Hd % 128 != 0)
-    CK(linear(TG, D, Hd, sv.a, w.fc2_w, (x3 && mlp_planes) ? x3->fc2 : nullptr, (size_t)D * Hd, out, e, mlp_planes ? hid_planes : nullptr, nullptr, 3));
+    CK(linear(fc2, TG, D, Hd, sv.a, w.fc2_w, out, e, fc2_in));                                                                   // f32: the block's output
     return 0;
 }
 
@@ -489,12 +522,11 @@ int act_prefix_block_fwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_
     hipStream_t s = (hipStream_t)stream;
     const bool keep = keep_for_backward != 0;
     PrefixSaved sv; carve_prefix(saved, *d, P, sv);
-    X3Block xb{x3->w_planes[0], x3->w_planes[1], x3->w_planes[2], x3->w_planes[3], x3->a_planes, x3->a_planes_elems, false};
+    X3Block xb = x3_block_bf16(*d, x3->w_planes, x3->a_planes, x3->a_planes_elems);
     const int TP = d->B * P, D = d->D;
-    if (xb.qkv && x3_fits(*d, P, xb.a_elems) && act_sgemm_nt_bf16x3_supported(TP, 2 * D, D)) {
+    if (x3_fits(*d, P, xb.a_elems) && x3_takes(xb.kv, TP, 2 * D, D)) {
         uint16_t* tp = xb.a_planes + (size_t)2 * d->B * d->S * d->hidden;
-        RUN(act_layernorm_fwd_planes_f32(prm, nullptr, w->norm1_w, w->norm1_b, nullptr, nullptr, tp, tp + (size_t)TP * D, keep ? sv.meanp : nullptr,
-                                        keep ? sv.rstdp : nullptr, TP, D, d->eps, s));
+        RUN(x3_layernorm(xb.kv.a_fmt, prm, nullptr, w->norm1_w, w->norm1_b, nullptr, tp, keep ? sv.meanp : nullptr, keep ? sv.rstdp : nullptr, TP, D, d->eps, s));
         xb.n1p_is_planes = true;
     } else {
         RUN(act_layernorm_fwd_f32(prm, nullptr, w->norm1_w, w->norm1_b, nullptr, sv.n1p, keep ? sv.meanp : nullptr, keep ? sv.rstdp : nullptr, TP, D, d->eps, s));
@@ -537,21 +569,18 @@ int act_prefix_block_bwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_
         return act_prefix_block_bwd_f32(d, P, w, prm, saved, dout, dx, dprm, scratch, ws, wsb, stream);
     PrefixSaved sv; carve_prefix(const_cast<float*>(saved), *d, P, sv);
     PrefixBwdScratch sc; carve_prefix_bwd(scratch, *d, P, sc);
-    const uint16_t *fc2T = x3->w_planes[0], *fc1T = x3->w_planes[1], *projT = x3->w_planes[2], *qkvT = x3->w_planes[3], *kvT = x3->w_planes[4];
+    const PlaneFmt bf = PlaneFmt::bf16(); const size_t sD = D, sHd = Hd;
+    const X3Linear fc2T = x3_linear_of(x3->w_planes[0], sHd * sD, bf), fc1T = x3_linear_of(x3->w_planes[1], sD * sHd, bf), projT = x3_linear_of(x3->w_planes[2], sD * sD, bf),
+                   qkvT = x3_linear_of(x3->w_planes[3], 3 * sD * sD, bf), kvT = x3_linear_of(x3->w_planes[4], 2 * sD * sD, bf);
     uint16_t* big = x3->a_planes;                                   // 2 TG Hd: planes of dh, later of dqkvx [TG, 3D], later of dkvp [TP, 2D]
     uint16_t* small = x3->a_planes + (size_t)2 * TG * Hd;           // 2 max(TG, TP) D: planes of dout, later of dx1
     // dIn [M, N] = dOut [M, K] . W [K, N]  (W^T as planes [N][K]); `pre`: dOut is already planes at `stage`; `emit`: the result leaves as planes only
-    auto dgrad = [&](int M, int N, int K, const float* dOut, const float* W, const uint16_t* WT, float* dIn, const act_gemm_epilogue_t& e, uint16_t* stage,
+    auto dgrad = [&](int M, int N, int K, const float* dOut, const float* W, const X3Linear& WT, float* dIn, const act_gemm_epilogue_t& e, uint16_t* stage,
                      bool pre = false, uint16_t* emit = nullptr) -> int {
-        if (WT && act_sgemm_nt_bf16x3_supported(M, N, K)) {
-            if (t_collect) return 0;
-            if (!pre) CK(act_split_bf16x2_f32(dOut, M, K, K, stage, stage + (size_t)M * K, s));
-            return act_sgemm_nt_bf16x3_planes_f32(M, N, K, stage, stage + (size_t)M * K, WT, WT + (size_t)N * K, emit ? nullptr : dIn, N, emit,
-                                                  emit ? emit + (size_t)M * N : nullptr, &e, s);
-        }
+        if (x3_takes(WT, M, N, K)) return x3_linear(WT, M, N, K, dOut, pre ? stage : nullptr, stage, dIn, emit, bf, e, s);
         return gemm_nn(M, N, K, dOut, K, W, N, dIn, N, e, ws, wsb, s);
     };
-    const bool mlp_planes = fc2T && fc1T && act_sgemm_nt_bf16x3_supported(TG, Hd, D) && act_sgemm_nt_bf16x3_supported(TG, D, Hd);
+    const bool mlp_planes = x3_takes(fc2T, TG, Hd, D) && x3_takes(fc1T, TG, D, Hd);
     act_gemm_epilogue_t e = epi0(); e.act = ACT_EPI_MUL_GELU_GRAD; e.aux = sv.hpre; e.ldaux = Hd;
     CK(dgrad(TG, Hd, D, dout, w->fc2_w, fc2T, sc.dh, e, small, false, mlp_planes ? big : nullptr));
     CK(dgrad(TG, D, Hd, sc.dh, w->fc1_w, fc1T, sc.dn2, epi0(), big, mlp_planes));
@@ -630,14 +659,14 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
         const uint64_t seed = (m->seed_base + 7919ull * (uint64_t)(i + 1)) & ((1ull << 62) - 1);
         X3Block hb{};           // split-f16 default: this block's planes and scales; a Linear without an activation scale (range guard) keeps the f32 kernel
         if (h3) {
-            hb.a_planes = h3->a_planes; hb.a_elems = h3->a_planes_elems; hb.f16 = true;
-            const uint16_t* pl[4];
+            hb.a_planes = h3->a_planes; hb.a_elems = h3->a_planes_elems;
+            const size_t sD = D, sHd = m->hidden, elems[4] = {3 * sD * sD, sD * sD, sHd * sD, sD * sHd};
+            X3Linear* lin[4] = {&hb.qkv, &hb.proj, &hb.fc1, &hb.fc2};
             for (int j = 0; j < 4; ++j) {
                 const float sa = h3->a_scale[4 * i + j];
-                const bool on = sa > 0.f && h3->w_planes[4 * i + j] && h3->w_inv_scale[4 * i + j];
-                pl[j] = on ? h3->w_planes[4 * i + j] : nullptr; hb.inv[j] = h3->w_inv_scale[4 * i + j]; hb.sa[j] = on ? sa : 0.f;
+                if (sa > 0.f && h3->w_planes[4 * i + j] && h3->w_inv_scale[4 * i + j])
+                    *lin[j] = x3_linear_of(h3->w_planes[4 * i + j], elems[j], PlaneFmt::f16(sa), h3->w_inv_scale[4 * i + j]);
             }
-            hb.qkv = pl[0]; hb.proj = pl[1]; hb.fc1 = pl[2]; hb.fc2 = pl[3];
         }
         if (!x3) {              // prompt keys / values: base product once, the dropped terms walked sparsely (the split-bf16 opt-in keeps its planes)
             const int rc = act_prompt_kv_fwd_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
@@ -651,8 +680,8 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
             if (rc != ACT_E_UNSUPPORTED) return rc;                    // switched off / a shape it does not take: the dense sequence below
         }
         X3Block xb{};
-        if (x3) xb = X3Block{x3->w_planes[4 * i], x3->w_planes[4 * i + 1], x3->w_planes[4 * i + 2], x3->w_planes[4 * i + 3], x3->a_planes, x3->a_planes_elems, false};
-        if (x3 && xb.qkv && x3_fits(d, m->P, x3->a_planes_elems) && act_sgemm_nt_bf16x3_supported(m->B * m->P, 2 * D, D)) {
+        if (x3) xb = x3_block_bf16(d, x3->w_planes + 4 * i, x3->a_planes, x3->a_planes_elems);
+        if (x3 && x3_fits(d, m->P, x3->a_planes_elems) && x3_takes(xb.kv, m->B * m->P, 2 * D, D)) {
             uint16_t* tp = x3->a_planes + (size_t)2 * TG * m->hidden;                         // the activation region (x3_fits)
             RUN(act_prompt_layernorm_fwd_planes_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
                                                    m->eps, tp, tp + (size_t)m->B * m->P * D, s));
@@ -966,15 +995,9 @@ static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, con
                                      cat, 2304, off, s));
         xin = cat + off; ldx = 2304; off += cout;
     }
-    const bool x3_ok = x3 && x3->w5_planes && x3->w5_inv_scale && x3->a_planes && x3->a_scale > 0.f && x3->a_planes_elems >= (size_t)2 * T * 2304 &&
-                       act_sgemm_nt_f16x3_supported(T, m->Cout, 2304);
-    if (x3_ok) {
-        if (t_collect) return 0;
-        uint16_t *a1 = x3->a_planes, *a2 = x3->a_planes + (size_t)T * 2304;
-        CK(act_split_f16x2_f32(cat, T, 2304, 2304, x3->a_scale, nullptr, a1, a2, s));
-        const act_gemm_epilogue_t e0 = epi0();
-        return act_sgemm_nt_f16x3_planes_f32(T, m->Cout, 2304, a1, a2, x3->a_scale, x3->w5_planes, x3->w5_planes + (size_t)m->Cout * 2304, x3->w5_inv_scale,
-                                             h, m->Cout, nullptr, nullptr, 0.f, &e0, s);
+    if (x3 && x3->w5_planes && x3->w5_inv_scale && x3->a_planes && x3->a_scale > 0.f && x3->a_planes_elems >= (size_t)2 * T * 2304) {
+        const X3Linear w5 = x3_linear_of(x3->w5_planes, (size_t)m->Cout * 2304, PlaneFmt::f16(x3->a_scale), x3->w5_inv_scale);
+        if (x3_takes(w5, T, m->Cout, 2304)) return x3_linear(w5, T, m->Cout, 2304, cat, nullptr, x3->a_planes, h, nullptr, w5.a_fmt, epi0(), s);
     }
     CK(gemm_nt(T, m->Cout, 2304, cat, 2304, m->w5, 2304, h, m->Cout, epi0(), ws, wsb, s));
     return 0;

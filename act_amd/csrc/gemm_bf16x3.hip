@@ -2,7 +2,7 @@
 //
 //   C[M,N] = epilogue( (A_hi + A_lo) . (B_hi + B_lo)^T )  with the lo.lo term dropped:  A_hi.B_hi + A_hi.B_lo + A_lo.B_hi, fp32 accumulation
 //
-// hi = bf16(x) (round to nearest even), lo = bf16(x - hi): 16 significand bits per operand instead of 24.  Every product of two planes is exact in the
+// hi = bf16(x) (round to nearest even), lo = bf16(x - hi) (split_planes.h): 16 significand bits per operand instead of 24.  Every product of two planes is exact in the
 // MFMA's fp32 accumulator; what is lost is the 2^-17 tail of each operand and the 2^-16 lo.lo term: 4.2e-6 relative per product against fp64, and the
 // frozen teacher's features move by 6e-6 .. 7e-6 of their range when the 48 Linear layers of its ViT blocks run this way (parity bar 1e-4; measured with
 // the CPU oracle, benchmarks/bf16x3_teacher_numerics.py, and on the device, tests/test_gpu_bf16x3.py).  It is NOT the default: the product path is
@@ -16,7 +16,7 @@
 // A lesson kept in the code: the staging arrays are NATIVE vector types (ext_vector_type); arrays of HIP's `uint4` struct stay in scratch memory.
 //
 // DEFAULT for the frozen teacher's inference forward (F16 form of the same kernel, ACT_TEACHER_F16X3, notebook/teacher_f16x3.md): two f16 planes with a scaled
-// low plane, x s = h1 + 2^-11 h2 (split_f16.h), keep 22 significand bits + the residual's sign instead of 16, at the same bytes, LDS traffic and MFMA count
+// low plane, x s = h1 + 2^-11 h2 (split_planes.h), keep 22 significand bits + the residual's sign instead of 16, at the same bytes, LDS traffic and MFMA count
 // (v_mfma_f32_16x16x32_f16 runs at the bf16 rate).  f16's narrow exponent range is handled with exact powers of two: the weights carry one scale per output
 // row (row max lifted into [2^14, 2^15)), the activations one static scale per Linear derived from a weight-only bound on the operand (composite.py), and the
 // two cross terms h1.h2 + h2.h1 go to a SECOND accumulator that is folded in with 2^-11 in the epilogue, where the scales are divided out again:
@@ -32,7 +32,7 @@
 // The order of accumulation of an output element does not depend on the tile (K tiles in sequence, the three products in the same order, the same epilogue):
 // every form gives the same bits (tests/test_gpu_f16x3_tiles.py).
 #include "gemm_common.h"
-#include "split_f16.h"
+#include "split_planes.h"
 #include <stdlib.h>
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -41,36 +41,15 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ unsigned bf16_rne(float x) {          // finite inputs (activations / weights): no NaN handling needed
-    unsigned u = __float_as_uint(x);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-
-// fp32 [R][K] (row stride ldx) -> hi [R][K], lo [R][K] bf16, four elements per thread (K % 4 == 0)
-__global__ __launch_bounds__(256) void split_bf16x2_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, unsigned short* __restrict__ hi,
-                                                           unsigned short* __restrict__ lo) {
+// fp32 [R][K] (row stride ldx) -> two planes [R][K] (split_planes.h), four elements per thread (K % 4 == 0): (hi, lo) bf16 planes of x, or (F16) the (h1, h2)
+// f16 planes of x * scale * row_scale[row]; both scales are powers of two chosen by the caller and are not read in the bf16 form
+template <bool F16>
+__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, float scale,
+                                                           const float* __restrict__ row_scale, unsigned short* __restrict__ p1, unsigned short* __restrict__ p2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / K4; const int c4 = (int)(i - row * K4);
         const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-        const float e[4] = {v.x, v.y, v.z, v.w};
-        unsigned h[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            h[j] = bf16_rne(e[j]);
-            l[j] = bf16_rne(e[j] - __uint_as_float(h[j] << 16));
-        }
-        reinterpret_cast<uint2*>(hi)[i] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-        reinterpret_cast<uint2*>(lo)[i] = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
-    }
-}
-// the f16 form: (h1, h2) planes of x * scale * row_scale[row] (split_f16.h); both scales are powers of two chosen by the caller
-__global__ __launch_bounds__(256) void split_f16x2_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, float scale,
-                                                          const float* __restrict__ row_scale, unsigned short* __restrict__ h1, unsigned short* __restrict__ h2) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        const long long row = i / K4; const int c4 = (int)(i - row * K4);
-        const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-        store_f16_planes4(h1, h2, (size_t)i, v, row_scale ? scale * row_scale[row] : scale);
+        store_planes4<F16>(p1, p2, (size_t)i, v, F16 && row_scale ? scale * row_scale[row] : scale);
     }
 }
 
@@ -223,17 +202,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
                 float* cp = p.C + (size_t)row * p.ldc + col;
                 if (vec) *reinterpret_cast<float4*>(cp) = v; else { cp[0] = v.x; cp[1] = v.y; cp[2] = v.z; cp[3] = v.w; }
             }
-            if constexpr (PLANES && F16) {
-                store_f16_planes4(p.Oh, p.Ol, ((size_t)row * p.N + col) >> 2, v, p.o_scale);
-            } else if constexpr (PLANES) {
-                const float e[4] = {v.x, v.y, v.z, v.w};
-                unsigned h[4], l[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { h[q] = bf16_rne(e[q]); l[q] = bf16_rne(e[q] - __uint_as_float(h[q] << 16)); }
-                const size_t o = (size_t)row * p.N + col;                 // N % 128 == 0, col % 4 == 0: 8-byte aligned
-                *reinterpret_cast<uint2*>(p.Oh + o) = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-                *reinterpret_cast<uint2*>(p.Ol + o) = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
-            }
+            if constexpr (PLANES) store_planes4<F16>(p.Oh, p.Ol, ((size_t)row * p.N + col) >> 2, v, p.o_scale);   // N % 128 == 0, col % 4 == 0: 8-byte aligned
         }
 }
 
@@ -260,54 +229,30 @@ int launch_x3(const X3Params& p, hipStream_t s) {
     return 0;
 }
 
+// the argument-checked split pass of both formats (the bf16 form reads neither scale)
+template <bool F16>
+int split_planes(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* p1, uint16_t* p2, act_stream_t stream) {
+    if (!x || !p1 || !p2) return ACT_E_NULLPTR;
+    if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || (F16 && !(scale > 0.f)) || (((uintptr_t)x | (uintptr_t)p1 | (uintptr_t)p2) & 15)) return ACT_E_BADARG;
+    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
+    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(split_planes_kernel<F16>, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, row_scale, p1, p2);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+
 }  // namespace
 
 extern "C" int act_split_bf16x2_f32(const float* x, int R, int K, int ldx, uint16_t* hi, uint16_t* lo, act_stream_t stream) {
-    if (!x || !hi || !lo) return ACT_E_NULLPTR;
-    if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || (((uintptr_t)x | (uintptr_t)hi | (uintptr_t)lo) & 15)) return ACT_E_BADARG;
-    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
-    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(split_bf16x2_kernel, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, hi, lo);
-    ACT_LAUNCH_CHECK(); return 0;
+    return split_planes<false>(x, R, K, ldx, 0.f, nullptr, hi, lo, stream);
+}
+extern "C" int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2,
+                                   act_stream_t stream) {
+    return split_planes<true>(x, R, K, ldx, scale, row_scale, h1, h2, stream);
 }
 
 extern "C" int act_sgemm_nt_bf16x3_supported(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && M % 128 == 0 && N % 128 == 0 && K % 64 == 0; }
-
-extern "C" int act_sgemm_nt_bf16x3_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
-                                       float* C, int ldc, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
-    return act_sgemm_nt_bf16x3_planes_f32(M, N, K, a_hi, a_lo, b_hi, b_lo, C, ldc, nullptr, nullptr, epilogue, stream);
-}
-
-extern "C" int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
-                                              float* C, int ldc, uint16_t* out_hi, uint16_t* out_lo, const act_gemm_epilogue_t* epilogue,
-                                              act_stream_t stream) {
-    if (!a_hi || !a_lo || !b_hi || !b_lo || (!C && !out_hi) || ((out_hi == nullptr) != (out_lo == nullptr))) return ACT_E_NULLPTR;
-    if (!act_sgemm_nt_bf16x3_supported(M, N, K) || (C && ldc < N)) return ACT_E_BADARG;
-    if ((((uintptr_t)a_hi | (uintptr_t)a_lo | (uintptr_t)b_hi | (uintptr_t)b_lo | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15)) return ACT_E_BADARG;
-    X3Params p{};
-    p.Ah = a_hi; p.Al = a_lo; p.Bh = b_hi; p.Bl = b_lo; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = out_hi; p.Ol = out_lo;
-    if (epilogue) p.epi = *epilogue; else { p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; }
-    if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    return launch_x3<128, 128, 2, 2, false>(p, s);
-}
-
-// ---- the f16 form (default teacher path) --------------------------------------------------------------------------------------------------------------------
-extern "C" int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2,
-                                   act_stream_t stream) {
-    if (!x || !h1 || !h2) return ACT_E_NULLPTR;
-    if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || !(scale > 0.f) || (((uintptr_t)x | (uintptr_t)h1 | (uintptr_t)h2) & 15)) return ACT_E_BADARG;
-    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
-    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(split_f16x2_kernel, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, row_scale, h1, h2);
-    ACT_LAUNCH_CHECK(); return 0;
-}
-
 extern "C" int act_sgemm_nt_f16x3_supported(int M, int N, int K) { return act_sgemm_nt_bf16x3_supported(M, N, K); }
 
 // Tile by shape alone.  The kernel's time follows how its grid fills the CUs, not the arithmetic; count it in the time one 128 x 128 workgroup takes on a CU
@@ -339,29 +284,45 @@ bool x3_only_128() {                                               // ACT_X3_TIL
     static const bool v = [] { const char* e = getenv("ACT_X3_TILE"); return e && atoi(e) == 128; }();
     return v;
 }
-}  // namespace
-
-extern "C" int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
-                                             const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
-                                             float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
-    return act_sgemm_nt_f16x3_planes_tile_f32(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, 0);
-}
-
-extern "C" int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
-                                                  const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
-                                                  float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
-    if (!a_h1 || !a_h2 || !b_h1 || !b_h2 || !b_inv_scale || (!C && !out_h1) || ((out_h1 == nullptr) != (out_h2 == nullptr))) return ACT_E_NULLPTR;
-    if (!act_sgemm_nt_f16x3_supported(M, N, K) || (C && ldc < N) || !(a_scale > 0.f) || (out_h1 && !(out_scale > 0.f))) return ACT_E_BADARG;
-    if ((((uintptr_t)a_h1 | (uintptr_t)a_h2 | (uintptr_t)b_h1 | (uintptr_t)b_h2 | (uintptr_t)out_h1 | (uintptr_t)out_h2 | (uintptr_t)b_inv_scale) & 15))
-        return ACT_E_BADARG;
-    if (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;       // a forced tile that the shape does not take
-    if (tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_pick_tile(M, N, K, x3_cu_count());
+// the argument-checked product of both formats.  The scales and the tile belong to the F16 form (a_scale = s_A, b_inv = 1 / s_B per row of B, out_scale = the
+// scale the planes-out are split at; tile: 0 = the rule above, 128 / 192 forced); the bf16 form reads none of them and runs the 128 x 128 tile
+template <bool F16>
+int multiply_planes(int M, int N, int K, const uint16_t* a1, const uint16_t* a2, float a_scale, const uint16_t* b1, const uint16_t* b2, const float* b_inv,
+                    float* C, int ldc, uint16_t* o1, uint16_t* o2, float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
+    if (!a1 || !a2 || !b1 || !b2 || (F16 && !b_inv) || (!C && !o1) || ((o1 == nullptr) != (o2 == nullptr))) return ACT_E_NULLPTR;
+    if (!act_sgemm_nt_bf16x3_supported(M, N, K) || (C && ldc < N) || (F16 && (!(a_scale > 0.f) || (o1 && !(out_scale > 0.f))))) return ACT_E_BADARG;
+    if ((((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)b_inv) & 15)) return ACT_E_BADARG;
+    if (F16 && tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;       // a forced tile that the shape does not take
+    if (F16 && tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
-    p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = out_h1; p.Ol = out_h2;
-    p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale;
+    p.Ah = a1; p.Al = a2; p.Bh = b1; p.Bl = b2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = o1; p.Ol = o2;
+    if (F16) { p.b_inv = b_inv; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale; }
     if (epilogue) p.epi = *epilogue; else { p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; }
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N));
-    return tile == 192 ? launch_x3<128, 192, 2, 4, true>(p, s) : launch_x3<128, 128, 2, 2, true>(p, s);
+    if constexpr (F16) return tile == 192 ? launch_x3<128, 192, 2, 4, true>(p, s) : launch_x3<128, 128, 2, 2, true>(p, s);
+    else return launch_x3<128, 128, 2, 2, false>(p, s);
+}
+}  // namespace
+
+extern "C" int act_sgemm_nt_bf16x3_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
+                                       float* C, int ldc, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
+    return multiply_planes<false>(M, N, K, a_hi, a_lo, 0.f, b_hi, b_lo, nullptr, C, ldc, nullptr, nullptr, 0.f, epilogue, stream, 128);
+}
+extern "C" int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
+                                              float* C, int ldc, uint16_t* out_hi, uint16_t* out_lo, const act_gemm_epilogue_t* epilogue,
+                                              act_stream_t stream) {
+    return multiply_planes<false>(M, N, K, a_hi, a_lo, 0.f, b_hi, b_lo, nullptr, C, ldc, out_hi, out_lo, 0.f, epilogue, stream, 128);
+}
+// ---- the f16 form (default teacher path) --------------------------------------------------------------------------------------------------------------------
+extern "C" int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                             const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                             float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {
+    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, 0);
+}
+extern "C" int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
+                                                  const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                                  float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
+    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile);
 }

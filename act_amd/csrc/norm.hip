@@ -8,26 +8,15 @@
 // The wave-per-row LayerNorm arithmetic is ln_row.h's; the Philox keep mask of the prompt kernels (domain 1, dense rows) is dropout.h's.
 #include "dropout.h"
 #include "ln_row.h"
-#include "split_f16.h"
+#include "split_planes.h"
 #include <stdlib.h>
 
-// (hi, lo) bf16 planes of four consecutive values (round to nearest even; lo = bf16(x - hi)): the operand form of the opt-in split-bf16 GEMM
-// (gemm_bf16x3.hip) -- same rounding as its split_bf16x2_kernel, so a producer that writes planes is bit-identical to producing fp32 and splitting it
-__device__ __forceinline__ unsigned ln_bf16_rne(float x) { unsigned u = __float_as_uint(x); u += 0x7FFFu + ((u >> 16) & 1u); return u >> 16; }
-__device__ __forceinline__ void store_planes4(unsigned short* __restrict__ hi, unsigned short* __restrict__ lo, size_t i4, const float4& o) {
-    const float e[4] = {o.x, o.y, o.z, o.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { h[j] = ln_bf16_rne(e[j]); l[j] = ln_bf16_rne(e[j] - __uint_as_float(h[j] << 16)); }
-    reinterpret_cast<uint2*>(hi)[i4] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
-    reinterpret_cast<uint2*>(lo)[i4] = make_uint2(l[0] | (l[1] << 16), l[2] | (l[3] << 16));
-}
-// the row in v -> y and / or its bf16 planes (and xin_out = the row itself), chunk by chunk.  (round 6: batching the gamma / beta loads of
+// the row in v -> y and / or its planes in the format `fmt` (and xin_out = the row itself), chunk by chunk.  (round 6: batching the gamma / beta loads of
 // layernorm_fwd_kernel the way layernorm_bwd_kernel does costs it two waves per SIMD of occupancy -- 117 VGPRs -- and was 5 % SLOWER: with one row per
 // wave and eight waves per SIMD the chunk-by-chunk round trips are already covered)
 __device__ __forceinline__ void ln_store_row(const float4* v, float mean, float rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
                                              float* __restrict__ y, unsigned short* __restrict__ y_hi, unsigned short* __restrict__ y_lo,
-                                             float* __restrict__ xin_out, int row, int lane, int nv, float f16_scale = 0.f) {
+                                             float* __restrict__ xin_out, int row, int lane, int nv, PlaneFmt fmt = PlaneFmt::bf16()) {
     float4* __restrict__ yr = reinterpret_cast<float4*>(y) + (size_t)row * nv;
     float4* __restrict__ xo = xin_out ? reinterpret_cast<float4*>(xin_out) + (size_t)row * nv : nullptr;
     const float4* __restrict__ g4 = reinterpret_cast<const float4*>(gamma);
@@ -38,23 +27,20 @@ __device__ __forceinline__ void ln_store_row(const float4* v, float mean, float 
         if (c < nv) {
             const float4 o = ln_row_norm4(v[i], mean, rstd, g4[c], b4[c]);
             if (y) yr[c] = o;
-            if (y_hi) {                                       // f16_scale > 0: the (h1, h2) f16 planes of y * f16_scale instead (split_f16.h)
-                if (f16_scale > 0.f) store_f16_planes4(y_hi, y_lo, (size_t)row * nv + c, o, f16_scale);
-                else store_planes4(y_hi, y_lo, (size_t)row * nv + c, o);
-            }
+            if (y_hi) store_planes4(fmt, y_hi, y_lo, (size_t)row * nv + c, o);
             if (xo) xo[c] = v[i];
         }
     }
 }
 
 // y = LN(x + pos) * gamma + beta ; optionally stores xin = x + pos (needed for the residual) ; mean/rstd for backward.
-// y_hi / y_lo (optional): y also (or, with y == NULL, only) as bf16 planes.
+// y_hi / y_lo (optional): y also (or, with y == NULL, only) as planes in the format `fmt` (split_planes.h).
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ pos,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             float* __restrict__ xin_out, float* __restrict__ y,
                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                             int T, int D, float eps, unsigned short* __restrict__ y_hi = nullptr,
-                                                            unsigned short* __restrict__ y_lo = nullptr, float f16_scale = 0.f) {
+                                                            unsigned short* __restrict__ y_lo = nullptr, PlaneFmt fmt = PlaneFmt::bf16()) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= T) return;
@@ -73,7 +59,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     }
     const float mean = ln_row_mean<LN_ROW_MAXV>(v, lane, nv, D);
     const float rstd = ln_row_rstd<LN_ROW_MAXV>(v, mean, lane, nv, D, eps);
-    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, xin_out, row, lane, nv, f16_scale);
+    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, xin_out, row, lane, nv, fmt);
     if (lane == 0) { if (mean_out) mean_out[row] = mean; if (rstd_out) rstd_out[row] = rstd; }
 }
 
@@ -292,29 +278,28 @@ extern "C" int act_layernorm_fwd_f32(const float* x, const float* pos, const flo
     if (T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D * (2 + (pos ? 1 : 0) + (xin_out ? 1 : 0)));
-    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, x, pos, gamma, beta, xin_out, y, mean, rstd, T, D, eps, nullptr, nullptr, 0.f);
+    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, x, pos, gamma, beta, xin_out, y, mean, rstd, T, D, eps, nullptr, nullptr, PlaneFmt::bf16());
     ACT_LAUNCH_CHECK(); return 0;
 }
-// plane_scale == 0: bf16 (hi, lo) planes; > 0: f16 (h1, h2) planes of y * plane_scale
 static int layernorm_fwd_planes(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y, uint16_t* y_hi,
-                                uint16_t* y_lo, float plane_scale, float* mean, float* rstd, int T, int D, float eps, act_stream_t stream) {
+                                uint16_t* y_lo, PlaneFmt fmt, float* mean, float* rstd, int T, int D, float eps, act_stream_t stream) {
     if (!x || !gamma || !beta || !y_hi || !y_lo) return ACT_E_NULLPTR;
     if (T < 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
     if (T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D * (2 + (pos ? 1 : 0) + (xin_out ? 1 : 0)));
-    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, x, pos, gamma, beta, xin_out, y, mean, rstd, T, D, eps, y_hi, y_lo, plane_scale);
+    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, x, pos, gamma, beta, xin_out, y, mean, rstd, T, D, eps, y_hi, y_lo, fmt);
     ACT_LAUNCH_CHECK(); return 0;
 }
 extern "C" int act_layernorm_fwd_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                             uint16_t* y_hi, uint16_t* y_lo, float* mean, float* rstd, int T, int D, float eps, act_stream_t stream) {
-    return layernorm_fwd_planes(x, pos, gamma, beta, xin_out, y, y_hi, y_lo, 0.f, mean, rstd, T, D, eps, stream);
+    return layernorm_fwd_planes(x, pos, gamma, beta, xin_out, y, y_hi, y_lo, PlaneFmt::bf16(), mean, rstd, T, D, eps, stream);
 }
 extern "C" int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                                 uint16_t* y_h1, uint16_t* y_h2, float plane_scale, float* mean, float* rstd, int T, int D, float eps,
                                                 act_stream_t stream) {
     if (!(plane_scale > 0.f)) return ACT_E_BADARG;
-    return layernorm_fwd_planes(x, pos, gamma, beta, xin_out, y, y_h1, y_h2, plane_scale, mean, rstd, T, D, eps, stream);
+    return layernorm_fwd_planes(x, pos, gamma, beta, xin_out, y, y_h1, y_h2, PlaneFmt::f16(plane_scale), mean, rstd, T, D, eps, stream);
 }
 
 // Prompt rows of the prompt-tuned Transformer (models/dvae.py:485-498,556-566), frozen-teacher form: for every cloud b and prompt p

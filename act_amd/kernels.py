@@ -178,27 +178,37 @@ def layernorm_planes(x, gamma, beta, eps, pos=None):
     return planes
 
 
-def gemm_nt_bf16x3(a_planes, b_planes, bias=None, act=EPI_NONE, res=None, out=None, planes_out=None):
-    """C[M,N] = epilogue(a . b^T) with both operands given as (hi, lo) bf16 planes [2, rows, K] (split_bf16x2) and the three products hi.hi + hi.lo + lo.hi
-    on the bf16 matrix cores (fp32 accumulation): 4e-6 relative per product.  M, N % 128 == 0, K % 64 == 0.  Opt-in path of the frozen teacher."""
+def _x3_problem(name, dtype, a_planes, b_planes, bias, act, res, out, planes_out):
+    """what gemm_nt_bf16x3 and gemm_nt_f16x3 share: the plane, shape and ``planes_out`` checks, the result tensor and the epilogue struct
+    -> (M, N, K, the operand pointers a1, a2, b1, b2, out, the planes_out pointers o1, o2 (None, None without), epilogue)"""
+    fmt = "bf16" if dtype == torch.bfloat16 else "f16"
     _, M, Kd = a_planes.shape
     _, N, Kb = b_planes.shape
-    if Kd != Kb or a_planes.dtype != torch.bfloat16 or b_planes.dtype != torch.bfloat16 or not (a_planes.is_contiguous() and b_planes.is_contiguous()):
-        raise _C.ActHipError("gemm_nt_bf16x3: contiguous bf16 planes [2, rows, K] with equal K expected")
-    if not lib.act_sgemm_nt_bf16x3_supported(M, N, Kd):
-        raise _C.ActHipError(f"gemm_nt_bf16x3: unsupported shape {M} x {N} x {Kd} (M, N % 128, K % 64)")
+    if Kd != Kb or a_planes.dtype != dtype or b_planes.dtype != dtype or not (a_planes.is_contiguous() and b_planes.is_contiguous()):
+        raise _C.ActHipError(f"{name}: contiguous {fmt} planes [2, rows, K] with equal K expected")
+    if not lib.act_sgemm_nt_bf16x3_supported(M, N, Kd):      # (act_sgemm_nt_f16x3_supported is the same predicate)
+        raise _C.ActHipError(f"{name}: unsupported shape {M} x {N} x {Kd} (M, N % 128, K % 64)")
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=a_planes.device)
     e = GemmEpilogue(alpha=1.0, act=act, accumulate=0, rows_per_scale=0, ldr=(res.stride(0) if res is not None else 0), ldaux=0, res_row_div=0,
                      bias=ptr(bias), rowscale=None, res=ptr(res), aux=None)
-    if planes_out is not None:                               # the result also as (hi, lo) planes [2, M, N] -- the A operand of a following product
-        if planes_out.dtype != torch.bfloat16 or tuple(planes_out.shape) != (2, M, N) or not planes_out.is_contiguous():
-            raise _C.ActHipError("gemm_nt_bf16x3: planes_out must be a contiguous bf16 tensor [2, M, N]")
-        check(lib.act_sgemm_nt_bf16x3_planes_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), ptr(b_planes[0]), ptr(b_planes[1]), ptr(out), out.stride(0),
-                                                 ptr(planes_out[0]), ptr(planes_out[1]), ctypes.byref(e), stream()), "act_sgemm_nt_bf16x3_planes_f32")
-        return out
-    check(lib.act_sgemm_nt_bf16x3_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), ptr(b_planes[0]), ptr(b_planes[1]), ptr(out), out.stride(0),
-                                      ctypes.byref(e), stream()), "act_sgemm_nt_bf16x3_f32")
+    o1, o2 = (None, None)
+    if planes_out is not None:                               # the result also as planes [2, M, N] -- the A operand of a following product
+        if planes_out.dtype != dtype or tuple(planes_out.shape) != (2, M, N) or not planes_out.is_contiguous():
+            raise _C.ActHipError(f"{name}: planes_out must be a contiguous {fmt} tensor [2, M, N]")
+        o1, o2 = ptr(planes_out[0]), ptr(planes_out[1])
+    return M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), ptr(b_planes[0]), ptr(b_planes[1]), out, o1, o2, e
+
+
+def gemm_nt_bf16x3(a_planes, b_planes, bias=None, act=EPI_NONE, res=None, out=None, planes_out=None):
+    """C[M,N] = epilogue(a . b^T) with both operands given as (hi, lo) bf16 planes [2, rows, K] (split_bf16x2) and the three products hi.hi + hi.lo + lo.hi
+    on the bf16 matrix cores (fp32 accumulation): 4e-6 relative per product.  M, N % 128 == 0, K % 64 == 0.  Opt-in path of the frozen teacher."""
+    M, N, Kd, a1, a2, b1, b2, out, o1, o2, e = _x3_problem("gemm_nt_bf16x3", torch.bfloat16, a_planes, b_planes, bias, act, res, out, planes_out)
+    if planes_out is not None:
+        check(lib.act_sgemm_nt_bf16x3_planes_f32(M, N, Kd, a1, a2, b1, b2, ptr(out), out.stride(0), o1, o2, ctypes.byref(e), stream()),
+              "act_sgemm_nt_bf16x3_planes_f32")
+    else:
+        check(lib.act_sgemm_nt_bf16x3_f32(M, N, Kd, a1, a2, b1, b2, ptr(out), out.stride(0), ctypes.byref(e), stream()), "act_sgemm_nt_bf16x3_f32")
     return out
 
 
@@ -214,7 +224,7 @@ def f16x3_row_scales(w):
 
 def split_f16x2(x, scale=1.0, row_scale=None, out=None):
     """fp32 [R, K] -> f16 planes [2, R, K] of xs = x * scale * row_scale[row] (powers of two): h1 = f16(xs), h2 = f16((xs - h1) * 2^11), round to nearest
-    even, a plane element below 2^-14 written as +0 before the residual is taken (csrc/split_f16.h; tests/f16x3_ref.py restates it)."""
+    even, a plane element below 2^-14 written as +0 before the residual is taken (csrc/split_planes.h; tests/f16x3_ref.py restates it)."""
     x = _f32rows(x, "x")
     R, Kd = x.shape
     if out is None:
@@ -239,27 +249,12 @@ def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_N
     f16x3_row_scales) and the products h1.h1 + 2^-11 (h1.h2 + h2.h1) on the f16 matrix cores, two fp32 accumulators: fp32-grade.  M, N % 128 == 0,
     K % 64 == 0.  ``planes_out`` [2, M, N] f16: the result also as planes at ``out_scale`` -- the A operand of a following product.  ``tile``: 0 = the
     library's rule (act_sgemm_nt_f16x3_pick_tile), 128 or 192 = that column width of the tile (tests and A/B runs; the bits do not depend on it)."""
-    _, M, Kd = a_planes.shape
-    _, N, Kb = b_planes.shape
-    if Kd != Kb or a_planes.dtype != torch.float16 or b_planes.dtype != torch.float16 or not (a_planes.is_contiguous() and b_planes.is_contiguous()):
-        raise _C.ActHipError("gemm_nt_f16x3: contiguous f16 planes [2, rows, K] with equal K expected")
-    if not lib.act_sgemm_nt_f16x3_supported(M, N, Kd):
-        raise _C.ActHipError(f"gemm_nt_f16x3: unsupported shape {M} x {N} x {Kd} (M, N % 128, K % 64)")
+    M, N, Kd, a1, a2, b1, b2, out, o1, o2, e = _x3_problem("gemm_nt_f16x3", torch.float16, a_planes, b_planes, bias, act, res, out, planes_out)
     b_inv_scale = _f32c(b_inv_scale)
     if b_inv_scale.numel() != N:
         raise _C.ActHipError("gemm_nt_f16x3: b_inv_scale must hold one value per row of b")
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.float32, device=a_planes.device)
-    e = GemmEpilogue(alpha=1.0, act=act, accumulate=0, rows_per_scale=0, ldr=(res.stride(0) if res is not None else 0), ldaux=0, res_row_div=0,
-                     bias=ptr(bias), rowscale=None, res=ptr(res), aux=None)
-    oh, ol = (None, None)
-    if planes_out is not None:
-        if planes_out.dtype != torch.float16 or tuple(planes_out.shape) != (2, M, N) or not planes_out.is_contiguous():
-            raise _C.ActHipError("gemm_nt_f16x3: planes_out must be a contiguous f16 tensor [2, M, N]")
-        oh, ol = ptr(planes_out[0]), ptr(planes_out[1])
-    check(lib.act_sgemm_nt_f16x3_planes_tile_f32(M, N, Kd, ptr(a_planes[0]), ptr(a_planes[1]), float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]),
-                                                 ptr(b_inv_scale), ptr(out), out.stride(0), oh, ol, float(out_scale), ctypes.byref(e), stream(), int(tile)),
-          "act_sgemm_nt_f16x3_planes_tile_f32")
+    check(lib.act_sgemm_nt_f16x3_planes_tile_f32(M, N, Kd, a1, a2, float(a_scale), b1, b2, ptr(b_inv_scale), ptr(out), out.stride(0), o1, o2, float(out_scale),
+                                                 ctypes.byref(e), stream(), int(tile)), "act_sgemm_nt_f16x3_planes_tile_f32")
     return out
 
 

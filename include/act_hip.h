@@ -420,7 +420,7 @@ int act_attention_fwd_prefix_planes_f32(const float* kv0, int S0, const float* q
 int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
                                    float* C, int ldc, uint16_t* out_hi, uint16_t* out_lo, const act_gemm_epilogue_t* epilogue, act_stream_t stream);
 
-/* ---- DEFAULT teacher arithmetic: the same kernel on f16 planes with a scaled low plane ("f16x3", csrc/gemm_bf16x3.hip F16 form, csrc/split_f16.h) ----
+/* ---- DEFAULT teacher arithmetic: the same kernel on f16 planes with a scaled low plane ("f16x3", csrc/gemm_bf16x3.hip F16 form, csrc/split_planes.h) ----
  * x s = h1 + 2^-11 h2 with h1 = f16(x s), h2 = f16((x s - h1) 2^11) (round to nearest even; a plane element below 2^-14 is written as +0 before the
  * residual is taken), s a power of two that keeps |x s| <= 2^15: 22 significand bits + the residual's sign per operand, fp32-grade products.
  * C = epilogue( (A_h1.B_h1^T + 2^-11 (A_h1.B_h2^T + A_h2.B_h1^T)) * b_inv_scale[n] / a_scale ), two fp32 accumulators, lo.lo term (2^-22) dropped.

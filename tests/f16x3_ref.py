@@ -1,4 +1,4 @@
-"""numpy restatement of the split-f16 teacher arithmetic (act_amd/csrc/split_f16.h, gemm_bf16x3.hip F16 form, composite.f16x3_*): the plane split, the scale
+"""numpy restatement of the split-f16 teacher arithmetic (act_amd/csrc/split_planes.h, gemm_bf16x3.hip F16 form, composite.f16x3_*): the plane split, the scale
 rules, the three-product GEMM with its two accumulators, and the weight-only range-guard bounds.  Written from the specification, not from the kernels:
 tests/test_f16x3_host.py checks it against float64, tests/test_gpu_f16x3.py checks the kernels against it bit for bit."""
 import math

@@ -82,7 +82,9 @@ def test_bf16x3_planes_output_is_the_split_of_the_fp32_output(dev):
 
 
 def test_producers_that_emit_planes_equal_a_split_of_their_fp32_result(dev):
-    """LayerNorm writing planes == split(LayerNorm) bit for bit; the prefix attention forward writing planes == split(its fp32 output)"""
+    """LayerNorm writing planes == split(LayerNorm) bit for bit; the prefix attention forward writing planes == split(its fp32 output); the prompt
+    LayerNorm writing planes == split(prompt LayerNorm) for the same seed, without and with dropout (ten rows of 264: the last four-row workgroup and the
+    second 64-lane chunk of 66 float4 are both ragged)"""
     import ctypes
     import act_amd.kernels as K
     from act_amd import _C
@@ -98,6 +100,14 @@ def test_producers_that_emit_planes_equal_a_split_of_their_fp32_result(dev):
     _C.check(_C.lib.act_attention_fwd_prefix_planes_f32(_C.ptr(kv0), S0, _C.ptr(qkv), Sq, None, _C.ptr(planes[0]), _C.ptr(planes[1]), None, B, H, hd,
                                                         float(hd) ** -0.5, _C.stream()), "act_attention_fwd_prefix_planes_f32")
     assert torch.equal(planes, K.split_bf16x2(out))
+    B, P, D = 2, 5, 264
+    tok = torch.randn(P, D, device=dev); ppos = 0.1 * torch.randn(P, D, device=dev)
+    g = 1 + 0.1 * torch.randn(D, device=dev); b = 0.1 * torch.randn(D, device=dev)
+    for drop_p, seed in ((0.0, 0), (0.25, 1234)):
+        planes = torch.empty(2, B * P, D, dtype=torch.bfloat16, device=dev)
+        _C.check(_C.lib.act_prompt_layernorm_fwd_planes_f32(_C.ptr(tok), _C.ptr(ppos), B, P, D, drop_p, seed, None, _C.ptr(g), _C.ptr(b), 1e-6,
+                                                            _C.ptr(planes[0]), _C.ptr(planes[1]), _C.stream()), "act_prompt_layernorm_fwd_planes_f32")
+        assert torch.equal(planes, K.split_bf16x2(K.prompt_layernorm(tok, ppos, B, drop_p, seed, g, b, 1e-6))), drop_p
 
 
 def test_bf16x3_rejects_what_it_does_not_support(dev):

@@ -1,5 +1,5 @@
 """The DEFAULT arithmetic of the frozen teacher's four Linear products per layer: split-f16 planes with a scaled low plane (csrc/gemm_bf16x3.hip F16 form,
-csrc/split_f16.h, ACT_TEACHER_F16X3).  Kernel level: the split equals the numpy restatement (tests/f16x3_ref.py) bit for bit, the GEMM is EXACT on lattice
+csrc/split_planes.h, ACT_TEACHER_F16X3).  Kernel level: the split equals the numpy restatement (tests/f16x3_ref.py) bit for bit, the GEMM is EXACT on lattice
 operands and fp32-grade on real ones (error against float64 within 1.5 x the f32 kernel's, same operands, same test).  Model level: the teacher's features
 with the switch on sit as close to the CPU oracle as the f32 path does (within 2 x), the f32 path is untouched, the range guard falls back per Linear, and
 the plane cache follows in-place weight changes."""
