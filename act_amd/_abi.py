@@ -323,6 +323,15 @@ _TABLE = {
     "act_three_adj_i32": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "act_interp_rows_any_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
     "act_interp_rows_any_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    # DGCNN classifier: feature-space kNN, EdgeConv tail with BatchNorm, LeakyReLU row BatchNorm (csrc/edgeconv.hip)
+    "act_knn_feat_f32": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "act_edge_bn_workspace": (_sz, [_i, _i, _i, _i]),
+    "act_edge_bn_lrelu_max_fwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _sz, _vp],
+    "act_edge_bn_lrelu_max_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_affine_lrelu_f32": [_vp, _vp, _vp, _f, _i, _i, _vp, _vp],
+    "act_bn_lrelu_bwd_workspace": (_sz, [_i, _i]),
+    "act_bn_lrelu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -39,6 +39,10 @@ int act_prompt_kv_rows(const float* tok, const float* ppos, int B, int P, int D,
 int act_prompt_kv_correct(const float* tok, int B, int P, int D, int N, float drop_p, const float* gamma, const float* W, const float* bias,
                           const ActPromptKvWs& w, float* kvp, hipStream_t s);
 
+// ---- inverse adjacency (sa.hip): idx int32 [B,E] with values in [0,N) -> off [B,N+1], ent [B,E], the entries of every point ascending; count,
+// exclusive scan, fill, no atomics.  Entries outside [0,N) are in no list.  B <= 65535.
+int act_sa_build_adjacency(const int32_t* idx, int B, int N, int E, int32_t* off, int32_t* ent, hipStream_t s);
+
 #define ACT_LAUNCH_CHECK() do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
 
 // Single-pass statistics around a pivot element (mean = pivot + dm, var = q / n - dm^2) are kept while dm^2 <= FAR_PIVOT * var; past that the

@@ -219,6 +219,11 @@ static int build_adjacency(const int32_t* idx, int B, int N, int E, int32_t* off
     return 0;
 }
 
+// the same adjacency for the other files of the library (edgeconv.hip); declared in common.h
+int act_sa_build_adjacency(const int32_t* idx, int B, int N, int E, int32_t* off, int32_t* ent, hipStream_t s) {
+    return build_adjacency(idx, B, N, E, off, ent, s);
+}
+
 extern "C" size_t act_group_rows_bwd_workspace(int B, int N, int S, int nsample) {
     if (B <= 0 || N <= 0 || S <= 0 || nsample <= 0) return 0;
     return adj_bytes(B, N, (long long)S * nsample);

@@ -1005,11 +1005,16 @@ def _sync_group(bn):
     return group if dist.get_world_size(group) > 1 else None
 
 
-def batch_norm_act(x, bn, training, relu=True):
-    """functional nn.BatchNorm1d / nn.SyncBatchNorm (+ReLU) on rows [R,C] with the module's parameters and buffers."""
+def batch_norm_act(x, bn, training, relu=True, slope=None):
+    """functional nn.BatchNorm1d / nn.SyncBatchNorm (+ReLU) on rows [R,C] with the module's parameters and buffers.  ``slope`` (a float): LeakyReLU
+    of that slope follows instead (``relu`` is then ignored; csrc/edgeconv.hip); None: exactly the ReLU / identity path."""
+    group = _sync_group(bn) if training else None
+    if slope is not None and group is not None:
+        raise NotImplementedError("batch_norm_act: slope= with a SyncBatchNorm across ranks is not implemented")
     if training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    group = _sync_group(bn) if training else None
+    if slope is not None:
+        return BNLreluFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps, float(slope))
     if group is not None:
         return SyncBNActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, relu, group)
     return BNActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps, relu)
@@ -2583,3 +2588,149 @@ class InterpRowsAnyFn(torch.autograd.Function):
 def interp_rows_any(x, nn3, B, N, G):
     """x [B*G,C] rows of the known points, nn3 = (idx, weight, adj_off | None, adj_ent | None) -> [B*N,C]; differentiable in ``x``"""
     return InterpRowsAnyFn.apply(x, nn3, B, N, G)
+
+
+# ---- DGCNN classifier (csrc/edgeconv.hip): feature-space kNN, EdgeConv tail with BatchNorm, LeakyReLU row BatchNorm ------------------------------
+KNN_FEAT_MAX_K = 64
+KNN_FEAT_MAX_C = 512
+
+
+def knn_features(x, k, want_d2=False):
+    """x [B,N,C] -> idx int32 [B,N,k] (and d2 [B,N,k] with ``want_d2``): per point the k nearest points of its own cloud in feature space, itself
+    included, in ascending (d2, index) order; d2 is the fp32 difference form summed over ascending channels.  1 <= C <= 512, 1 <= k <= min(N, 64).
+    No gradient."""
+    x = _sa_f32(x.detach() if isinstance(x, torch.Tensor) else x, "knn_features: x", (None, None, None))
+    B, N, C = x.shape
+    k = int(k)
+    if B < 1 or N < 1 or not 1 <= C <= KNN_FEAT_MAX_C:
+        raise ValueError(f"knn_features: x: expected a non-empty [B, N, C] with C <= {KNN_FEAT_MAX_C}, got {list(x.shape)}")
+    if not 1 <= k <= min(N, KNN_FEAT_MAX_K):
+        raise ValueError(f"knn_features: k must be in [1, min(N, {KNN_FEAT_MAX_K})] = [1, {min(N, KNN_FEAT_MAX_K)}], got {k}")
+    if B > 65535:
+        raise ValueError(f"knn_features: B must be <= 65535, got {B}")
+    idx = torch.empty(B, N, k, dtype=torch.int32, device=x.device)
+    d2 = torch.empty(B, N, k, dtype=torch.float32, device=x.device) if want_d2 else None
+    rc = lib.act_knn_feat_f32(ptr(x), B, N, C, k, ptr(idx), ptr(d2), stream())
+    if rc in (-1, -2):
+        raise ValueError(f"act_knn_feat_f32 refused B={B}, N={N}, C={C}, k={k} (code {rc})")
+    check(rc, "act_knn_feat_f32")
+    return (idx, d2) if want_d2 else idx
+
+
+class EdgeBnLreluMaxFn(torch.autograd.Function):
+    """out[b*N+i, c] = max_j LeakyReLU(BatchNorm(P[b, idx[b,i,j], c] + Q[b,i,c])) with pq = [P | ... | Q] (Q at column qoff) and the BatchNorm over
+    all B*N*k edges; no edge tensor is formed, forward or backward (csrc/edgeconv.hip).  Differentiable in pq, gamma and beta."""
+
+    @staticmethod
+    def forward(ctx, pq, gamma, beta, running_mean, running_var, idx, qoff, B, N, k, C, training, momentum, eps, slope):
+        pq = _f32c(pq, "edge_conv_bn: pq")
+        dev = pq.device
+        R = B * N
+        out = torch.empty(R, C, dtype=torch.float32, device=dev)
+        arg = torch.empty(R, C, dtype=torch.int32, device=dev)
+        vsum = torch.empty(R, C, dtype=torch.float32, device=dev)
+        mean, mean_lo, rstd = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3))
+        ws = workspace(dev, lib.act_edge_bn_workspace(B, N, k, C))
+        check(lib.act_edge_bn_lrelu_max_fwd_f32(ptr(pq), pq.stride(0), int(qoff), ptr(idx), B, N, k, C, ptr(gamma), ptr(beta), ptr(running_mean),
+                                                ptr(running_var), int(training), float(momentum), float(eps), float(slope), ptr(out), C, 0,
+                                                ptr(arg), ptr(vsum), ptr(mean), ptr(mean_lo), ptr(rstd), ptr(ws), ws.numel() * 4, stream()),
+              "act_edge_bn_lrelu_max_fwd_f32")
+        ctx.save_for_backward(pq, gamma, beta, idx, arg, vsum, mean, mean_lo, rstd)
+        ctx.cfg = (int(qoff), B, N, k, C, bool(training), float(slope))
+        ctx.mark_non_differentiable(arg, vsum)
+        return out, arg, vsum
+
+    @staticmethod
+    def backward(ctx, dout, _darg, _dvsum):
+        pq, gamma, beta, idx, arg, vsum, mean, mean_lo, rstd = ctx.saved_tensors
+        qoff, B, N, k, C, training, slope = ctx.cfg
+        if not training:
+            raise NotImplementedError("EdgeConv BatchNorm backward in eval mode is off the training path")
+        if qoff < C:
+            raise ValueError(f"edge_conv_bn: backward needs P and Q in separate columns (qoff >= C), got qoff={qoff}, C={C}")
+        dout = _f32c(dout, "edge_conv_bn: grad")
+        dev = pq.device
+        dpq = torch.empty_like(pq) if (pq.shape[1] == 2 * C and qoff == C) else torch.zeros_like(pq)
+        dg, db = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(C, dtype=torch.float32, device=dev)
+        ws = workspace(dev, lib.act_edge_bn_workspace(B, N, k, C))
+        check(lib.act_edge_bn_lrelu_max_bwd_f32(ptr(pq), pq.stride(0), qoff, ptr(idx), B, N, k, C, ptr(gamma), ptr(beta), ptr(mean), ptr(mean_lo), ptr(rstd),
+                                                slope, ptr(arg), ptr(vsum), ptr(dout), dout.stride(0), ptr(dpq), ptr(dg), ptr(db), ptr(ws),
+                                                ws.numel() * 4, stream()), "act_edge_bn_lrelu_max_bwd_f32")
+        return (dpq, dg, db) + (None,) * 12
+
+
+def edge_conv_bn(pq, qoff, idx, B, N, k, C, bn, training, slope=0.2, validate=True, want_aux=False):
+    """pq [B*N, ld] (P at column 0, Q at column ``qoff``), idx int [B,N,k] -> [B*N, C]: the fused tail of an EdgeConv layer with the parameters and
+    buffers of the BatchNorm module ``bn`` (see EdgeBnLreluMaxFn).  ``validate``: range-check idx on the device (one host read) and raise ValueError
+    for an index outside [0,N); pass False for indices ``knn_features`` made.  ``want_aux``: also return (arg, vsum)."""
+    B, N, k, C, qoff = int(B), int(N), int(k), int(C), int(qoff)
+    if not isinstance(pq, torch.Tensor) or not pq.is_cuda:
+        raise _C.ActHipError("edge_conv_bn: pq: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if pq.dtype != torch.float32 or pq.dim() != 2:
+        raise _C.ActHipError(f"edge_conv_bn: pq: expected float32 [B*N, ld], got {pq.dtype} {list(pq.shape)}")
+    if B < 1 or N < 1 or k < 1 or C < 1 or C % 4:
+        raise ValueError(f"edge_conv_bn: need B, N, k >= 1 and C % 4 == 0, got B={B}, N={N}, k={k}, C={C}")
+    if B > 65535 or k > 65535:
+        raise ValueError(f"edge_conv_bn: B and k must be <= 65535, got B={B}, k={k}")
+    if pq.shape[0] != B * N or qoff < 0 or qoff + C > pq.shape[1]:
+        raise ValueError(f"edge_conv_bn: pq {list(pq.shape)} does not hold [B*N={B * N}] rows with Q at columns [{qoff}, {qoff + C})")
+    if bn.num_features != C or bn.weight is None:
+        raise ValueError(f"edge_conv_bn: bn must be an affine BatchNorm over {C} channels")
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+        raise _C.ActHipError("edge_conv_bn: idx: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if idx.dtype not in (torch.int32, torch.int64) or tuple(idx.shape) != (B, N, k):
+        raise ValueError(f"edge_conv_bn: idx: expected int32 [{B}, {N}, {k}], got {idx.dtype} {list(idx.shape)}")
+    if validate and bool(((idx < 0) | (idx >= N)).any()):
+        raise ValueError(f"edge_conv_bn: idx holds an index outside [0, {N})")
+    idx = _i32c(idx)
+    if training and _sync_group(bn) is not None:
+        raise NotImplementedError("edge_conv_bn: SyncBatchNorm across ranks is not implemented for the EdgeConv tail")
+    if not training and bn.running_mean is None:
+        raise ValueError("edge_conv_bn: eval mode needs running statistics")
+    if training and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    momentum = 0.1 if bn.momentum is None else bn.momentum
+    out, arg, vsum = EdgeBnLreluMaxFn.apply(pq, bn.weight, bn.bias, bn.running_mean, bn.running_var, idx, qoff, B, N, k, C, bool(training), momentum,
+                                            bn.eps, slope)
+    return (out, arg, vsum) if want_aux else out
+
+
+class BNLreluFn(torch.autograd.Function):
+    """BNActFn with LeakyReLU(slope) in place of ReLU: the statistics kernel is shared, the apply and the backward carry the slope."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, slope):
+        x = _f32c(x)
+        R, C = x.shape
+        dev = x.device
+        y = torch.empty_like(x)
+        if training:
+            mean, rstd, scale, shift = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(4))
+            ws = workspace(dev, lib.act_colstats_workspace(R, C))
+            check(lib.act_bn_stats_f32(ptr(x), R, C, ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean),
+                                       ptr(running_var), ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(ws), ws.numel() * 4,
+                                       stream()), "act_bn_stats_f32")
+        else:
+            rstd = torch.rsqrt(running_var + eps)
+            mean = running_mean
+            scale = gamma * rstd
+            shift = beta - running_mean * scale
+        check(lib.act_affine_lrelu_f32(ptr(x), ptr(scale), ptr(shift), float(slope), R, C, ptr(y), stream()), "act_affine_lrelu_f32")
+        ctx.save_for_backward(x, scale, shift, mean, rstd)
+        ctx.training, ctx.slope = training, float(slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, scale, shift, mean, rstd = ctx.saved_tensors
+        dy = _f32c(dy)
+        R, C = x.shape
+        if not ctx.training:
+            raise NotImplementedError("BatchNorm backward in eval mode is off the training path")
+        dx = torch.empty_like(x)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = workspace(x.device, lib.act_bn_lrelu_bwd_workspace(R, C))
+        check(lib.act_bn_lrelu_bwd_f32(ptr(x), ptr(dy), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), ctx.slope, R, C, ptr(dx), ptr(dg), ptr(db),
+                                       ptr(ws), ws.numel() * 4, stream()), "act_bn_lrelu_bwd_f32")
+        return dx, dg, db, None, None, None, None, None, None

@@ -3,3 +3,4 @@ from . import dvae  # noqa: F401
 from . import act  # noqa: F401
 from . import bert  # noqa: F401
 from . import pointnet2_nets  # noqa: F401
+from . import dgcnn_nets  # noqa: F401

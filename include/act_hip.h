@@ -1011,6 +1011,45 @@ int act_interp_rows_any_fwd_f32(const float* P, const int32_t* idx, const float*
 int act_interp_rows_any_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
                                 float* dP, act_stream_t stream);
 
+/* ---- DGCNN classifier (csrc/edgeconv.hip; Wang et al. 2019) ----------------------------------------------------------------------------
+ * Batched Euclidean kNN in feature space: x fp32 [B,N,C] -> idx int32 [B,N,k], d2 fp32 [B,N,k] (may be NULL): for every point of a cloud
+ * the k points of the same cloud in ascending (d2, index) order, the point itself a candidate.  d2(i,j) = sum_c (x_ic - x_jc)^2 in the
+ * difference form, channels ascending, every subtraction, product and sum rounded, no FMA: d2(i,i) == 0 and d2 is symmetric.  A NaN
+ * distance orders after every other one (ties by index), so a row is always k distinct indices in [0,N).  No atomics; a cloud's result does
+ * not depend on B.  N >= 1, 1 <= C <= 512, 1 <= k <= min(N, 64), B <= 65535, else ACT_E_BADARG. */
+int act_knn_feat_f32(const float* x, int B, int N, int C, int k, int32_t* idx, float* d2, act_stream_t stream);
+/* Fused EdgeConv tail with BatchNorm.  pq fp32 [B*N, ld] holds P at column 0 and Q at column qoff; idx int32 [B,N,k], any values (an
+ * index outside [0,N) is clamped into range, duplicates allowed); C % 4 == 0, k <= 65535, B <= 65535.
+ *   v[b,i,j,c] = P[b, idx[b,i,j], c] + Q[b,i,c]          (one rounded add, never stored)
+ *   training != 0: mean_c and the biased var_c over the B*N*k values of v[..,c] (float64 moments around a value of v), and running_mean /
+ *                  running_var (both or neither NULL) move by momentum, the variance unbiased; training == 0: the running statistics
+ *   scale_c = gamma_c * rstd_c, shift_c = beta_c - mean_c * scale_c, out[b*N+i, ooff + c] = max_j LeakyReLU_slope(scale_c * v + shift_c),
+ * evaluated on the largest v (scale_c >= 0) or the smallest (scale_c < 0), which is exact because the map is monotone, and in the centred form
+ * scale_c * ((v - mean_c) - mean_lo_c) + beta_c so that a common offset of v does not cancel.  Also written: arg int32 [B*N,C] the selected j
+ * (the lowest on ties), vsum [B*N,C] = sum_j v in ascending j, mean, mean_lo (the float64 mean minus its float32 rounding; 0 in eval mode)
+ * and rstd [C].  Fixed order, no atomics. */
+size_t act_edge_bn_workspace(int B, int N, int k, int C);
+int act_edge_bn_lrelu_max_fwd_f32(const float* pq, int ld, int qoff, const int32_t* idx, int B, int N, int k, int C, const float* gamma,
+                                  const float* beta, float* running_mean, float* running_var, int training, float momentum, float eps,
+                                  float slope, float* out, int ldo, int ooff, int32_t* arg, float* vsum, float* mean, float* mean_lo,
+                                  float* rstd, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* its backward in train mode, from the forward's arg, vsum, mean, mean_lo and rstd and dout [B*N, ldd]: dpq [B*N, ld] receives dP at column 0 and dQ
+ * at column qoff (qoff >= C; other columns are not written), dgamma and dbeta [C].  The BatchNorm backward of the materialised form,
+ * gathered per point over the inverse adjacency of the clamped idx (built in the workspace: count, exclusive scan, fill) in ascending
+ * (i, j): no atomics, bit-identical run to run. */
+int act_edge_bn_lrelu_max_bwd_f32(const float* pq, int ld, int qoff, const int32_t* idx, int B, int N, int k, int C, const float* gamma,
+                                  const float* beta, const float* mean, const float* mean_lo, const float* rstd, float slope,
+                                  const int32_t* arg, const float* vsum, const float* dout, int ldd, float* dpq, float* dgamma,
+                                  float* dbeta, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* LeakyReLU forms of act_affine_act_f32 and act_bn_bwd_f32 on rows [R,C]: y = LeakyReLU_slope(x * scale + shift) (product and sum rounded),
+ * and with g = dy * (z > 0 ? 1 : slope): dbeta = sum g, dgamma = sum g xhat (float64 sums in a fixed order), dx = scale * (g - dbeta / R -
+ * xhat * dgamma / R). */
+int act_affine_lrelu_f32(const float* x, const float* scale, const float* shift, float slope, int R, int C, float* y, act_stream_t stream);
+size_t act_bn_lrelu_bwd_workspace(int R, int C);
+int act_bn_lrelu_bwd_f32(const float* x, const float* dy, const float* scale, const float* shift, const float* mean, const float* rstd,
+                         float slope, int R, int C, float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
+                         act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
