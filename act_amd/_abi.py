@@ -79,6 +79,10 @@ class DgcnnF16x3(ctypes.Structure):                    # act_dgcnn_f16x3_t
     _fields_ = [("w5_planes", _vp), ("w5_inv_scale", _vp), ("a_scale", _f), ("a_planes", _vp), ("a_planes_elems", _sz)]
 
 
+class PointnetF16x3(ctypes.Structure):                 # act_pointnet_f16x3_t
+    _fields_ = [("c4_planes", _vp), ("c4_inv_scale", _vp), ("a_scale", _f)]
+
+
 class AugmentOp(ctypes.Structure):                     # act_augment_op_t
     _fields_ = [("kind", _i), ("p0", _f), ("p1", _f), ("p2", _f), ("draws", _vp), ("draws2", _vp)]
 
@@ -90,6 +94,7 @@ STRUCTS = {
     "act_prefix_vit_t": PrefixVit, "act_vit_bf16x3_t": VitBf16x3, "act_vit_f16x3_t": VitF16x3,
     "act_pointnet_params_t": PointnetParams,
     "act_pointnet_grads_t": PointnetGrads, "act_pointnet_dims_t": PointnetDims, "act_dgcnn_t": Dgcnn, "act_dgcnn_f16x3_t": DgcnnF16x3,
+    "act_pointnet_f16x3_t": PointnetF16x3,
     "act_augment_op_t": AugmentOp,
 }
 
@@ -195,6 +200,10 @@ _TABLE = {
     "act_sgemm_nt_f16x3_planes_tile_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
     "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
     "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
+    "act_split_f16x2_affine_relu_f32": [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp],
+    "act_sgemm_nt_f16x3_gmax_supported": [_i, _i, _i, _i],
+    "act_sgemm_nt_f16x3_gmax_pick_tile": [_i, _i, _i, _i],
+    "act_sgemm_nt_f16x3_gmax_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
     # GEMM launch-configuration table
     "act_gemm_tune_set": [_i] * 7,
     "act_gemm_tune_get": [_i] * 5 + [_P(_i), _P(_i)],
@@ -232,6 +241,7 @@ _TABLE = {
     "act_pointnet_saved_floats": (_sz, [_pnd]),
     "act_pointnet_fwd_f32": [_pnd, _pnp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "act_pointnet_fwd_groups_f32": [_pnd, _pnp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp],
+    "act_pointnet_fwd_groups_f16x3_f32": [_pnd, _pnp, _P(PointnetF16x3), _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp],
     "act_pointnet_bwd_scratch_floats": (_sz, [_pnd]),
     "act_pointnet_bwd_f32": [_pnd, _pnp, _vp, _vp, _vp, _P(PointnetGrads), _vp, _vp, _sz, _vp],
     "act_dgcnn_scratch_floats": (_sz, [_P(Dgcnn)]),

@@ -20,6 +20,7 @@ import torch
 from . import _C
 from . import kernels as K
 from ._abi import BlockDims, BlockParams, BlockStack, Dgcnn, PointnetDims, PointnetGrads, PointnetParams, PrefixVit, VitBf16x3, VitF16x3, DgcnnF16x3
+from ._abi import PointnetF16x3
 from ._abi import GemmFx          # noqa: F401  (tests and benchmarks build it as CP.GemmFx)
 
 lib, check = _C.lib, _C.check
@@ -306,6 +307,12 @@ _VIT_F16 = weakref.WeakKeyDictionary()         # tokenizer -> (signature, planes
 # four edge-conv products stay on the f32 kernel).  fp32-grade, not bit-identical (notebook/tokenizer_f16x3.md); ACT_TOKENIZER_F16X3=0 restores the f32 path
 # bit for bit.  Stage I trains the tokenizer under autograd and never comes here.
 TOKENIZER_F16X3 = os.environ.get("ACT_TOKENIZER_F16X3", "1") != "0"
+# DEFAULT ON: the last product of the FROZEN tokenizer's mini-PointNet (pointnet_forward below: R x C x 512 against the frozen second_conv[3] weight, the group
+# max-pool as its epilogue) on the same split-f16 kernel, BatchNorm-2 + ReLU + the split applied while the kernel stages h3.  Taken under no-grad, with every
+# parameter of the encoder frozen and training-mode statistics (the bound on the operand comes from them); fp32-grade, not bit-identical
+# (notebook/pn_f16x3.md); ACT_TOKENIZER_PN_F16X3=0 restores the f32 path bit for bit.  The student's encoder and Stage I's tokenizer train and never come here.
+TOKENIZER_PN_F16X3 = os.environ.get("ACT_TOKENIZER_PN_F16X3", "1") != "0"
+_PN_F16 = weakref.WeakKeyDictionary()          # Encoder -> (signature, c4 planes, inverse row scales, max|gamma|, max|beta| of bn2, {R: a_scale})
 _DGCNN_F16 = weakref.WeakKeyDictionary()       # DGCNN -> (signature, w5 planes, inverse row scales, max|gamma|, max|beta|, couts, groups, {(G, k): a_scale})
 
 
@@ -646,8 +653,9 @@ class PointnetFn(torch.autograd.Function):
     ``buffers`` = (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var), updated in place when training."""
 
     @staticmethod
-    def forward(ctx, x, c1w, c1b, g1, b1, c2w, c2b, c3w, c3b, g2, b2, c4w, c4b, buffers, dims, training, groups=None):
+    def forward(ctx, x, c1w, c1b, g1, b1, c2w, c2b, c3w, c3b, g2, b2, c4w, c4b, buffers, dims, training, groups=None, x3=None):
         # ``groups``: int32 ids of the only groups whose tokens are wanted (padded so that len * n % 128 == 0), or None for all
+        # ``x3``: PointnetF16x3 of a frozen encoder under no-grad (pointnet_forward), or None
         dev = x.device
         x = K._f32c(x)
         need_grad = any(ctx.needs_input_grad)
@@ -658,8 +666,12 @@ class PointnetFn(torch.autograd.Function):
         ng = 0 if groups is None else int(groups.numel())
         args = (ctypes.byref(dims), ctypes.byref(prm), _p(x), int(training), int(need_grad), _p(saved), _p(out),
                 _p(groups) if ng else None, ng, _p(ws), ws.numel() * 4)
+        # (the f32 shapes are collected and tuned in either mode: a last product the split-f16 kernel does not take falls back to them)
         ensure_tuned(("pn_fwd", dims.BG, dims.n, dims.C, ng), lambda: lib.act_pointnet_fwd_groups_f32(*args, _C.stream()), dev)
-        check(lib.act_pointnet_fwd_groups_f32(*args, _C.stream()), "act_pointnet_fwd_groups_f32")
+        if x3 is not None and not need_grad:
+            check(lib.act_pointnet_fwd_groups_f16x3_f32(args[0], args[1], ctypes.byref(x3), *args[2:], _C.stream()), "act_pointnet_fwd_groups_f16x3_f32")
+        else:
+            check(lib.act_pointnet_fwd_groups_f32(*args, _C.stream()), "act_pointnet_fwd_groups_f32")
         if need_grad:
             ctx.save_for_backward(x, saved, c1w, c1b, g1, b1, c2w, c2b, c3w, c3b, g2, b2, c4w, c4b)
             ctx.dims, ctx.training = dims, bool(training)
@@ -682,7 +694,36 @@ class PointnetFn(torch.autograd.Function):
         args = (ctypes.byref(dims), ctypes.byref(prm), _p(x), _p(saved), _p(dout), ctypes.byref(gp), _p(scratch), _p(ws), ws.numel() * 4)
         ensure_tuned(("pn_bwd", dims.BG, dims.n, dims.C), lambda: lib.act_pointnet_bwd_f32(*args, _C.stream()), dev)
         check(lib.act_pointnet_bwd_f32(*args, _C.stream()), "act_pointnet_bwd_f32")
-        return (None,) + grads + (None, None, None, None)
+        return (None,) + grads + (None, None, None, None, None)
+
+
+def f16x3_pointnet_bound(gmax, bmax, R):
+    """weight-only bound on every element of the last conv's A operand relu(bn2(h3)) under TRAINING-mode statistics: BatchNorm over the R rows of a column
+    standardises to |x - mean| rstd <= sqrt(R - 1) < sqrt(R) (biased variance, eps >= 0), so |y| <= sqrt(R) max|gamma| + max|beta|, and ReLU does not enlarge it.
+    (Running statistics give no such bound: the eval-mode forward stays on the f32 product.)  gmax / bmax: max|gamma| / max|beta| of bn2 (host floats)."""
+    return math.sqrt(R) * gmax + bmax
+
+
+def _pointnet_f16_planes(enc, R):
+    """f16 (h1, h2) planes of the frozen second_conv[3] weight with one power-of-two scale per output row, the inverse scales and max|gamma|, max|beta| of bn2
+    (read to the host HERE, never per step) -- computed ONCE and cached per Encoder under the (address, version) signature of the three tensors
+    (load_state_dict copies in place); the activation scale is host arithmetic from those and the call's row count.  -> (PointnetF16x3, keep-alive)"""
+    bn2, c4 = enc.second_conv[1], enc.second_conv[3]
+    sig = tuple((t.data_ptr(), t._version) for t in (c4.weight, bn2.weight, bn2.bias))
+    cache = _PN_F16.get(enc)
+    if cache is None or cache[0] != sig:
+        with torch.no_grad():
+            w = c4.weight.detach().reshape(c4.weight.shape[0], c4.weight.shape[1])
+            scale, inv = K.f16x3_row_scales(w)
+            planes = K.split_f16x2(w, 1.0, scale)
+            inv = inv.contiguous()
+            gmax, bmax = torch.stack([bn2.weight.detach().double().abs().max(), bn2.bias.detach().double().abs().max()]).tolist()
+        cache = _PN_F16[enc] = (sig, planes, inv, gmax, bmax, {})
+    _, planes, inv, gmax, bmax, scales = cache
+    a_scale = scales.get(R)
+    if a_scale is None:
+        a_scale = scales[R] = f16x3_act_scale(f16x3_pointnet_bound(gmax, bmax, R))
+    return PointnetF16x3(planes.data_ptr(), inv.data_ptr(), a_scale), cache
 
 
 def pointnet_forward(enc, point_groups, need=None):
@@ -702,9 +743,15 @@ def pointnet_forward(enc, point_groups, need=None):
             if bn.num_batches_tracked is not None:
                 bn.num_batches_tracked.add_(1)
     w2 = lambda c: c.weight.view(c.weight.shape[0], c.weight.shape[1])
+    x3 = keep = None
+    # frozen encoder under no-grad with batch statistics (the bound of the split path needs them): the tokenizer of Stage II
+    if (TOKENIZER_PN_F16X3 and groups is None and training and not torch.is_grad_enabled()
+            and not any(p.requires_grad for p in enc.parameters())):
+        x3, keep = _pointnet_f16_planes(enc, bs * g * n)
     out = PointnetFn.apply(point_groups.reshape(bs * g * n, 3), w2(c1), c1.bias, bn1.weight, bn1.bias, w2(c2), c2.bias, w2(c3), c3.bias,
                            bn2.weight, bn2.bias, w2(c4), c4.bias,
-                           (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var), dims, training, groups)
+                           (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var), dims, training, groups, x3)
+    del keep
     return out.reshape(bs, g, dims.C)
 
 

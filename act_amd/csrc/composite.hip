@@ -778,8 +778,22 @@ int act_pointnet_fwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params
     return act_pointnet_fwd_groups_f32(d, w, x, training, keep_for_backward, saved, out, nullptr, 0, ws, wsb, stream);
 }
 
+static int pointnet_fwd(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const act_pointnet_f16x3_t* x3, const float* x, int training,
+                        int keep_for_backward, float* saved, float* out, const int32_t* groups, int n_groups, float* ws, size_t wsb, act_stream_t stream);
 int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const float* x, int training, int keep_for_backward,
                                 float* saved, float* out, const int32_t* groups, int n_groups, float* ws, size_t wsb, act_stream_t stream) {
+    return pointnet_fwd(d, w, nullptr, x, training, keep_for_backward, saved, out, groups, n_groups, ws, wsb, stream);
+}
+// same launch sequence with the last product (R x C x 512, the frozen c4_w, group max as epilogue) on the split-f16 kernel: relu(bn2(h3)) is formed, scaled by
+// x3->a_scale and split while that kernel stages h3.  Everything up to the BatchNorm-2 affine is the f32 entry's, bit for bit; an unusable x3, a call that keeps
+// for a backward or lists groups, the plain schedule or a shape the kernel does not take runs the f32 product and equals act_pointnet_fwd_groups_f32 bit for bit.
+int act_pointnet_fwd_groups_f16x3_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const act_pointnet_f16x3_t* x3, const float* x,
+                                      int training, int keep_for_backward, float* saved, float* out, const int32_t* groups, int n_groups, float* ws,
+                                      size_t wsb, act_stream_t stream) {
+    return pointnet_fwd(d, w, x3, x, training, keep_for_backward, saved, out, groups, n_groups, ws, wsb, stream);
+}
+static int pointnet_fwd(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const act_pointnet_f16x3_t* x3, const float* x, int training,
+                        int keep_for_backward, float* saved, float* out, const int32_t* groups, int n_groups, float* ws, size_t wsb, act_stream_t stream) {
     if (!w || !x || !saved || !out) return ACT_E_NULLPTR;
     if (bad_pn(d)) return ACT_E_BADARG;
     if (groups && (n_groups <= 0 || ((long long)n_groups * d->n) % 128)) return ACT_E_BADARG;
@@ -844,6 +858,14 @@ int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet
     } else {
         CK(gemm_nt(R, 512, 256, sv.h2, 256, w->c3_w + 256, 512, sv.h3, 512, e, ws, wsb, s));
         RUN(act_bn_eval_affine_f32(w->bn2_w, w->bn2_b, w->bn2_mean, w->bn2_var, d->eps2, 512, scale2, shift2, s));
+    }
+    if (x3 && x3->c4_planes && x3->c4_inv_scale && x3->a_scale > 0.f && !keep_for_backward && !groups && C % 128 == 0 &&
+        act_sgemm_nt_f16x3_gmax_supported(R, C, 512, n)) {
+        // the same product on the split-f16 kernel (frozen c4_w as planes).  The f32 shape is still recorded while shapes are collected: a call that falls
+        // back (below) finds its configuration tuned
+        if (collecting(1, 1, R, C, 512)) return 0;
+        return act_sgemm_nt_f16x3_gmax_f32(R, C, 512, sv.h3, 512, scale2, shift2, nullptr, nullptr, x3->a_scale, x3->c4_planes,
+                                           x3->c4_planes + (size_t)C * 512, x3->c4_inv_scale, w->c4_b, n, out, C, 0, s);
     }
     {   // conv 512->C on relu(bn2(h3)) applied on load; only the max over the group leaves the kernel
         act_gemm_fx_t fx{}; fx.a_scale = scale2; fx.a_shift = shift2; fx.gmax = out; fx.garg = keep_for_backward ? sv.arg2 : nullptr; fx.group = n; fx.store_c = 0;

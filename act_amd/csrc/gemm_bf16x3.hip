@@ -31,6 +31,11 @@
 // CU, each 1.5 tiles' worth: proj 67.6 -> 56.2 us, fc2 160.0 -> 132.0 us per launch inside the step.  act_sgemm_nt_f16x3_pick_tile (below) picks by shape alone.
 // The order of accumulation of an output element does not depend on the tile (K tiles in sequence, the three products in the same order, the same epilogue):
 // every form gives the same bits (tests/test_gpu_f16x3_tiles.py).
+//
+// THE GROUP-MAX PRODUCT (notebook/pn_f16x3.md): the last conv of the frozen tokenizer's mini-PointNet, out[g] = max over the rows of group g of
+// relu(h3 * sc + sh) . W^T + b, is the F16 form with two more template flags: A32 -- A arrives as fp32 and is activated (BatchNorm-2 affine + ReLU, the activation
+// scale folded in) and split while it is staged, the planes never exist in memory -- and GMAX -- the epilogue reduces over each group of 32 or 64 rows inside the
+// wave's 64-row block and stores only that.  act_sgemm_nt_f16x3_gmax_f32; 254 VGPRs on 128 x 128, 196 on 128 x 192, no scratch.  The other instances are unchanged.
 #include "gemm_common.h"
 #include "split_planes.h"
 #include <stdlib.h>
@@ -41,15 +46,30 @@ typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
 
+// relu(a * sc + sh), one fma per element: the A-side affine map of the group-max product, shared by its on-load form and the pass below
+__device__ __forceinline__ float4 x3_affine_relu4(const float4& a, const float4& sc, const float4& sh) {
+    return make_float4(fmaxf(__builtin_fmaf(a.x, sc.x, sh.x), 0.f), fmaxf(__builtin_fmaf(a.y, sc.y, sh.y), 0.f),
+                       fmaxf(__builtin_fmaf(a.z, sc.z, sh.z), 0.f), fmaxf(__builtin_fmaf(a.w, sc.w, sh.w), 0.f));
+}
+__device__ __forceinline__ float4 x3_scale4(const float4& a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
+
 // fp32 [R][K] (row stride ldx) -> two planes [R][K] (split_planes.h), four elements per thread (K % 4 == 0): (hi, lo) bf16 planes of x, or (F16) the (h1, h2)
 // f16 planes of x * scale * row_scale[row]; both scales are powers of two chosen by the caller and are not read in the bf16 form
-template <bool F16>
+// AFF (F16 only): the planes of relu(x * col_scale[k] + col_shift[k]) * scale instead -- the power of two folded into the affine map first, one fma per element,
+// exactly what the product's on-load form computes, so the two forms give the same planes bit for bit
+template <bool F16, bool AFF = false>
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, float scale,
-                                                           const float* __restrict__ row_scale, unsigned short* __restrict__ p1, unsigned short* __restrict__ p2) {
+                                                           const float* __restrict__ row_scale, unsigned short* __restrict__ p1, unsigned short* __restrict__ p2,
+                                                           const float* __restrict__ col_scale = nullptr, const float* __restrict__ col_shift = nullptr) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / K4; const int c4 = (int)(i - row * K4);
         const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-        store_planes4<F16>(p1, p2, (size_t)i, v, F16 && row_scale ? scale * row_scale[row] : scale);
+        if constexpr (AFF) {
+            const float4 sc = x3_scale4(*reinterpret_cast<const float4*>(col_scale + c4 * 4), scale), sh = x3_scale4(*reinterpret_cast<const float4*>(col_shift + c4 * 4), scale);
+            store_planes4<F16>(p1, p2, (size_t)i, x3_affine_relu4(v, sc, sh), 1.0f);
+        } else {
+            store_planes4<F16>(p1, p2, (size_t)i, v, F16 && row_scale ? scale * row_scale[row] : scale);
+        }
     }
 }
 
@@ -63,7 +83,28 @@ struct X3Params {
     int M, N, K;
     act_gemm_epilogue_t epi;
     const float* b_inv; float a_inv, o_scale;  // F16 form: 1 / s_B[n], 1 / s_A, and the scale the planes-out are split at (the next product's s_A)
+    // A32 form: A arrives as fp32 [M][K] (row stride lda) and its planes are those of relu(A * a_sc[k] + a_sh[k]) * a_fold, made while the tile is staged
+    const float *A32, *a_sc, *a_sh; int lda; float a_fold;
+    int group;                                 // GMAX form: rows per group (32 or 64); C = out [M / group][N] (row stride ldc), the max over each group's rows
 };
+
+// A32 staging: eight consecutive k of one row as two fp32 vectors -> affine + ReLU (sc / sh: this thread's eight (scale, shift) pairs, the activation scale
+// folded in) -> split_f16x2 (split_planes.h) -> the 16 bytes of each plane that the planes-in form loads from memory
+__device__ __forceinline__ void x3_affine_split8(const u32x4v& a0, const u32x4v& a1, const float* sc, const float* sh, u32x4v& h1, u32x4v& h2) {
+    // one half (four k) at a time, the halves kept apart in the schedule: the 128 x 128 form has 30 registers to spare
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const float4 c = *reinterpret_cast<const float4*>(sc + half * (LROW / 2)), s = *reinterpret_cast<const float4*>(sh + half * (LROW / 2));
+        const float4 v = x3_affine_relu4(__builtin_bit_cast(float4, half ? a1 : a0), c, s);
+        const float e[4] = {v.x, v.y, v.z, v.w};
+        unsigned h[4], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) split_f16x2(e[j], h[j], l[j]);
+        h1[2 * half] = h[0] | (h[1] << 16); h1[2 * half + 1] = h[2] | (h[3] << 16);
+        h2[2 * half] = l[0] | (l[1] << 16); h2[2 * half + 1] = l[2] | (l[3] << 16);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 
 // one MFMA of two 16-bit fragments (8 per lane), bf16 or f16 by the plane format
 template <bool F16>
@@ -77,8 +118,13 @@ constexpr int x3_wgs_per_cu(int waves) { return waves <= 4 ? 2 : 1; }
 
 // F16: f16 planes, the two cross terms in a second accumulator set (acc[1]), scales divided out in the epilogue; otherwise bf16 planes and one accumulator set
 // WGM x WGN waves, each on a (BM / WGM) x (BN / WGN) block of the tile.  (__launch_bounds__' second argument counts waves per SIMD.)
-template <int BM, int BN, int WGM, int WGN, int ACT, bool PLANES, bool F16>
+// A32 (F16 only): A is fp32 and is activated and split while it is staged (x3_affine_split8); its K (scale, shift) pairs sit in the pad columns of the two A
+// plane images of LDS stage 0 -- four floats behind each of the BM rows, which no staging store and no fragment read touches -- so K <= 4 BM and the form costs
+// no LDS.  GMAX: the epilogue keeps the max over every `group` rows and stores that instead of C.  Both default to off: the other instances are unchanged.
+template <int BM, int BN, int WGM, int WGN, int ACT, bool PLANES, bool F16, bool A32 = false, bool GMAX = false>
 __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WGN / 4) void sgemm_nt_bf16x3_kernel(const X3Params p) {
+    static_assert(F16 || !(A32 || GMAX), "the on-load split and the group max belong to the f16 form");
+    static_assert(!GMAX || (BM / WGM == 64 && !PLANES), "a group of 32 or 64 rows lies inside one wave's 64-row block");
     constexpr int NT = 64 * WGM * WGN, RP = NT / 4;           // threads; rows of a plane tile that one staging pass covers
     constexpr int WM = BM / WGM, WN = BN / WGN;               // the wave's block
     constexpr int TM = WM / 16, TN = WN / 16;                 // 16 x 16 tiles per wave
@@ -112,8 +158,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
             for (int j = 0; j < TN; ++j) acc[x][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int srow = tid >> 2, sch = tid & 3;                 // staging: (row, 16-byte chunk) of a [rows][32 bf16] plane tile
-    const size_t goa = (size_t)(m0 + srow) * K + sch * 8, gob = (size_t)(n0 + srow) * K + sch * 8;
-    const unsigned short* gA[2] = {p.Ah + goa, p.Al + goa};
+    const int lda = A32 ? p.lda : K;                          // A32: this thread's eight k of a row are two 16-byte fp32 loads (set 0: k .. k+3, set 1: k+4 .. k+7)
+    const size_t goa = (size_t)(m0 + srow) * lda + sch * 8, gob = (size_t)(n0 + srow) * K + sch * 8;
+    const float* gA32[2] = {A32 ? p.A32 + goa : nullptr, A32 ? p.A32 + goa + 4 : nullptr};
+    const unsigned short* gA[2] = {A32 ? nullptr : p.Ah + goa, A32 ? nullptr : p.Al + goa};
     const unsigned short* gB[2] = {p.Bh + gob, p.Bl + gob};
     u32x4v ra0[2][NA], rb0[2][NB], ra1[2][NA], rb1[2][NB];      // two staging sets (native vectors: arrays of HIP's uint4 struct would sit in scratch)
     const int s_off = srow * LROW + sch * 8;
@@ -122,19 +170,36 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
     // staging pass i covers rows i * RP .. of the plane tile.  A last PARTIAL pass (BM or BN no multiple of RP) loads unconditionally from its row clamped into
     // the tile (ta / tb: that row's offset from this thread's first row) and stores to the LDS only where the row exists -- a test that is uniform per wave
     // (a wave stages 16 consecutive rows; BM, BN and RP are multiples of 16), so there is still no divergent code around the staging registers
-    const long long ta = (long long)(min(srow + RP * (NA - 1), BM - 1) - srow) * K, tb = (long long)(min(srow + RP * (NB - 1), BN - 1) - srow) * K;
+    const long long ta = (long long)(min(srow + RP * (NA - 1), BM - 1) - srow) * lda, tb = (long long)(min(srow + RP * (NB - 1), BN - 1) - srow) * K;
+    // A32: (scale, shift) of k at float (k / 4) * (LROW / 2) + 16 + k % 4 of the first / second A plane image of stage 0 (the pad columns)
+    const float* Lf = reinterpret_cast<const float*>(L);
+    const int sx_off = sch * 2 * (LROW / 2) + 16;              // + T * 8 * (LROW / 2): this thread's eight k of K tile T
 #define X3_WHOLE(I, ROWS) (RP * ((I) + 1) <= (ROWS))
 #define X3_LOAD(RA, RB, T)                                                                                                             \
     _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                                                 \
         _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
-            RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * K : ta) + (T) * BK);      \
+            if constexpr (A32)                                                                                                         \
+                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA32[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * BK); \
+            else                                                                                                                       \
+                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * K : ta) + (T) * BK);  \
         _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
             RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (X3_WHOLE(i_, BN) ? (long long)(RP * i_) * K : tb) + (T) * BK);      \
     }
-#define X3_STORE(RA, RB, STG)                                                                                                          \
+    /* T: the K tile the registers hold (read by the A32 form only) */
+#define X3_STORE(RA, RB, STG, T)                                                                                                       \
+    if constexpr (A32) {                                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                                             \
+        _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
+            if (X3_WHOLE(i_, BM) || srow + RP * i_ < BM) {                                                                             \
+                u32x4v h1_, h2_;                                                                                                       \
+                x3_affine_split8(RA[0][i_], RA[1][i_], Lf + sx_off + (T) * 8 * (LROW / 2), Lf + PA / 2 + sx_off + (T) * 8 * (LROW / 2), h1_, h2_); \
+                *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + s_off + RP * i_ * LROW]) = h1_;                                          \
+                *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + PA + s_off + RP * i_ * LROW]) = h2_;                                     \
+            }                                                                                                                          \
+    }                                                                                                                                  \
     _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                                                 \
         _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
-            if (X3_WHOLE(i_, BM) || srow + RP * i_ < BM)                                                                               \
+            if (!A32 && (X3_WHOLE(i_, BM) || srow + RP * i_ < BM))                                                                     \
                 *reinterpret_cast<u32x4v*>(&L[(STG) * STAGE + s_ * PA + s_off + RP * i_ * LROW]) = RA[s_][i_];                         \
         _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
             if (X3_WHOLE(i_, BN) || srow + RP * i_ < BN)                                                                               \
@@ -159,16 +224,24 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
     // loads / stores are unconditional: past the end they re-read the last K tile and fill a stage nobody reads (no divergent code around the staging registers)
     X3_LOAD(ra0, rb0, 0)
     X3_LOAD(ra1, rb1, min(1, last))
-    X3_STORE(ra0, rb0, 0)
+    if constexpr (A32) {                                          // the K (scale, shift) pairs, times the activation scale (a power of two: exact), into the pads
+        float* Lw = reinterpret_cast<float*>(L);
+        for (int q = tid; q < K / 4; q += NT) {
+            *reinterpret_cast<float4*>(&Lw[q * (LROW / 2) + 16]) = x3_scale4(*reinterpret_cast<const float4*>(p.a_sc + 4 * q), p.a_fold);
+            *reinterpret_cast<float4*>(&Lw[PA / 2 + q * (LROW / 2) + 16]) = x3_scale4(*reinterpret_cast<const float4*>(p.a_sh + 4 * q), p.a_fold);
+        }
+        __syncthreads();
+    }
+    X3_STORE(ra0, rb0, 0, 0)
     __syncthreads();
     for (int t = 0; t < ntiles; t += 2) {                         // ntiles is even (K % 64 == 0, checked by the launcher)
         X3_LOAD(ra0, rb0, min(t + 2, last))                       // LDS stage 0 = tile t; set 1 = tile t+1 (in flight); request tile t+2
         X3_COMPUTE(0)
-        X3_STORE(ra1, rb1, 1)
+        X3_STORE(ra1, rb1, 1, min(t + 1, last))
         __syncthreads();
         X3_LOAD(ra1, rb1, min(t + 3, last))                       // LDS stage 1 = tile t+1; set 0 = tile t+2 (in flight); request tile t+3
         X3_COMPUTE(1)
-        X3_STORE(ra0, rb0, 0)
+        X3_STORE(ra0, rb0, 0, min(t + 2, last))
         __syncthreads();
     }
 #undef X3_WHOLE
@@ -180,24 +253,60 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
     // F16: v = (acc0 + 2^-11 acc1) / s_B[n] / s_A first -- two multiplications by powers of two, exact -- then the same epilogue
     const bool vec = (((uintptr_t)p.C | (uintptr_t)p.epi.bias | (uintptr_t)p.epi.res | (uintptr_t)p.epi.aux) & 15) == 0 &&
                      ((p.ldc | (p.epi.res ? p.epi.ldr : 0) | (p.epi.aux ? p.epi.ldaux : 0)) & 3) == 0;
+    auto value = [&](int i, int j, int row, int col) -> float4 {      // the finished 1 x 4 piece of block (i, j)
+        float4 v = make_float4(acc[0][i][j][0], acc[0][i][j][1], acc[0][i][j][2], acc[0][i][j][3]);
+        if constexpr (F16) {
+            const float4 bi = *reinterpret_cast<const float4*>(p.b_inv + col);           // 16-byte aligned (launcher), col % 4 == 0
+            constexpr float W = 1.0f / 2048.0f;
+            v.x = __builtin_fmaf(acc[1][i][j][0], W, v.x) * bi.x * p.a_inv; v.y = __builtin_fmaf(acc[1][i][j][1], W, v.y) * bi.y * p.a_inv;
+            v.z = __builtin_fmaf(acc[1][i][j][2], W, v.z) * bi.z * p.a_inv; v.w = __builtin_fmaf(acc[1][i][j][3], W, v.w) * bi.w * p.a_inv;
+        }
+        if (vec) v = epilogue_apply4_act<ACT>(p.epi, v, row, col);
+        else {
+            v.x = epilogue_apply<ACT>(p.epi, v.x, row, col); v.y = epilogue_apply<ACT>(p.epi, v.y, row, col + 1);
+            v.z = epilogue_apply<ACT>(p.epi, v.z, row, col + 2); v.w = epilogue_apply<ACT>(p.epi, v.w, row, col + 3);
+        }
+        return v;
+    };
+    if constexpr (GMAX) {
+        // max over every `group` (32 or 64) consecutive rows instead of C: the wave's 64 rows are two half blocks (i = 0, 1 | 2, 3), each reduced over i in
+        // the lane and over the 16 lanes that share g; lane r == 0 stores one float4 per group.  From -inf: a biased output may be all negative.  (max is
+        // associative and commutative: the order of the reduction, hence the tile form, does not change a bit.)
+        constexpr float NINF = -__builtin_huge_valf();
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int col = n0 + wn * WN + j * 16 + g * 4;
+            float4 m[2] = {make_float4(NINF, NINF, NINF, NINF), make_float4(NINF, NINF, NINF, NINF)};
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const float4 v = value(i, j, m0 + wm * WM + i * 16 + r, col);
+                float4& d = m[i / (TM / 2)];
+                d.x = fmaxf(d.x, v.x); d.y = fmaxf(d.y, v.y); d.z = fmaxf(d.z, v.z); d.w = fmaxf(d.w, v.w);
+            }
+            if (p.group == 64) { m[0].x = fmaxf(m[0].x, m[1].x); m[0].y = fmaxf(m[0].y, m[1].y); m[0].z = fmaxf(m[0].z, m[1].z); m[0].w = fmaxf(m[0].w, m[1].w); }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1 && p.group == 64) break;
+#pragma unroll
+                for (int off = 1; off < 16; off <<= 1) {
+                    m[h].x = fmaxf(m[h].x, __shfl_xor(m[h].x, off)); m[h].y = fmaxf(m[h].y, __shfl_xor(m[h].y, off));
+                    m[h].z = fmaxf(m[h].z, __shfl_xor(m[h].z, off)); m[h].w = fmaxf(m[h].w, __shfl_xor(m[h].w, off));
+                }
+                if (r == 0) {
+                    float* cp = p.C + (size_t)((m0 + wm * WM + h * 32) / p.group) * p.ldc + col;
+                    if (vec) *reinterpret_cast<float4*>(cp) = m[h]; else { cp[0] = m[h].x; cp[1] = m[h].y; cp[2] = m[h].z; cp[3] = m[h].w; }
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int row = m0 + wm * WM + i * 16 + r;
             const int col = n0 + wn * WN + j * 16 + g * 4;
-            float4 v = make_float4(acc[0][i][j][0], acc[0][i][j][1], acc[0][i][j][2], acc[0][i][j][3]);
-            if constexpr (F16) {
-                const float4 bi = *reinterpret_cast<const float4*>(p.b_inv + col);           // 16-byte aligned (launcher), col % 4 == 0
-                constexpr float W = 1.0f / 2048.0f;
-                v.x = __builtin_fmaf(acc[1][i][j][0], W, v.x) * bi.x * p.a_inv; v.y = __builtin_fmaf(acc[1][i][j][1], W, v.y) * bi.y * p.a_inv;
-                v.z = __builtin_fmaf(acc[1][i][j][2], W, v.z) * bi.z * p.a_inv; v.w = __builtin_fmaf(acc[1][i][j][3], W, v.w) * bi.w * p.a_inv;
-            }
-            if (vec) v = epilogue_apply4_act<ACT>(p.epi, v, row, col);
-            else {
-                v.x = epilogue_apply<ACT>(p.epi, v.x, row, col); v.y = epilogue_apply<ACT>(p.epi, v.y, row, col + 1);
-                v.z = epilogue_apply<ACT>(p.epi, v.z, row, col + 2); v.w = epilogue_apply<ACT>(p.epi, v.w, row, col + 3);
-            }
+            const float4 v = value(i, j, row, col);
             if (!PLANES || p.C) {
                 float* cp = p.C + (size_t)row * p.ldc + col;
                 if (vec) *reinterpret_cast<float4*>(cp) = v; else { cp[0] = v.x; cp[1] = v.y; cp[2] = v.z; cp[3] = v.w; }
@@ -225,6 +334,16 @@ int launch_x3(const X3Params& p, hipStream_t s) {
             break;
         default: return ACT_E_BADARG;
     }
+    ACT_LAUNCH_CHECK();
+    return 0;
+}
+
+// the group-max product (F16, bias only): A as planes, or (a32) as fp32 activated and split on load
+template <int BM, int BN, int WGM, int WGN>
+int launch_x3_gmax(const X3Params& p, bool a32, hipStream_t s) {
+    const dim3 grid((p.M / BM) * (p.N / BN)), block(64 * WGM * WGN);
+    if (a32) hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_NONE, false, true, true, true>), grid, block, 0, s, p);
+    else     hipLaunchKernelGGL((sgemm_nt_bf16x3_kernel<BM, BN, WGM, WGN, ACT_EPI_NONE, false, true, false, true>), grid, block, 0, s, p);
     ACT_LAUNCH_CHECK();
     return 0;
 }
@@ -305,6 +424,43 @@ int multiply_planes(int M, int N, int K, const uint16_t* a1, const uint16_t* a2,
     else return launch_x3<128, 128, 2, 2, false>(p, s);
 }
 }  // namespace
+
+// ---- the group-max product of the frozen tokenizer's mini-PointNet (composite.hip, act_pointnet_fwd_x3_f32) -------------------------------------------------
+extern "C" int act_split_f16x2_affine_relu_f32(const float* x, int R, int K, int ldx, const float* col_scale, const float* col_shift, float scale, uint16_t* h1,
+                                               uint16_t* h2, act_stream_t stream) {
+    if (!x || !col_scale || !col_shift || !h1 || !h2) return ACT_E_NULLPTR;
+    if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || !(scale > 0.f)) return ACT_E_BADARG;
+    if (((uintptr_t)x | (uintptr_t)h1 | (uintptr_t)h2 | (uintptr_t)col_scale | (uintptr_t)col_shift) & 15) return ACT_E_BADARG;
+    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
+    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL((split_planes_kernel<true, true>), dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, nullptr, h1, h2, col_scale, col_shift);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+extern "C" int act_sgemm_nt_f16x3_gmax_supported(int M, int N, int K, int group) {
+    return act_sgemm_nt_f16x3_supported(M, N, K) && K <= 512 && (group == 32 || group == 64);
+}
+// Tile of the group-max product by shape alone: the rule of the storing product (notebook/pn_f16x3.md has both tiles measured at the tokenizer's shape)
+extern "C" int act_sgemm_nt_f16x3_gmax_pick_tile(int M, int N, int K, int cus) { return act_sgemm_nt_f16x3_pick_tile(M, N, K, cus); }
+extern "C" int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift,
+                                           const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2,
+                                           const float* b_inv_scale, const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream) {
+    const bool a32 = A != nullptr;
+    if (!b_h1 || !b_h2 || !b_inv_scale || !out || (a32 ? (!a_col_scale || !a_col_shift) : (!a_h1 || !a_h2))) return ACT_E_NULLPTR;
+    if (!act_sgemm_nt_f16x3_gmax_supported(M, N, K, group) || ldo < N || !(a_scale > 0.f) || (a32 && (lda < K || (lda & 3)))) return ACT_E_BADARG;
+    if (((uintptr_t)A | (uintptr_t)a_col_scale | (uintptr_t)a_col_shift | (uintptr_t)a_h1 | (uintptr_t)a_h2 | (uintptr_t)b_h1 | (uintptr_t)b_h2 |
+         (uintptr_t)b_inv_scale) & 15) return ACT_E_BADARG;
+    if (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;
+    if (tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_gmax_pick_tile(M, N, K, x3_cu_count());
+    X3Params p{};
+    p.A32 = A; p.lda = lda; p.a_sc = a_col_scale; p.a_sh = a_col_shift; p.a_fold = a_scale; p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2;
+    p.C = out; p.ldc = ldo; p.M = M; p.N = N; p.K = K; p.group = group; p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale;
+    p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; p.epi.bias = bias;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)(M / group) * N));
+    return tile == 192 ? launch_x3_gmax<128, 192, 2, 4>(p, a32, s) : launch_x3_gmax<128, 128, 2, 2>(p, a32, s);
+}
 
 extern "C" int act_sgemm_nt_bf16x3_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
                                        float* C, int ldc, const act_gemm_epilogue_t* epilogue, act_stream_t stream) {

@@ -258,6 +258,41 @@ def gemm_nt_f16x3(a_planes, a_scale, b_planes, b_inv_scale, bias=None, act=EPI_N
     return out
 
 
+def split_f16x2_affine_relu(x, col_scale, col_shift, scale):
+    """fp32 [R, K] -> f16 planes [2, R, K] of relu(x * col_scale[k] + col_shift[k]) * scale, the power of two folded into the affine map first: the pass form of
+    what gemm_nt_f16x3_gmax does on load (test helper and speed baseline; the product path splits on load)"""
+    x = _f32rows(x, "x")
+    R, Kd = x.shape
+    out = torch.empty(2, R, Kd, dtype=torch.float16, device=x.device)
+    check(lib.act_split_f16x2_affine_relu_f32(_C.ptr_rows(x), R, Kd, x.stride(0), ptr(_f32c(col_scale)), ptr(_f32c(col_shift)), float(scale), ptr(out[0]),
+                                              ptr(out[1]), stream()), "act_split_f16x2_affine_relu_f32")
+    return out
+
+
+def gemm_nt_f16x3_gmax(a, a_scale, b_planes, b_inv_scale, group, bias=None, col_scale=None, col_shift=None, tile=0):
+    """out[M / group, N] = max over every ``group`` (32 | 64) consecutive rows of ((a' . b^T) / a_scale / b_scale[n] + bias): the last product of the frozen
+    tokenizer's mini-PointNet on the split-f16 kernel, nothing but the group max stored.  ``a`` fp32 [M, K] with col_scale / col_shift: a' = the planes of
+    relu(a * col_scale + col_shift) * a_scale, formed while the kernel stages a; ``a`` f16 planes [2, M, K]: a' = those planes.  K <= 512."""
+    planes = a.dtype == torch.float16
+    b_planes, b_inv_scale = b_planes.contiguous(), _f32c(b_inv_scale)
+    N, Kd = b_planes.shape[1], b_planes.shape[2]
+    if planes:
+        a = a.contiguous()
+        M = a.shape[1]
+        args = (None, 0, None, None, ptr(a[0]), ptr(a[1]))
+    else:
+        a = _f32rows(a, "a")
+        M = a.shape[0]
+        args = (_C.ptr_rows(a), a.stride(0), ptr(_f32c(col_scale)), ptr(_f32c(col_shift)), None, None)
+    if a.shape[-1] != Kd or b_inv_scale.numel() != N or M % int(group):
+        raise _C.ActHipError("gemm_nt_f16x3_gmax: shapes do not match")
+    out = torch.empty(M // int(group), N, dtype=torch.float32, device=a.device)
+    check(lib.act_sgemm_nt_f16x3_gmax_f32(M, N, Kd, *args, float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]), ptr(b_inv_scale),
+                                          ptr(_f32c(bias)) if bias is not None else None, int(group), ptr(out), N, int(tile), stream()),
+          "act_sgemm_nt_f16x3_gmax_f32")
+    return out
+
+
 # ---- GEMM autotuner: the step has ~40 distinct (layout, M, N, K) shapes; each is timed once (tile shape x split-K) on first
 # use -- i.e. during the warm-up steps -- and the winner is cached, so steady-state steps never synchronise.
 _GEMM_CACHE = {}

@@ -446,6 +446,18 @@ int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const flo
                                      float eps, act_stream_t stream);
 int act_attention_fwd_prefix_f16_planes_f32(const float* kv0, int S0, const float* qkv1, int Sq, float* out, uint16_t* out_h1, uint16_t* out_h2,
                                             float plane_scale, float* lse, int B, int H, int head_dim, float scale, act_stream_t stream);
+/* The group-max product of the frozen tokenizer's mini-PointNet on this kernel:  out[g, :] = max over the `group` (32 or 64) rows of group g of
+ * (a . B^T + bias), a [M, K] = relu(A * a_col_scale[k] + a_col_shift[k]) -- nothing else is stored.  A != NULL: a is formed, scaled by a_scale and split
+ * while the kernel stages A (fp32, row stride lda; a_h1 / a_h2 unused); A == NULL: a_h1 / a_h2 are the planes of a * a_scale, as the pass
+ * act_split_f16x2_affine_relu_f32 writes them.  The two forms give the same bits, as do the two tiles (tile: 0 = act_sgemm_nt_f16x3_gmax_pick_tile, 128, 192).
+ * ..._supported: the shapes of act_sgemm_nt_f16x3_supported with K <= 512 and group in {32, 64}.  bias nullable; out [M / group, N], row stride ldo. */
+int act_split_f16x2_affine_relu_f32(const float* x, int R, int K, int ldx, const float* col_scale, const float* col_shift, float scale, uint16_t* h1,
+                                    uint16_t* h2, act_stream_t stream);
+int act_sgemm_nt_f16x3_gmax_supported(int M, int N, int K, int group);
+int act_sgemm_nt_f16x3_gmax_pick_tile(int M, int N, int K, int cus);
+int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift, const uint16_t* a_h1,
+                                const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2, const float* b_inv_scale,
+                                const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream);
 
 /* ---- GEMM launch-configuration table (host side) ------------------------------------------------------------------------
  * act_sgemm_f32 (no explicit configuration) first consults this table keyed by (a_kmajor, b_kmajor, M, N, K), then its built-in
@@ -642,6 +654,21 @@ int act_pointnet_fwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params
 int act_pointnet_fwd_groups_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const float* x, int training, int keep_for_backward,
                                 float* saved, float* out, const int32_t* groups, int n_groups, float* workspace, size_t workspace_bytes,
                                 act_stream_t stream);
+/* The same entry for a FROZEN encoder under no-grad (the Stage-II tokenizer): the last product -- R = BG * n rows, C columns, K = 512, the group max as its
+ * epilogue -- on the split-f16 kernel (act_sgemm_nt_f16x3_gmax_f32, A activated and split on load).  c4_planes = the h1 plane of c4_w split with one power of
+ * two per output row (act_split_f16x2_f32; the h2 plane C * 512 elements behind it), c4_inv_scale [C] the inverse row scales, a_scale a power of two with
+ * a_scale * max|relu(bn2(h3))| <= 2^15 (training-mode statistics bound that by sqrt(R) max|gamma| + max|beta|; the caller derives it).  Everything up to and
+ * including h3 and the BatchNorm-2 affine is act_pointnet_fwd_groups_f32's, bit for bit.  The split path is taken only with a usable x3 (not NULL, no NULL
+ * pointer in it, a_scale > 0), keep_for_backward == 0, groups == NULL, the fused schedule, and R % 128 == 0, C % 128 == 0; every other call runs the f32
+ * product and equals act_pointnet_fwd_groups_f32 bit for bit. */
+typedef struct {
+    const uint16_t* c4_planes;
+    const float* c4_inv_scale;
+    float a_scale;
+} act_pointnet_f16x3_t;
+int act_pointnet_fwd_groups_f16x3_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const act_pointnet_f16x3_t* x3, const float* x,
+                                      int training, int keep_for_backward, float* saved, float* out, const int32_t* groups, int n_groups,
+                                      float* workspace, size_t workspace_bytes, act_stream_t stream);
 size_t act_pointnet_bwd_scratch_floats(const act_pointnet_dims_t* d);
 int act_pointnet_bwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const float* x, const float* saved,
                          const float* dout, const act_pointnet_grads_t* grads, float* scratch, float* workspace,
