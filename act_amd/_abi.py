@@ -200,6 +200,7 @@ _TABLE = {
     "act_sgemm_nt_f16x3_planes_tile_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
     "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
     "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
+    "act_prompt_layernorm_fwd_f16_planes_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp],
     "act_split_f16x2_affine_relu_f32": [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp],
     "act_sgemm_nt_f16x3_gmax_supported": [_i, _i, _i, _i],
     "act_sgemm_nt_f16x3_gmax_pick_tile": [_i, _i, _i, _i],
@@ -230,6 +231,8 @@ _TABLE = {
     "act_prompt_kv_sparse": [_i],
     "act_prompt_kv_workspace": (_sz, [_i, _i, _i, _i]),
     "act_prompt_kv_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp],
+    "act_prompt_kv_f16x3": [_i],
+    "act_prompt_kv_fwd_f16x3_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _i, _vp],
     "act_prefix_block_bwd_scratch_floats": (_sz, [_dims, _i]),
     "act_prefix_block_bwd_f32": [_dims, _i, _blk, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_prefix_vit_scratch_floats": (_sz, [_P(PrefixVit)]),

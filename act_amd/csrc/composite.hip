@@ -181,8 +181,8 @@ int x3_attention(PlaneFmt fmt, const float* kvp, int P, const float* qkvx, int G
     return act_attention_fwd_prefix_planes_f32(kvp, P, qkvx, G, att, dst, dst2, lse, B, H, hd, attn_scale(hd), s);
 }
 
-// The planes of one frozen block: its four Linears and `kv`, the K,V rows of the qkv Linear applied to the prompt rows (bf16 opt-in only: the default teacher's
-// prompt keys / values stay on the f32 path), + the scratch its activations are split into.
+// The planes of one frozen block: its four Linears and `kv`, the K,V rows of the qkv Linear applied to the prompt rows (the bf16 opt-in multiplies them inside
+// prefix_block_core, the f16 default through act_prompt_kv_fwd_f16x3_f32 ahead of it), + the scratch its activations are split into.
 // (n1p_is_planes: the caller's prompt LayerNorm already left the prompt rows as planes in the activation region)
 struct X3Block { X3Linear kv, qkv, proj, fc1, fc2; uint16_t* a_planes; size_t a_elems; bool n1p_is_planes; };
 // OPT-IN (act_prefix_vit_fwd_bf16x3_f32): w_planes[0..3] = the hi planes of qkv_w, proj_w, fc1_w, fc2_w, the lo plane behind each
@@ -202,6 +202,9 @@ inline bool x3_fits(const act_block_dims_t& d, int P, size_t a_elems) {
     const size_t TG = (size_t)d.B * d.S, TP = (size_t)d.B * P;
     return a_elems >= 2 * TG * d.hidden + 2 * (TG > TP ? TG : TP) * d.D;
 }
+// tile of the default teacher's prompt keys / values product (act_prompt_kv_fwd_f16x3_f32): 0 = the rule of act_sgemm_nt_f16x3_pick_tile; both tiles are measured
+// at (8192, 1536, 768) in notebook/prompt_kv_f16x3.md
+constexpr int kPromptKvTile = 0;
 
 // the launch sequence of one prefix block given the LayerNorm'd prompt rows n1p (shared by the inference stack and the
 // differentiable forward)
@@ -513,6 +516,30 @@ int act_prompt_kv_fwd_f32(const float* tok, const float* ppos, int B, int P, int
     return 0;
 }
 
+// ============================================================================================== prompt keys / values, dense on the split-f16 kernel
+// The default teacher's form wherever the kernel takes B P x N x D: the prompt LayerNorm leaves the rows as f16 planes at a_scale (the static scale of the
+// block's qkv Linear -- the bound sqrt(D) |gamma| + |beta| holds for any LayerNorm row), one planes product with the bias epilogue writes kv.  Two launches.
+static std::atomic<int> g_prompt_kv_f16x3{[] { const char* e = getenv("ACT_PROMPT_KV_F16X3"); return !(e && e[0] == '0') ? 1 : 0; }()};
+int act_prompt_kv_f16x3(int on) { return on < 0 ? g_prompt_kv_f16x3.load() : g_prompt_kv_f16x3.exchange(on ? 1 : 0); }
+int act_prompt_kv_fwd_f16x3_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, const float* w_inv,
+                                float a_scale, const float* bias, float* kv, uint16_t* planes, size_t planes_elems, int tile, act_stream_t stream) {
+    if (B <= 0 || P <= 0 || D <= 0 || N <= 0) return ACT_E_BADARG;
+    const size_t rows = (size_t)B * P;
+    if (!g_prompt_kv_f16x3.load() || !(a_scale > 0.f) || !w_h1 || !w_h2 || !w_inv || !planes || planes_elems < 2 * rows * (size_t)D ||
+        rows > (size_t)0x7fffffff || !act_sgemm_nt_f16x3_supported((int)rows, N, D))
+        return ACT_E_UNSUPPORTED;
+    if (!tok || !ppos || !gamma || !beta || !kv) return ACT_E_NULLPTR;
+    if (drop_p < 0.f || drop_p >= 1.f || (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) ||
+        (((uintptr_t)planes | (uintptr_t)w_h1 | (uintptr_t)w_h2 | (uintptr_t)w_inv) & 15))
+        return ACT_E_BADARG;                                            // (checked before the first launch: the product below would refuse the same)
+    uint16_t* p2 = planes + rows * D;                                   // (rows % 128 == 0: the second plane is 16-byte aligned with the first)
+    RUN(act_prompt_layernorm_fwd_f16_planes_f32(tok, ppos, B, P, D, drop_p, seed, seed_dev, gamma, beta, eps, planes, p2, a_scale, stream));
+    act_gemm_epilogue_t e = epi0(); e.bias = bias;
+    RUN(act_sgemm_nt_f16x3_planes_tile_f32((int)rows, N, D, planes, p2, a_scale, w_h1, w_h2, w_inv, kv, N, nullptr, nullptr, 0.f, &e, stream, tile));
+    return 0;
+}
+
 // OPT-IN: the same forward with the block's four (frozen) weights given as (hi, lo) bf16 planes: every product whose shape the split-bf16 kernel takes runs there
 // (w_planes[0..3] = hi planes of qkv_w, proj_w, fc1_w, fc2_w, lo plane behind each; a_planes as in act_vit_bf16x3_t).  The backward is unchanged (f32).
 int act_prefix_block_fwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const act_vit_bf16x3_t* x3, const float* x, const float* pos,
@@ -629,7 +656,8 @@ int act_prefix_vit_fwd_bf16x3_f32(const act_prefix_vit_t* m, const act_vit_bf16x
     return prefix_vit_fwd(m, x3, nullptr, tokens, center, out, scratch, ws, wsb, stream);
 }
 // DEFAULT teacher arithmetic (ACT_TEACHER_F16X3, on unless switched off): the four Linear products of every block on the split-f16 kernel wherever it takes the
-// shape and the range guard gave the Linear an activation scale; the prompts' keys / values stay on the sparse f32 path
+// shape and the range guard gave the Linear an activation scale; the prompts' keys / values as one dense product on the same kernel at the qkv Linear's scale
+// (ACT_PROMPT_KV_F16X3, act_prompt_kv_fwd_f16x3_f32), on the sparse f32 path where that entry declines
 int act_prefix_vit_fwd_f16x3_f32(const act_prefix_vit_t* m, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
                                  float* scratch, float* ws, size_t wsb, act_stream_t stream) {
     if (!h3 || !h3->w_planes || !h3->w_inv_scale || !h3->a_scale || !h3->a_planes) return ACT_E_NULLPTR;
@@ -667,6 +695,20 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
                 if (sa > 0.f && h3->w_planes[4 * i + j] && h3->w_inv_scale[4 * i + j])
                     *lin[j] = x3_linear_of(h3->w_planes[4 * i + j], elems[j], PlaneFmt::f16(sa), h3->w_inv_scale[4 * i + j]);
             }
+            if (hb.qkv.w1) hb.kv = X3Linear{hb.qkv.w1 + sD * sD, hb.qkv.w2 + sD * sD, hb.qkv.inv + sD, hb.qkv.a_fmt};   // rows D .. 3D of both plane images
+        }
+        if (h3 && !x3) {        // prompt keys / values, split-f16 default: LayerNorm to planes + one dense planes product, where the kernel takes the shape
+            uint16_t* tp = x3_fits(d, m->P, hb.a_elems) ? hb.a_planes + (size_t)2 * TG * m->hidden : nullptr;             // the activation region (x3_fits)
+            const int rc = act_prompt_kv_fwd_f16x3_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
+                                                       m->eps, hb.kv.w1, hb.kv.w2, hb.kv.inv, hb.kv.a_fmt.f16_scale, w.qkv_b ? w.qkv_b + D : nullptr, sv.kvp, tp,
+                                                       tp ? hb.a_elems - (size_t)2 * TG * m->hidden : 0, kPromptKvTile, stream);
+            if (rc == 0) {
+                (void)collecting(1, 1, m->B * m->P, 2 * D, D);          // the dense f32 product stays tuned: a fall-back can be switched to at run time
+                CK(prefix_block_core(d, m->P, w, cur, pos, nullptr, false, sv, nxt, ws, wsb, s, &hb, true));
+                float* t = cur; cur = nxt; nxt = t;
+                continue;
+            }
+            if (rc != ACT_E_UNSUPPORTED) return rc;                    // switched off / no scale / a shape it does not take: the sparse sequence below
         }
         if (!x3) {              // prompt keys / values: base product once, the dropped terms walked sparsely (the split-bf16 opt-in keeps its planes)
             const int rc = act_prompt_kv_fwd_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,

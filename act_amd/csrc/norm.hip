@@ -309,7 +309,8 @@ __global__ __launch_bounds__(256) void prompt_layernorm_fwd_kernel(const float* 
                                                                    float drop_p, uint64_t seed, const uint64_t* __restrict__ seed_dev,
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    float* __restrict__ y, int T, int D, float eps,
-                                                                   unsigned short* __restrict__ y_hi = nullptr, unsigned short* __restrict__ y_lo = nullptr) {
+                                                                   unsigned short* __restrict__ y_hi = nullptr, unsigned short* __restrict__ y_lo = nullptr,
+                                                                   PlaneFmt fmt = PlaneFmt::bf16()) {
     const DropoutKey key = dropout_key(drop_p, seed, seed_dev);
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -331,12 +332,12 @@ __global__ __launch_bounds__(256) void prompt_layernorm_fwd_kernel(const float* 
     }
     const float mean = ln_row_mean<LN_ROW_MAXV>(v, lane, nv, D);
     const float rstd = ln_row_rstd<LN_ROW_MAXV>(v, mean, lane, nv, D, eps);
-    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, nullptr, row, lane, nv);
+    ln_store_row(v, mean, rstd, gamma, beta, y, y_hi, y_lo, nullptr, row, lane, nv, fmt);
 }
 
-extern "C" int act_prompt_layernorm_fwd_planes_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
-                                                   const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, uint16_t* y_hi,
-                                                   uint16_t* y_lo, act_stream_t stream) {
+// the prompt rows as planes in the format `fmt` (y == NULL: planes only)
+static int prompt_layernorm_fwd_planes(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                       const float* gamma, const float* beta, float eps, uint16_t* y_hi, uint16_t* y_lo, PlaneFmt fmt, act_stream_t stream) {
     if (!tok || !ppos || !gamma || !beta || !y_hi || !y_lo) return ACT_E_NULLPTR;
     if (B < 0 || P <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LN_ROW_MAXV || drop_p < 0.f || drop_p >= 1.f || (((uintptr_t)y_hi | (uintptr_t)y_lo) & 7)) return ACT_E_BADARG;
     if (B == 0) return 0;
@@ -344,8 +345,19 @@ extern "C" int act_prompt_layernorm_fwd_planes_f32(const float* tok, const float
     const int T = B * P;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D);
     hipLaunchKernelGGL(prompt_layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, tok, ppos, P, drop_p, seed, seed_dev, gamma, beta,
-                       (float*)nullptr, T, D, eps, y_hi, y_lo);
+                       (float*)nullptr, T, D, eps, y_hi, y_lo, fmt);
     ACT_LAUNCH_CHECK(); return 0;
+}
+extern "C" int act_prompt_layernorm_fwd_planes_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
+                                                   const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, uint16_t* y_hi,
+                                                   uint16_t* y_lo, act_stream_t stream) {
+    return prompt_layernorm_fwd_planes(tok, ppos, B, P, D, drop_p, seed, seed_dev, gamma, beta, eps, y_hi, y_lo, PlaneFmt::bf16(), stream);
+}
+extern "C" int act_prompt_layernorm_fwd_f16_planes_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
+                                                       const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, uint16_t* y_h1,
+                                                       uint16_t* y_h2, float plane_scale, act_stream_t stream) {
+    if (!(plane_scale > 0.f)) return ACT_E_BADARG;
+    return prompt_layernorm_fwd_planes(tok, ppos, B, P, D, drop_p, seed, seed_dev, gamma, beta, eps, y_h1, y_h2, PlaneFmt::f16(plane_scale), stream);
 }
 
 extern "C" int act_prompt_layernorm_fwd_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
@@ -358,7 +370,7 @@ extern "C" int act_prompt_layernorm_fwd_f32(const float* tok, const float* ppos,
     const int T = B * P;
     ActProfScope ps(KID_LAYERNORM_FWD, s, 0.0, 4.0 * T * (double)D);
     hipLaunchKernelGGL(prompt_layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, tok, ppos, P, drop_p, seed, seed_dev, gamma, beta, y, T, D, eps,
-                       nullptr, nullptr);
+                       nullptr, nullptr, PlaneFmt::bf16());
     ACT_LAUNCH_CHECK(); return 0;
 }
 

@@ -1362,6 +1362,35 @@ def prompt_kv(tok, ppos, B, drop_p, seed, gamma, beta, eps, w, bias=None, seed_d
     return gemm(n1p, w, True, True, bias=bias)
 
 
+def prompt_layernorm_f16_planes(tok, ppos, B, drop_p, seed, gamma, beta, eps, scale, seed_dev=None):
+    """the rows of prompt_layernorm (same mask) written as f16 planes [2, B*P, D] at ``scale`` (bit-identical to split_f16x2(prompt_layernorm(...), scale))"""
+    P, D = tok.shape
+    planes = torch.empty(2, B * P, D, dtype=torch.float16, device=tok.device)
+    check(lib.act_prompt_layernorm_fwd_f16_planes_f32(ptr(_f32c(tok)), ptr(_f32c(ppos)), B, P, D, float(drop_p), int(seed), ptr(seed_dev), ptr(gamma), ptr(beta),
+                                                      float(eps), ptr(planes[0]), ptr(planes[1]), float(scale), stream()),
+          "act_prompt_layernorm_fwd_f16_planes_f32")
+    return planes
+
+
+def prompt_kv_f16x3(tok, ppos, B, drop_p, seed, gamma, beta, eps, w_planes, w_inv_scale, a_scale, bias=None, seed_dev=None, tile=0, out=None, planes=None):
+    """prompt_kv as ONE dense split-f16 product (act_prompt_kv_fwd_f16x3_f32, the default teacher's form): w_planes [2, N, D] f16 and w_inv_scale [N] as
+    gemm_nt_f16x3 takes them, a_scale = the static scale of the LayerNorm rows.  ``planes``: the f16 scratch the rows are split into (>= 2 B P D elements;
+    allocated when None).  -> kv [B*P, N], or None when the entry answers ACT_E_UNSUPPORTED (nothing launched, ``out`` untouched)."""
+    P, D = tok.shape
+    N = w_planes.shape[1]
+    if out is None:
+        out = torch.empty(B * P, N, dtype=torch.float32, device=tok.device)
+    if planes is None:
+        planes = torch.empty(2 * B * P * D, dtype=torch.float16, device=tok.device)
+    rc = lib.act_prompt_kv_fwd_f16x3_f32(ptr(_f32c(tok)), ptr(_f32c(ppos)), B, P, D, N, float(drop_p), int(seed), ptr(seed_dev), ptr(gamma), ptr(beta),
+                                         float(eps), ptr(w_planes[0]), ptr(w_planes[1]), ptr(w_inv_scale), float(a_scale), ptr(bias), ptr(out), ptr(planes),
+                                         planes.numel(), int(tile), stream())
+    if rc == _E_UNSUPPORTED:
+        return None
+    check(rc, "act_prompt_kv_fwd_f16x3_f32")
+    return out
+
+
 def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, bqkv, wproj, bproj, n2w, n2b, w1, b1, w2, b2, heads, eps, n1p=None,
                                    kvp=None):
     """Inference-only pre-LN block on G 'patch' tokens per cloud with P extra 'prompt' tokens that act as keys/values only

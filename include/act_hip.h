@@ -446,6 +446,10 @@ int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const flo
                                      float eps, act_stream_t stream);
 int act_attention_fwd_prefix_f16_planes_f32(const float* kv0, int S0, const float* qkv1, int Sq, float* out, uint16_t* out_h1, uint16_t* out_h2,
                                             float plane_scale, float* lse, int B, int H, int head_dim, float scale, act_stream_t stream);
+/* the prompt rows of act_prompt_layernorm_fwd_f32 (same Philox mask, bit for bit) as f16 planes at plane_scale (> 0, else ACT_E_BADARG; planes 8-byte aligned) */
+int act_prompt_layernorm_fwd_f16_planes_f32(const float* tok, const float* ppos, int B, int P, int D, float drop_p, uint64_t seed,
+                                            const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, uint16_t* y_h1, uint16_t* y_h2,
+                                            float plane_scale, act_stream_t stream);
 /* The group-max product of the frozen tokenizer's mini-PointNet on this kernel:  out[g, :] = max over the `group` (32 or 64) rows of group g of
  * (a . B^T + bias), a [M, K] = relu(A * a_col_scale[k] + a_col_shift[k]) -- nothing else is stored.  A != NULL: a is formed, scaled by a_scale and split
  * while the kernel stages A (fp32, row stride lda; a_h1 / a_h2 unused); A == NULL: a_h1 / a_h2 are the planes of a * a_scale, as the pass
@@ -576,6 +580,15 @@ size_t act_prompt_kv_workspace(int B, int P, int D, int N);      /* bytes; 0 for
 int act_prompt_kv_fwd_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed,
                           const uint64_t* seed_dev, const float* gamma, const float* beta, float eps, const float* W, const float* bias,
                           float* kvp, float* scratch, size_t scratch_bytes, float* workspace, size_t workspace_bytes, act_stream_t stream);
+/* The same keys / values as ONE dense product on the split-f16 kernel (the default teacher's form): act_prompt_layernorm_fwd_f16_planes_f32 into `planes`
+ * (second plane B P D elements further; planes_elems >= 2 B P D, 16-byte aligned) at a_scale, then act_sgemm_nt_f16x3_planes_tile_f32 with the bias epilogue
+ * -> kv [B P, N] fp32.  w_h1 / w_h2 / w_inv: the planes and inverse row scales of W [N, D]; a_scale: the static activation scale of the LayerNorm rows; tile: 0 =
+ * the library's rule, 128, 192.  ACT_E_UNSUPPORTED (nothing launched) when switched off (ACT_PROMPT_KV_F16X3=0 / act_prompt_kv_f16x3(0)), for a_scale <= 0,
+ * a null plane or scale pointer, planes_elems too small, or a shape act_sgemm_nt_f16x3_supported(B P, N, D) refuses: the caller runs act_prompt_kv_fwd_f32. */
+int act_prompt_kv_f16x3(int on /* < 0: query */);       /* -> previous setting */
+int act_prompt_kv_fwd_f16x3_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, const float* w_inv,
+                                float a_scale, const float* bias, float* kv, uint16_t* planes, size_t planes_elems, int tile, act_stream_t stream);
 size_t act_prefix_block_bwd_scratch_floats(const act_block_dims_t* d, int P);
 int act_prefix_block_bwd_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* prm, const float* saved,
                              const float* dout, float* dx, float* dprm, float* scratch, float* workspace, size_t workspace_bytes,
@@ -620,7 +633,8 @@ int act_prefix_block_bwd_bf16x3_f32(const act_block_dims_t* d, int P, const act_
 int act_prefix_vit_fwd_f32(const act_prefix_vit_t* m, const float* tokens, const float* center, float* out, float* scratch,
                            float* workspace, size_t workspace_bytes, act_stream_t stream);
 /* DEFAULT on the host side (ACT_TEACHER_F16X3, 0 restores act_prefix_vit_fwd_f32): the FOUR Linear products of every block (qkv, proj, fc1, fc2 on the patch
- * tokens) on the split-f16 kernel; the prompts' keys / values stay on act_prompt_kv_fwd_f32.  w_planes[4 i + j] = h1 plane of block i's j-th weight, split
+ * tokens) on the split-f16 kernel, and the prompts' keys / values through act_prompt_kv_fwd_f16x3_f32 at the qkv Linear's scale (act_prompt_kv_fwd_f32 where
+ * that entry answers ACT_E_UNSUPPORTED).  w_planes[4 i + j] = h1 plane of block i's j-th weight, split
  * with one power of two per output row (h2 plane rows * cols elements further); w_inv_scale[4 i + j] = the N inverse row scales (device); a_scale[4 i + j]
  * (HOST) = the static activation scale s_A of that Linear, from a weight-only bound on its operand (bound * s_A <= 2^15: overflow impossible by
  * construction), or 0: that Linear stays on the f32 kernel, as does any shape the kernel does not take.  a_planes as in act_vit_bf16x3_t. */
