@@ -176,8 +176,11 @@ __global__ __launch_bounds__(1024) void fps_big_kernel(const float* __restrict__
 template <int WAVES, int PPL>
 static int launch_fps(const float* xyz, int B, int N, int G, int32_t* idx, float* centers, int skip, hipStream_t s) {
     const size_t cloud_bytes = (size_t)N * 3 * sizeof(float);
-    const int lds_cloud = cloud_bytes <= 128 * 1024 ? 1 : 0;
-    const size_t smem = 4 * WAVES * sizeof(float) + (lds_cloud ? cloud_bytes : 0) + (size_t)G * sizeof(int);
+    // the cloud goes to the LDS only where it fits NEXT TO the header and the G selected indices; a request whose indices crowd it out reads
+    // the winner's coordinates from global memory instead (N = 10,922 with G >= 8,131), so only G itself can exceed the limit below
+    const size_t fixed_bytes = 4 * WAVES * sizeof(float) + (size_t)G * sizeof(int);
+    const int lds_cloud = cloud_bytes <= 128 * 1024 && fixed_bytes + cloud_bytes <= 160 * 1024 ? 1 : 0;
+    const size_t smem = fixed_bytes + (lds_cloud ? cloud_bytes : 0);
     if (smem > 160 * 1024) return ACT_E_BADARG;
     auto k = lds_cloud ? fps_kernel<WAVES, PPL, true> : fps_kernel<WAVES, PPL, false>;
     if (smem > 48 * 1024) {
