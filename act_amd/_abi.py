@@ -251,11 +251,6 @@ _TABLE = {
     "act_dgcnn_features_f32": [_P(Dgcnn), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_dgcnn_features_f16x3_f32": [_P(Dgcnn), _P(DgcnnF16x3), _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     # dense per-point prediction (csrc/seg.hip)
-    "act_three_nn_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "act_interp_rows_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_interp_rows_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_interp_xyz_grad_workspace": (_sz, [_ll, _i]),
-    "act_interp_xyz_grad_f32": [_vp, _vp, _ll, _i, _vp, _vp, _vp, _sz, _vp],
     "act_log_softmax_fwd_f32": [_vp, _ll, _i, _vp, _vp],
     "act_log_softmax_bwd_f32": [_vp, _vp, _ll, _i, _vp, _vp],
     "act_nll_weighted_workspace": (_sz, [_ll]),
@@ -331,11 +326,13 @@ _TABLE = {
     "act_group_rows_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
     "act_group_gather_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "act_group_gather_bwd_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp],
-    # PointNet++ feature propagation at any size (csrc/sa.hip)
-    "act_three_nn_any_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    # three-NN feature propagation (csrc/sa.hip)
+    "act_three_nn_f32": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "act_three_adj_i32": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "act_interp_rows_any_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "act_interp_rows_any_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_rows_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_rows_bwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp],
+    "act_interp_xyz_grad_workspace": (_sz, [_ll, _i]),
+    "act_interp_xyz_grad_f32": [_vp, _vp, _ll, _i, _vp, _vp, _vp, _sz, _vp],
     # DGCNN classifier: feature-space kNN, EdgeConv tail with BatchNorm, LeakyReLU row BatchNorm (csrc/edgeconv.hip)
     "act_knn_feat_f32": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "act_edge_bn_workspace": (_sz, [_i, _i, _i, _i]),

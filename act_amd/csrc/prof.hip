@@ -71,7 +71,7 @@ void act_prof_end(int kid, hipStream_t stream) {
 }
 
 extern "C" {
-int act_version(void) { return 100; }
+int act_version(void) { return 101; }
 const char* act_arch(void) { return "gfx950"; }
 int act_prof_enable(int on) { int p = g_act_prof_on; g_act_prof_on = on ? 1 : 0; return p; }
 int act_prof_reset(void) {

@@ -1,6 +1,7 @@
 // sa.hip -- PointNet++ set abstraction (reference: {part,semantic}_segmentation/models/pointnet2_utils.py:84-155; upstream pointnet2_ops
 // ball_query / group_points): radius search that keeps the first nsample hits in index order, the fused gather that writes the grouped rows
-// in the row-major layout the row GEMMs read, and the deterministic backward of that gather over an inverse adjacency.
+// in the row-major layout the row GEMMs read, and the deterministic backward of that gather over an inverse adjacency; and the library's one
+// three-NN feature propagation (PointNet++ networks and the Transformer segmentation head): search, inverse adjacency, row interpolation.
 //
 // Conventions: distances are the DIFFERENCE form (dx*dx + dy*dy) + dz*dz in fp32, never contracted (file built with -ffp-contract=off, and
 // sqdist3 rounds every product and sum); radius^2 is the fp32 product of the fp32 radius, as in upstream's kernel.  No float atomics and no
@@ -320,15 +321,15 @@ extern "C" int act_group_gather_bwd_f32(const float* dout, const int32_t* idx, i
     ACT_LAUNCH_CHECK(); return 0;
 }
 
-// ---- feature propagation at any size (reference pointnet2_utils.py:262-312; upstream pointnet2_ops three_nn / three_interpolate) --------------
+// ---- three-NN feature propagation (reference pointnet2_utils.py:262-312; upstream pointnet2_ops three_nn / three_interpolate) ------------------
 // Three nearest known points of every unknown point.  One lane per unknown point; the known cloud streams through LDS in tiles of SA_NN_TILE
-// points (every lane reads the same words: broadcast, no bank conflicts), the three best (d2, index) pairs stay in registers.  Same distance,
-// same strict '<' insertion over ascending indices and same weight arithmetic as three_nn_kernel of seg.hip, so at 3 <= m <= 512 the two agree
-// bit for bit.  m < 3: the slots that never fill keep idx 0 and d2 = +inf, so r = 1 / (inf + 1e-8) = 0 and their weight is exactly 0 while the
-// others are normalised over what exists (m == 1: r0 / r0 = 1).
+// points (every lane reads the same words: broadcast, no bank conflicts), the three best (d2, index) pairs stay in registers: ascending
+// (distance, index) order, strict '<' keeps the lower index on ties (the known points are visited in increasing index).
+// weight = (1 / (d2 + 1e-8)) / sum of the three.  m < 3: the slots that never fill keep idx 0 and d2 = +inf, so r = 1 / (inf + 1e-8) = 0 and
+// their weight is exactly 0 while the others are normalised over what exists (m == 1: r0 / r0 = 1).
 #define SA_NN_TILE 1024
-__global__ __launch_bounds__(256) void three_nn_any_kernel(const float* __restrict__ unknown, const float* __restrict__ known, int n, int m,
-                                                           int32_t* __restrict__ idx, float* __restrict__ wout, float* __restrict__ d2out) {
+__global__ __launch_bounds__(256) void three_nn_kernel(const float* __restrict__ unknown, const float* __restrict__ known, int n, int m,
+                                                       int32_t* __restrict__ idx, float* __restrict__ wout, float* __restrict__ d2out) {
     __shared__ float sc[SA_NN_TILE * 3];
     const int b = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -366,8 +367,60 @@ __global__ __launch_bounds__(256) void three_nn_any_kernel(const float* __restri
     if (d2out) { d2out[p * 3 + 0] = d0; d2out[p * 3 + 1] = d1; d2out[p * 3 + 2] = d2; }
 }
 
-extern "C" int act_three_nn_any_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2,
-                                    int32_t* adj_off, int32_t* adj_ent, act_stream_t stream) {
+// The inverse adjacency of idx [B, 3n] over m <= SA_ADJ3_MAX_M known points in ONE launch, one workgroup per cloud: thread g counts the entries
+// e = 3i+k with idx[e] == g (pass 1), an exclusive scan over the known points gives the offsets, pass 2 lists the entries of every known point in
+// increasing e.  No atomics, and an index outside [0, m) matches no thread that writes: the same off / ent as build_adjacency.
+#define SA_ADJ3_MAX_M 256
+#define SA_ADJ3_CHUNK 2048
+__global__ __launch_bounds__(SA_ADJ3_MAX_M) void three_adj_kernel(const int32_t* __restrict__ idx, int n, int m, int32_t* __restrict__ off,
+                                                                   int32_t* __restrict__ ent) {
+    __shared__ int32_t chunk[SA_ADJ3_CHUNK];
+    __shared__ int32_t cnt[SA_ADJ3_MAX_M + 1];
+    const int b = blockIdx.x, g = threadIdx.x, E = 3 * n;
+    const int32_t* ib = idx + (size_t)b * E;
+    int c = 0;
+    for (int e0 = 0; e0 < E; e0 += SA_ADJ3_CHUNK) {
+        const int len = min(SA_ADJ3_CHUNK, E - e0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < len; i += blockDim.x) chunk[i] = ib[e0 + i];
+        __syncthreads();
+        for (int i = 0; i < len; ++i) c += (chunk[i] == g);
+    }
+    if (g < m) cnt[g] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        for (int j = 0; j < m; ++j) { const int t = cnt[j]; cnt[j] = acc; acc += t; }
+        cnt[m] = acc;
+    }
+    __syncthreads();
+    int32_t* ob = off + (size_t)b * (m + 1);
+    if (g < m) ob[g] = cnt[g];
+    if (g == 0) ob[m] = cnt[m];
+    int pos = g < m ? cnt[g] : 0;
+    int32_t* eb = ent + (size_t)b * E;
+    for (int e0 = 0; e0 < E; e0 += SA_ADJ3_CHUNK) {
+        const int len = min(SA_ADJ3_CHUNK, E - e0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < len; i += blockDim.x) chunk[i] = ib[e0 + i];
+        __syncthreads();
+        if (g < m)
+            for (int i = 0; i < len; ++i)
+                if (chunk[i] == g) eb[pos++] = e0 + i;
+    }
+}
+
+// off [B,m+1] / ent [B,3n] of idx [B,3n]: the one-launch kernel while a workgroup holds a thread per known point, else the shared builder (three
+// launches that spread a cloud's known points over several workgroups).  Both give the same lists, so the choice does not show in the output.
+static int three_adjacency(const int32_t* idx, int B, int n, int m, int32_t* off, int32_t* ent, hipStream_t s) {
+    if (m > SA_ADJ3_MAX_M) return build_adjacency(idx, B, m, 3 * n, off, ent, s);
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 4.0 * B * ((double)n * 6 + m + 1));
+    hipLaunchKernelGGL(three_adj_kernel, dim3(B), dim3(SA_ADJ3_MAX_M), 0, s, idx, n, m, off, ent);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+
+extern "C" int act_three_nn_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2,
+                                int32_t* adj_off, int32_t* adj_ent, act_stream_t stream) {
     if (!unknown || !known || !idx || !weight) return ACT_E_NULLPTR;
     if ((adj_off == nullptr) != (adj_ent == nullptr)) return ACT_E_NULLPTR;
     if (B <= 0 || B > 65535 || n <= 0 || m <= 0) return ACT_E_BADARG;
@@ -375,79 +428,117 @@ extern "C" int act_three_nn_any_f32(const float* unknown, const float* known, in
     hipStream_t s = (hipStream_t)stream;
     {
         ActProfScope ps(KID_ELTWISE, s, 9.0 * B * (double)n * m, 4.0 * B * ((double)n * 9 + (double)m * 3));
-        hipLaunchKernelGGL(three_nn_any_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, s, unknown, known, n, m, idx, weight, d2);
+        hipLaunchKernelGGL(three_nn_kernel, dim3(cdiv(n, 256), B), dim3(256), 0, s, unknown, known, n, m, idx, weight, d2);
         ACT_LAUNCH_CHECK();
     }
-    return adj_off ? build_adjacency(idx, B, m, 3 * n, adj_off, adj_ent, s) : 0;
+    return adj_off ? three_adjacency(idx, B, n, m, adj_off, adj_ent, s) : 0;
 }
 
 // the inverse adjacency alone, for caller-supplied indices (three_interpolate): off [B,m+1], ent [B,3n]; an index outside [0,m) is in no list
 extern "C" int act_three_adj_i32(const int32_t* idx, int B, int n, int m, int32_t* adj_off, int32_t* adj_ent, act_stream_t stream) {
     if (!idx || !adj_off || !adj_ent) return ACT_E_NULLPTR;
     if (B <= 0 || B > 65535 || n <= 0 || m <= 0 || 3LL * n > 0x7fffffffLL) return ACT_E_BADARG;
-    return build_adjacency(idx, B, m, 3 * n, adj_off, adj_ent, (hipStream_t)stream);
+    return three_adjacency(idx, B, n, m, adj_off, adj_ent, (hipStream_t)stream);
 }
 
-// Row interpolation with skipped slots: Y[b*N+n, :] = sum over the slots k with w[n,k] != 0 and idx[n,k] in [0,G) of w[n,k] * P[b*G + idx[n,k], :],
-// the sum in slot order as w0*a, then fma, then fma (the order of interp_fwd_kernel of seg.hip).  A skipped slot is never read, so a
-// non-finite row behind a weight of exactly 0 cannot reach the result.  V = float4 when C % 4 == 0 and the rows are 16-byte aligned, else float.
+// ---- row interpolation ----------------------------------------------------------------------------------------------------------------------
+// Y[b*N+n, :] = sum over the slots k with w[n,k] != 0 and idx[n,k] in [0,G) of w[n,k] * P[b*G + idx[n,k], :]  (+ xyz[n] . wxyz[c,:], then + bias[c]),
+// the sum in slot order as w0*a, then fma, then fma.  A skipped slot is never read, so a non-finite row behind a weight of exactly 0 cannot
+// reach the result.  One row per wave, 4 rows per block; V = float4 when C % 4 == 0 and the rows are 16-byte aligned, else float.
 __device__ __forceinline__ float vmul(float w, float v) { return w * v; }
 __device__ __forceinline__ float vfma(float w, float v, float a) { return fmaf(w, v, a); }
+__device__ __forceinline__ float vadd(float a, float v) { return a + v; }
 __device__ __forceinline__ float4 vmul(float w, float4 v) { return make_float4(w * v.x, w * v.y, w * v.z, w * v.w); }
 __device__ __forceinline__ float4 vfma(float w, float4 v, float4 a) {
     return make_float4(fmaf(w, v.x, a.x), fmaf(w, v.y, a.y), fmaf(w, v.z, a.z), fmaf(w, v.w, a.w));
 }
+__device__ __forceinline__ float4 vadd(float4 a, float4 v) { return make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w); }
+__device__ __forceinline__ float vsel(bool c, float a, float b) { return c ? a : b; }
+__device__ __forceinline__ float4 vsel(bool c, float4 a, float4 b) { return make_float4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w); }
 __device__ __forceinline__ void vzero(float& v) { v = 0.f; }
 __device__ __forceinline__ void vzero(float4& v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
-
-template <typename V>
-__global__ __launch_bounds__(256) void interp_any_fwd_kernel(const V* __restrict__ P, const int32_t* __restrict__ idx, const float* __restrict__ w,
-                                                             int N, int G, int CV, long long R, V* __restrict__ Y) {
-    const long long r = (long long)blockIdx.x * 4 + threadIdx.y;        // row blocks on grid.x (up to 2^31 - 1), channel blocks on grid.y
-    const int c = blockIdx.y * 64 + threadIdx.x;
-    if (r >= R || c >= CV) return;
-    const long long base = (r / N) * G;
-    V y;
-    vzero(y);
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int j = idx[r * 3 + k];
-        const float wk = w[r * 3 + k];
-        if (wk != 0.f && (unsigned)j < (unsigned)G) {
-            const V v = P[(base + j) * CV + c];
-            y = first ? vmul(wk, v) : vfma(wk, v, y);
-            first = false;
-        }
-    }
-    Y[r * CV + c] = y;
+// p . wxyz[c,:] for the channels of lane element c: wc = wxyz + 3 * (first channel)
+__device__ __forceinline__ float xyz_dot(float px, float py, float pz, const float* wc) { return fmaf(pz, wc[2], fmaf(py, wc[1], px * wc[0])); }
+__device__ __forceinline__ void vxyz(float px, float py, float pz, const float* wc, float& v) { v = xyz_dot(px, py, pz, wc); }
+__device__ __forceinline__ void vxyz(float px, float py, float pz, const float* wc, float4& v) {
+    v = make_float4(xyz_dot(px, py, pz, wc), xyz_dot(px, py, pz, wc + 3), xyz_dot(px, py, pz, wc + 6), xyz_dot(px, py, pz, wc + 9));
 }
 
-static bool vec4_ok(int C, const void* a, const void* b) { return !(C & 3) && !(((uintptr_t)a | (uintptr_t)b) & 15); }
+template <typename V>
+__global__ __launch_bounds__(256) void interp_fwd_kernel(const V* __restrict__ P, const int32_t* __restrict__ idx, const float* __restrict__ w,
+                                                         const float* __restrict__ xyz, const float* __restrict__ wxyz,
+                                                         const float* __restrict__ bias, int N, int G, int CV, long long R, V* __restrict__ Y) {
+    const long long r = (long long)blockIdx.x * 4 + threadIdx.y;        // a one-dimensional grid of row blocks; the wave walks its row's channels
+    if (r >= R) return;
+    const long long base = (r / N) * G;
+    int j[3];
+    float wk[3];
+    bool live[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        j[k] = idx[r * 3 + k];
+        wk[k] = w[r * 3 + k];
+        live[k] = wk[k] != 0.f && (unsigned)j[k] < (unsigned)G;
+    }
+    float px = 0.f, py = 0.f, pz = 0.f;
+    if (wxyz) { px = xyz[r * 3 + 0]; py = xyz[r * 3 + 1]; pz = xyz[r * 3 + 2]; }
+    for (int c = threadIdx.x; c < CV; c += 64) {
+        V y;
+        if (live[0] && live[1] && live[2]) {                             // wave-uniform (a wave holds one row): the three loads are in flight together
+            const V a = P[(base + j[0]) * CV + c], bb = P[(base + j[1]) * CV + c], cc = P[(base + j[2]) * CV + c];
+            y = vfma(wk[2], cc, vfma(wk[1], bb, vmul(wk[0], a)));
+        } else {
+            vzero(y);
+            bool first = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (live[k]) {
+                    const V v = P[(base + j[k]) * CV + c];
+                    y = first ? vmul(wk[k], v) : vfma(wk[k], v, y);
+                    first = false;
+                }
+            }
+        }
+        if (wxyz) {
+            V t;
+            vxyz(px, py, pz, wxyz + (size_t)c * 3 * (sizeof(V) / sizeof(float)), t);
+            y = vadd(y, t);
+        }
+        if (bias) y = vadd(y, reinterpret_cast<const V*>(bias)[c]);
+        Y[r * CV + c] = y;
+    }
+}
 
-extern "C" int act_interp_rows_any_fwd_f32(const float* P, const int32_t* idx, const float* weight, int B, int N, int G, int C, float* Y,
-                                           act_stream_t stream) {
+static bool vec4_ok(int C, const void* a, const void* b, const void* c = nullptr) {
+    return !(C & 3) && !(((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15);
+}
+
+extern "C" int act_interp_rows_fwd_f32(const float* P, const int32_t* idx, const float* weight, const float* xyz, const float* wxyz,
+                                       const float* bias, int B, int N, int G, int C, float* Y, act_stream_t stream) {
     if (!P || !idx || !weight || !Y) return ACT_E_NULLPTR;
+    if (wxyz && !xyz) return ACT_E_NULLPTR;
     if (B <= 0 || N <= 0 || G <= 0 || C <= 0) return ACT_E_BADARG;
     const long long R = (long long)B * N;
-    if (R > (1LL << 27) || C > 64 * 65535) return ACT_E_BADARG;         // 2^25 row blocks of 64 x 4 threads on grid.x, channel blocks on grid.y
+    if (R > (1LL << 27)) return ACT_E_BADARG;                           // 2^25 row blocks of 64 x 4 threads
     hipStream_t s = (hipStream_t)stream;
-    ActProfScope ps(KID_ELTWISE, s, 6.0 * R * C, 4.0 * (R * (double)C * 4 + R * 6));
-    if (vec4_ok(C, P, Y))
-        hipLaunchKernelGGL(interp_any_fwd_kernel<float4>, dim3(cdiv(R, 4), cdiv(C / 4, 64)), dim3(64, 4), 0, s, reinterpret_cast<const float4*>(P),
-                           idx, weight, N, G, C / 4, R, reinterpret_cast<float4*>(Y));
+    ActProfScope ps(KID_ELTWISE, s, 6.0 * R * C, 4.0 * (R * (double)C * 4 + R * 9));
+    if (vec4_ok(C, P, Y, bias))
+        hipLaunchKernelGGL(interp_fwd_kernel<float4>, dim3(cdiv(R, 4)), dim3(64, 4), 0, s, reinterpret_cast<const float4*>(P), idx,
+                           weight, xyz, wxyz, bias, N, G, C / 4, R, reinterpret_cast<float4*>(Y));
     else
-        hipLaunchKernelGGL(interp_any_fwd_kernel<float>, dim3(cdiv(R, 4), cdiv(C, 64)), dim3(64, 4), 0, s, P, idx, weight, N, G, C, R, Y);
+        hipLaunchKernelGGL(interp_fwd_kernel<float>, dim3(cdiv(R, 4)), dim3(64, 4), 0, s, P, idx, weight, xyz, wxyz, bias, N, G, C, R, Y);
     ACT_LAUNCH_CHECK(); return 0;
 }
 
-// dP[b*G+g, :] = sum over the entries e of known point g (increasing e) with w[e] != 0 of w[e] * dY[b*N + e/3, :]: interp_bwd_kernel of seg.hip
-// with the skip, at any C.  Entries are bounded by the adjacency builder (0 <= e < 3N).
+// dP[b*G+g, :] = sum over the entries e of known point g (increasing e) with w[e] != 0 of w[e] * dY[b*N + e/3, :].  Entries are bounded by the
+// adjacency builder (0 <= e < 3N).
 template <typename V>
-__global__ __launch_bounds__(256) void interp_any_bwd_kernel(const V* __restrict__ dY, const int32_t* __restrict__ off, const int32_t* __restrict__ ent,
-                                                             const float* __restrict__ w, int N, int G, int CV, long long RG, V* __restrict__ dP) {
-    const long long rg = (long long)blockIdx.x * 4 + threadIdx.y;
-    const int c = blockIdx.y * 64 + threadIdx.x;
+__global__ __launch_bounds__(256) void interp_bwd_kernel(const V* __restrict__ dY, const int32_t* __restrict__ off, const int32_t* __restrict__ ent,
+                                                         const float* __restrict__ w, int N, int G, int CV, int CB, long long RG, V* __restrict__ dP) {
+    // grid.x = row blocks x CB channel blocks, the channel blocks of a row block next to each other: neighbouring workgroups read neighbouring
+    // pieces of the same dY rows
+    const long long rg = (long long)(blockIdx.x / CB) * 4 + threadIdx.y;
+    const int c = (blockIdx.x % CB) * 64 + threadIdx.x;
     if (rg >= RG || c >= CV) return;
     const long long b = rg / G;
     const int g = (int)(rg - b * G);
@@ -455,31 +546,85 @@ __global__ __launch_bounds__(256) void interp_any_bwd_kernel(const V* __restrict
     const int32_t* eb = ent + b * 3LL * N;
     const float* wb = w + b * 3LL * N;
     const V* yb = dY + b * (long long)N * CV;
+    const int e0 = max(ob[g], 0), e1 = min(ob[g + 1], 3 * N);          // a caller's adjacency is never followed out of its arrays
     V acc;
     vzero(acc);
-    const int e1 = min(ob[g + 1], 3 * N);                              // a caller's adjacency is never followed out of its arrays
-    for (int i = max(ob[g], 0); i < e1; ++i) {
-        const int e = eb[i];
-        if ((unsigned)e >= 3u * (unsigned)N) continue;
-        const float wt = wb[e];
-        if (wt != 0.f) acc = vfma(wt, yb[(long long)(e / 3) * CV + c], acc);
+    // no branch in the walk, so that the row loads of several entries are in flight together: an entry outside [0, 3N) reads entry 0 and, like
+    // an entry of weight 0, leaves acc as it is.  A wave holds one known point, so the list bounds and the entry are the same in all its
+    // lanes: read once per wave, the index arithmetic runs on the scalar unit (measured 203 against 208 us at 32 x 2,048 <- 128, C = 1,536).
+    const int s0 = __builtin_amdgcn_readfirstlane(e0), s1 = __builtin_amdgcn_readfirstlane(e1);
+    for (int i = s0; i < s1; ++i) {
+        const int e = __builtin_amdgcn_readfirstlane(eb[i]);
+        const bool in = (unsigned)e < 3u * (unsigned)N;
+        const int es = in ? e : 0;
+        const float wt = wb[es];
+        acc = vsel(in && wt != 0.f, vfma(wt, yb[(long long)(es / 3) * CV + c], acc), acc);
     }
     dP[rg * CV + c] = acc;
 }
 
-extern "C" int act_interp_rows_any_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N,
-                                           int G, int C, float* dP, act_stream_t stream) {
+extern "C" int act_interp_rows_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G,
+                                       int C, float* dP, act_stream_t stream) {
     if (!dY || !adj_off || !adj_ent || !weight || !dP) return ACT_E_NULLPTR;
     if (B <= 0 || N <= 0 || G <= 0 || C <= 0 || 3LL * N > 0x7fffffffLL) return ACT_E_BADARG;
     const long long RG = (long long)B * G;
-    if (RG > (1LL << 27) || C > 64 * 65535) return ACT_E_BADARG;
+    const bool v4 = vec4_ok(C, dY, dP);
+    const int CV = v4 ? C / 4 : C, CB = (CV + 63) / 64;
+    if (RG > (1LL << 27) || ((RG + 3) / 4) * CB > 0x7fffffffLL) return ACT_E_BADARG;      // row blocks x channel blocks on grid.x
+    const unsigned blocks = (unsigned)(((RG + 3) / 4) * CB);
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_ELTWISE, s, 6.0 * B * (double)N * C, 4.0 * ((double)B * N * C * 3 + RG * C + B * (double)N * 6));
-    if (vec4_ok(C, dY, dP))
-        hipLaunchKernelGGL(interp_any_bwd_kernel<float4>, dim3(cdiv(RG, 4), cdiv(C / 4, 64)), dim3(64, 4), 0, s,
-                           reinterpret_cast<const float4*>(dY), adj_off, adj_ent, weight, N, G, C / 4, RG, reinterpret_cast<float4*>(dP));
+    if (v4)
+        hipLaunchKernelGGL(interp_bwd_kernel<float4>, dim3(blocks), dim3(64, 4), 0, s, reinterpret_cast<const float4*>(dY), adj_off, adj_ent, weight,
+                           N, G, CV, CB, RG, reinterpret_cast<float4*>(dP));
     else
-        hipLaunchKernelGGL(interp_any_bwd_kernel<float>, dim3(cdiv(RG, 4), cdiv(C, 64)), dim3(64, 4), 0, s, dY, adj_off, adj_ent, weight, N, G, C,
-                           RG, dP);
+        hipLaunchKernelGGL(interp_bwd_kernel<float>, dim3(blocks), dim3(64, 4), 0, s, dY, adj_off, adj_ent, weight, N, G, CV, CB, RG, dP);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+
+// ---- gradient of the xyz columns and the bias of the interpolation epilogue (the restructured first propagation conv) ----
+// dwxyz[c, j] = sum_r dY[r, c] * xyz[r, j], dbias[c] = sum_r dY[r, c]: per block of SEG_XYZ_ROWS rows a partial [4, C], then one ordered pass
+#define SEG_XYZ_ROWS 512
+__global__ __launch_bounds__(256) void xyz_grad_partial_kernel(const float* __restrict__ dY, const float* __restrict__ xyz, long long R, int C,
+                                                               float* __restrict__ part) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const long long r0 = (long long)blockIdx.y * SEG_XYZ_ROWS, r1 = min(R, r0 + SEG_XYZ_ROWS);
+    if (c >= C) return;
+    float sx = 0.f, sy = 0.f, sz = 0.f, sb = 0.f;
+    for (long long r = r0; r < r1; ++r) {
+        const float g = dY[r * C + c];
+        sx = fmaf(g, xyz[r * 3 + 0], sx); sy = fmaf(g, xyz[r * 3 + 1], sy); sz = fmaf(g, xyz[r * 3 + 2], sz); sb += g;
+    }
+    float* pb = part + (size_t)blockIdx.y * 4 * C;
+    pb[c] = sx; pb[C + c] = sy; pb[2 * C + c] = sz; pb[3 * C + c] = sb;
+}
+__global__ __launch_bounds__(256) void xyz_grad_final_kernel(const float* __restrict__ part, int nparts, int C, float* __restrict__ dwxyz,
+                                                             float* __restrict__ dbias) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float sx = 0.f, sy = 0.f, sz = 0.f, sb = 0.f;
+    for (int p = 0; p < nparts; ++p) {
+        const float* pb = part + (size_t)p * 4 * C;
+        sx += pb[c]; sy += pb[C + c]; sz += pb[2 * C + c]; sb += pb[3 * C + c];
+    }
+    if (dwxyz) { dwxyz[c * 3 + 0] = sx; dwxyz[c * 3 + 1] = sy; dwxyz[c * 3 + 2] = sz; }
+    if (dbias) dbias[c] = sb;
+}
+
+extern "C" size_t act_interp_xyz_grad_workspace(long long R, int C) {
+    return (size_t)((R + SEG_XYZ_ROWS - 1) / SEG_XYZ_ROWS) * 4 * (size_t)C * sizeof(float);
+}
+
+extern "C" int act_interp_xyz_grad_f32(const float* dY, const float* xyz, long long R, int C, float* dwxyz, float* dbias, float* workspace,
+                                       size_t workspace_bytes, act_stream_t stream) {
+    if (!dY || !xyz || !workspace || (!dwxyz && !dbias)) return ACT_E_NULLPTR;
+    if (R <= 0 || C <= 0) return ACT_E_BADARG;
+    if (workspace_bytes < act_interp_xyz_grad_workspace(R, C)) return ACT_E_BADARG;
+    const int nparts = (int)((R + SEG_XYZ_ROWS - 1) / SEG_XYZ_ROWS);
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 8.0 * R * C, 4.0 * ((double)R * C + R * 3 + 8.0 * nparts * C));
+    hipLaunchKernelGGL(xyz_grad_partial_kernel, dim3(cdiv(C, 256), nparts), dim3(256), 0, s, dY, xyz, R, C, workspace);
+    ACT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(xyz_grad_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, workspace, nparts, C, dwxyz, dbias);
     ACT_LAUNCH_CHECK(); return 0;
 }

@@ -1412,119 +1412,7 @@ def block_forward_prefix_perkernel(x2d, pos2d, prm2d, B, P, G, n1w, n1b, wqkv, b
     return gemm(a, w2, True, True, bias=b2, res=x1)
 
 
-# ---- dense per-point prediction (csrc/seg.hip): three-NN feature propagation, log-softmax, weighted NLL, confusion matrix -------------------
-def three_nn(xyz, centers, want_adj=True):
-    """xyz [B,N,3], centers [B,G,3] -> (idx int32 [B,N,3], weight [B,N,3], adj_off int32 [B,G+1] | None, adj_ent int32 [B,3N] | None):
-    the three nearest centres of every point in ascending (difference-form distance, index) order, their normalised inverse-distance
-    weights (semantic_segmentation/models/pointnet2_utils.py:293-299) and the inverse adjacency the interpolation backward gathers over."""
-    xyz, centers = _f32c(xyz), _f32c(centers)
-    B, N, _ = xyz.shape
-    G = centers.shape[1]
-    dev = xyz.device
-    idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
-    w = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
-    off = torch.empty(B, G + 1, dtype=torch.int32, device=dev) if want_adj else None
-    ent = torch.empty(B, 3 * N, dtype=torch.int32, device=dev) if want_adj else None
-    check(lib.act_three_nn_f32(ptr(xyz), ptr(centers), B, N, G, ptr(idx), ptr(w), ptr(off), ptr(ent), stream()), "act_three_nn_f32")
-    return idx, w, off, ent
-
-
-def interp_rows_fwd(P, idx, w, B, N, G, xyz=None, wxyz=None, bias=None):
-    """P [B*G,C] -> Y [B*N,C] = sum_k w * P[idx] (+ xyz . wxyz^T + bias)"""
-    P, idx, w = _f32c(P), _i32c(idx), _f32c(w)
-    xyz, wxyz, bias = (None if t is None else _f32c(t) for t in (xyz, wxyz, bias))
-    C = P.shape[1]
-    if P.shape[0] != B * G or idx.numel() != 3 * B * N or w.numel() != 3 * B * N or (xyz is not None and xyz.numel() != 3 * B * N) or (
-            wxyz is not None and wxyz.shape != (C, 3)) or (bias is not None and bias.numel() != C):
-        raise _C.ActHipError("interp_rows_fwd: operand shapes do not match B, N, G, C")
-    Y = torch.empty(B * N, C, dtype=torch.float32, device=P.device)
-    check(lib.act_interp_rows_fwd_f32(ptr(P), ptr(idx), ptr(w), ptr(xyz), ptr(wxyz), ptr(bias), B, N, G, C, ptr(Y), stream()),
-          "act_interp_rows_fwd_f32")
-    return Y
-
-
-def interp_rows_bwd(dY, off, ent, w, B, N, G):
-    dY, off, ent, w = _f32c(dY), _i32c(off), _i32c(ent), _f32c(w)
-    C = dY.shape[1]
-    if dY.shape[0] != B * N or off.numel() != B * (G + 1) or ent.numel() != 3 * B * N or w.numel() != 3 * B * N:
-        raise _C.ActHipError("interp_rows_bwd: operand shapes do not match B, N, G")
-    dP = torch.empty(B * G, C, dtype=torch.float32, device=dY.device)
-    check(lib.act_interp_rows_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_bwd_f32")
-    return dP
-
-
-def interp_xyz_grad(dY, xyz, want_w=True, want_b=True):
-    """-> (dY^T xyz [C,3] | None, column sums of dY [C] | None)"""
-    dY, xyz = _f32c(dY), _f32c(xyz)
-    R, C = dY.shape
-    if xyz.numel() != 3 * R:
-        raise _C.ActHipError("interp_xyz_grad: xyz must hold 3 values per row of dY")
-    dw = torch.empty(C, 3, dtype=torch.float32, device=dY.device) if want_w else None
-    db = torch.empty(C, dtype=torch.float32, device=dY.device) if want_b else None
-    ws = workspace(dY.device, lib.act_interp_xyz_grad_workspace(R, C))
-    check(lib.act_interp_xyz_grad_f32(ptr(dY), ptr(xyz), R, C, ptr(dw), ptr(db), ptr(ws), ws.numel() * 4, stream()), "act_interp_xyz_grad_f32")
-    return dw, db
-
-
-class InterpRowsFn(torch.autograd.Function):
-    """three-NN interpolation of per-centre rows to the points: x [B*G,C] -> [B*N,C] (pointnet2_utils.py:300); backward is a gather over the
-    inverse adjacency (deterministic, bit-identical run to run).  The neighbour indices / weights are constants: the reference's distances come
-    from the input cloud, a leaf."""
-
-    @staticmethod
-    def forward(ctx, x, nn3, B, N, G):
-        idx, w, off, ent = nn3
-        y = interp_rows_fwd(x, idx, w, B, N, G)
-        ctx.save_for_backward(w, off, ent)
-        ctx.dims = (B, N, G)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        w, off, ent = ctx.saved_tensors
-        return interp_rows_bwd(dy, off, ent, w, *ctx.dims), None, None, None, None
-
-
-def interp_rows(x, nn3, B, N, G):
-    return InterpRowsFn.apply(x, nn3, B, N, G)
-
-
-class InterpConvFn(torch.autograd.Function):
-    """the first conv of PointNetFeaturePropagation on cat(xyz, interp(x)) in the per-group form: W [C, 3+K] (xyz columns first), x [B*G,K],
-    xyz [B*N,3].  P = x . W[:,3:]^T once per centre (B*G rows instead of B*N), then Y = sum_k w_k P[idx_k] + xyz . W[:,:3]^T + b in one kernel.
-    Equal in real arithmetic to the plain form W . cat(xyz, sum_k w_k x[idx_k]) + b (the weights enter linearly)."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, xyz, nn3, B, N, G):
-        idx, w, off, ent = nn3
-        x = _f32c(x)
-        wf = W[:, 3:].contiguous()
-        wxyz = W[:, :3].contiguous()
-        P = gemm(x, wf, True, True)
-        y = interp_rows_fwd(P, idx, w, B, N, G, xyz=xyz, wxyz=wxyz, bias=b)
-        ctx.save_for_backward(x, wf, xyz, w, off, ent)
-        ctx.dims = (B, N, G)
-        ctx.has_bias = b is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, wf, xyz, w, off, ent = ctx.saved_tensors
-        dy = _f32c(dy)
-        dP = interp_rows_bwd(dy, off, ent, w, *ctx.dims)
-        dx = gemm(dP, wf, True, False) if ctx.needs_input_grad[0] else None
-        dW = db = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dwxyz, db = interp_xyz_grad(dy, xyz, want_w=ctx.needs_input_grad[1], want_b=ctx.has_bias and ctx.needs_input_grad[2])
-            if ctx.needs_input_grad[1]:
-                dW = torch.cat((dwxyz, gemm(dP, x, False, False)), dim=1)
-        return dx, dW, db, None, None, None, None, None
-
-
-def interp_conv(x, W, b, xyz, nn3, B, N, G):
-    return InterpConvFn.apply(x, W, b, xyz, nn3, B, N, G)
-
-
+# ---- dense per-point prediction (csrc/seg.hip): log-softmax, weighted NLL, confusion matrix ------------------------------------------------
 class LogSoftmaxFn(torch.autograd.Function):
     """F.log_softmax over the last dim of rows [R,C], C <= 64"""
 
@@ -2558,26 +2446,44 @@ def grouping_operation(features, idx):
     return GroupingOperationFn.apply(features, idx)
 
 
-# ---- PointNet++ feature propagation at any size (csrc/sa.hip): general three-NN, adjacency, interpolation with skipped slots -------------------
-def three_nn_any(unknown, known, want_adj=True, want_d2=False):
+# ---- three-NN feature propagation (csrc/sa.hip): search, inverse adjacency, row interpolation with skipped slots -----------------------------
+def _sa_i32(t, name, shape=None, count=None):
+    """int32 (or int64, converted) CUDA operand ``name`` of the given shape or element count, made contiguous"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _C.ActHipError(f"{name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if t.dtype not in (torch.int32, torch.int64) or (shape is not None and tuple(t.shape) != tuple(shape)) or (
+            count is not None and t.numel() != count):
+        raise _C.ActHipError(f"{name}: expected int32 {list(shape) if shape is not None else '[%d entries]' % count}, got {t.dtype} {list(t.shape)}")
+    return _i32c(t)
+
+
+def _xyz_rows(xyz, name, R):
+    """xyz [R,3] or [B,N,3] with B * N == R -> contiguous [R,3]"""
+    xyz = _sa_f32(xyz, name, (None, None, 3) if isinstance(xyz, torch.Tensor) and xyz.dim() == 3 else (R, 3))
+    if xyz.numel() != 3 * R:
+        raise _C.ActHipError(f"{name}: expected 3 values for each of {R} rows, got {list(xyz.shape)}")
+    return xyz.view(R, 3)
+
+
+def three_nn(unknown, known, want_adj=True, want_d2=False):
     """unknown [B,n,3], known [B,m,3], any n >= 1 and m >= 1 -> (idx int32 [B,n,3], weight [B,n,3], adj_off int32 [B,m+1] | None, adj_ent int32
-    [B,3n] | None), plus d2 [B,n,3] with ``want_d2``: ``three_nn`` without the 3 <= G <= 512 limit, bit-identical to it where both apply.
-    m < 3: the missing slots carry idx 0, d2 = +inf and weight exactly 0 (the reference's S == 2 / S == 1 forms); ``interp_rows_any`` skips
-    them."""
-    unknown = _sa_f32(unknown, "three_nn_any: unknown", (None, None, 3))
+    [B,3n] | None), plus d2 [B,n,3] with ``want_d2``: the three nearest known points of every unknown point in ascending (difference-form
+    distance, index) order, their normalised inverse-distance weights (semantic_segmentation/models/pointnet2_utils.py:293-299) and the inverse
+    adjacency the interpolation backward gathers over.  m < 3: the missing slots carry idx 0, d2 = +inf and weight exactly 0 (the reference's
+    S == 2 / S == 1 forms); the interpolation skips them."""
+    unknown = _sa_f32(unknown, "three_nn: unknown", (None, None, 3))
     B, n, _ = unknown.shape
-    known = _sa_f32(known, "three_nn_any: known", (B, None, 3))
+    known = _sa_f32(known, "three_nn: known", (B, None, 3))
     m = known.shape[1]
     if B < 1 or n < 1 or m < 1:
-        raise _C.ActHipError(f"three_nn_any: unknown {list(unknown.shape)} / known {list(known.shape)} must not be empty")
+        raise _C.ActHipError(f"three_nn: unknown {list(unknown.shape)} / known {list(known.shape)} must not be empty")
     dev = unknown.device
     idx = torch.empty(B, n, 3, dtype=torch.int32, device=dev)
     w = torch.empty(B, n, 3, dtype=torch.float32, device=dev)
     d2 = torch.empty(B, n, 3, dtype=torch.float32, device=dev) if want_d2 else None
     off = torch.empty(B, m + 1, dtype=torch.int32, device=dev) if want_adj else None
     ent = torch.empty(B, 3 * n, dtype=torch.int32, device=dev) if want_adj else None
-    check(lib.act_three_nn_any_f32(ptr(unknown), ptr(known), B, n, m, ptr(idx), ptr(w), ptr(d2), ptr(off), ptr(ent), stream()),
-          "act_three_nn_any_f32")
+    check(lib.act_three_nn_f32(ptr(unknown), ptr(known), B, n, m, ptr(idx), ptr(w), ptr(d2), ptr(off), ptr(ent), stream()), "act_three_nn_f32")
     return (idx, w, off, ent, d2) if want_d2 else (idx, w, off, ent)
 
 
@@ -2597,61 +2503,115 @@ def three_adjacency(idx, m):
     return off, ent
 
 
-def interp_rows_any_fwd(P, idx, w, B, N, G):
-    """P [B*G,C], any C >= 1 -> Y [B*N,C] = sum over the slots of non-zero weight of w * P[idx]"""
-    P = _sa_f32(P, "interp_rows_any_fwd: P", (B * G, None))
-    w = _sa_f32(w, "interp_rows_any_fwd: weight", (B, N, 3))
-    if not isinstance(idx, torch.Tensor) or not idx.is_cuda or tuple(idx.shape) != (B, N, 3) or idx.dtype not in (torch.int32, torch.int64):
-        raise _C.ActHipError(f"interp_rows_any_fwd: idx: expected a CUDA int32 [{B}, {N}, 3]")
+def interp_rows_fwd(P, idx, w, B, N, G, xyz=None, wxyz=None, bias=None):
+    """P [B*G,C], any C >= 1 -> Y [B*N,C] = sum over the slots of non-zero weight of w * P[idx] (+ xyz . wxyz^T + bias)"""
+    P = _sa_f32(P, "interp_rows_fwd: P", (B * G, None))
+    w = _sa_f32(w, "interp_rows_fwd: weight", (B, N, 3))
+    idx = _sa_i32(idx, "interp_rows_fwd: idx", shape=(B, N, 3))
     C = P.shape[1]
     if B < 1 or N < 1 or G < 1 or C < 1:
-        raise _C.ActHipError("interp_rows_any_fwd: B, N, G and C must be >= 1")
-    idx = _i32c(idx)
+        raise _C.ActHipError("interp_rows_fwd: B, N, G and C must be >= 1")
+    if wxyz is not None:
+        xyz = _xyz_rows(xyz, "interp_rows_fwd: xyz", B * N)
+        wxyz = _sa_f32(wxyz, "interp_rows_fwd: wxyz", (C, 3))
+    if bias is not None:
+        bias = _sa_f32(bias, "interp_rows_fwd: bias", (C,))
     Y = torch.empty(B * N, C, dtype=torch.float32, device=P.device)
-    check(lib.act_interp_rows_any_fwd_f32(ptr(P), ptr(idx), ptr(w), B, N, G, C, ptr(Y), stream()), "act_interp_rows_any_fwd_f32")
+    check(lib.act_interp_rows_fwd_f32(ptr(P), ptr(idx), ptr(w), ptr(xyz) if wxyz is not None else None, ptr(wxyz), ptr(bias), B, N, G, C, ptr(Y),
+                                      stream()), "act_interp_rows_fwd_f32")
     return Y
 
 
-def interp_rows_any_bwd(dY, off, ent, w, B, N, G):
-    dY = _sa_f32(dY, "interp_rows_any_bwd: dY", (B * N, None))
-    w = _sa_f32(w, "interp_rows_any_bwd: weight", (B, N, 3))
-    for t, name, count in ((off, "adj_off", B * (G + 1)), (ent, "adj_ent", 3 * B * N)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _C.ActHipError(f"interp_rows_any_bwd: {name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
-        if t.dtype not in (torch.int32, torch.int64) or t.numel() != count:
-            raise _C.ActHipError(f"interp_rows_any_bwd: {name}: expected {count} int32 entries for B, N, G = {B}, {N}, {G}, got {t.dtype} "
-                                 f"{list(t.shape)}")
-    off, ent = _i32c(off), _i32c(ent)
+def interp_rows_bwd(dY, off, ent, w, B, N, G):
+    dY = _sa_f32(dY, "interp_rows_bwd: dY", (B * N, None))
+    w = _sa_f32(w, "interp_rows_bwd: weight", (B, N, 3))
+    off = _sa_i32(off, "interp_rows_bwd: adj_off", count=B * (G + 1))
+    ent = _sa_i32(ent, "interp_rows_bwd: adj_ent", count=3 * B * N)
     C = dY.shape[1]
     dP = torch.empty(B * G, C, dtype=torch.float32, device=dY.device)
-    check(lib.act_interp_rows_any_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_any_bwd_f32")
+    check(lib.act_interp_rows_bwd_f32(ptr(dY), ptr(off), ptr(ent), ptr(w), B, N, G, C, ptr(dP), stream()), "act_interp_rows_bwd_f32")
     return dP
 
 
-class InterpRowsAnyFn(torch.autograd.Function):
-    """InterpRowsFn at any G and C, with caller-supplied or kernel weights: x [B*G,C] -> [B*N,C].  Slots of weight exactly 0 are skipped in both
-    directions.  The backward gathers over the inverse adjacency (built here when ``nn3`` carries none): deterministic, bit-identical run to
-    run.  Indices and weights are constants: the cloud is a leaf."""
+def interp_xyz_grad(dY, xyz, want_w=True, want_b=True):
+    """-> (dY^T xyz [C,3] | None, column sums of dY [C] | None)"""
+    dY = _sa_f32(dY, "interp_xyz_grad: dY", (None, None))
+    R, C = dY.shape
+    xyz = _xyz_rows(xyz, "interp_xyz_grad: xyz", R)
+    dw = torch.empty(C, 3, dtype=torch.float32, device=dY.device) if want_w else None
+    db = torch.empty(C, dtype=torch.float32, device=dY.device) if want_b else None
+    ws = workspace(dY.device, lib.act_interp_xyz_grad_workspace(R, C))
+    check(lib.act_interp_xyz_grad_f32(ptr(dY), ptr(xyz), R, C, ptr(dw), ptr(db), ptr(ws), ws.numel() * 4, stream()), "act_interp_xyz_grad_f32")
+    return dw, db
+
+
+def _nn3_adjacency(idx, off, ent, G):
+    """the adjacency of ``nn3``, built here when the search was asked for none"""
+    return (off, ent) if off is not None else three_adjacency(idx, G)
+
+
+class InterpRowsFn(torch.autograd.Function):
+    """three-NN interpolation of per-known-point rows to the unknown points at any G and C, with caller-supplied or kernel weights: x [B*G,C] ->
+    [B*N,C] (pointnet2_utils.py:300).  Slots of weight exactly 0 are skipped in both directions.  The backward gathers over the inverse adjacency
+    (built here when ``nn3`` carries none): deterministic, bit-identical run to run.  Indices and weights are constants: the reference's distances
+    come from the input cloud, a leaf."""
 
     @staticmethod
     def forward(ctx, x, nn3, B, N, G):
         idx, w, off, ent = nn3
-        y = interp_rows_any_fwd(x, idx, w, B, N, G)
-        ctx.nn3 = (idx, w, off, ent)
+        y = interp_rows_fwd(x, idx, w, B, N, G)
+        ctx.save_for_backward(idx, w, off, ent)
         ctx.dims = (B, N, G)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        idx, w, off, ent = ctx.nn3
-        if off is None:
-            off, ent = three_adjacency(idx, ctx.dims[2])
-        return interp_rows_any_bwd(dy, off, ent, w, *ctx.dims), None, None, None, None
+        idx, w, off, ent = ctx.saved_tensors
+        off, ent = _nn3_adjacency(idx, off, ent, ctx.dims[2])
+        return interp_rows_bwd(dy, off, ent, w, *ctx.dims), None, None, None, None
 
 
-def interp_rows_any(x, nn3, B, N, G):
+def interp_rows(x, nn3, B, N, G):
     """x [B*G,C] rows of the known points, nn3 = (idx, weight, adj_off | None, adj_ent | None) -> [B*N,C]; differentiable in ``x``"""
-    return InterpRowsAnyFn.apply(x, nn3, B, N, G)
+    return InterpRowsFn.apply(x, nn3, B, N, G)
+
+
+class InterpConvFn(torch.autograd.Function):
+    """the first conv of PointNetFeaturePropagation on cat(xyz, interp(x)) in the per-group form: W [C, 3+K] (xyz columns first), x [B*G,K],
+    xyz [B*N,3].  P = x . W[:,3:]^T once per centre (B*G rows instead of B*N), then Y = sum_k w_k P[idx_k] + xyz . W[:,:3]^T + b in one kernel.
+    Equal in real arithmetic to the plain form W . cat(xyz, sum_k w_k x[idx_k]) + b (the weights enter linearly)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, xyz, nn3, B, N, G):
+        idx, w, off, ent = nn3
+        x = _f32c(x)
+        xyz = _xyz_rows(xyz, "interp_conv: xyz", B * N)
+        wf = W[:, 3:].contiguous()
+        wxyz = W[:, :3].contiguous()
+        P = gemm(x, wf, True, True)
+        y = interp_rows_fwd(P, idx, w, B, N, G, xyz=xyz, wxyz=wxyz, bias=b)
+        ctx.save_for_backward(x, wf, xyz, idx, w, off, ent)
+        ctx.dims = (B, N, G)
+        ctx.has_bias = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wf, xyz, idx, w, off, ent = ctx.saved_tensors
+        dy = _f32c(dy)
+        off, ent = _nn3_adjacency(idx, off, ent, ctx.dims[2])
+        dP = interp_rows_bwd(dy, off, ent, w, *ctx.dims)
+        dx = gemm(dP, wf, True, False) if ctx.needs_input_grad[0] else None
+        dW = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dwxyz, db = interp_xyz_grad(dy, xyz, want_w=ctx.needs_input_grad[1], want_b=ctx.has_bias and ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[1]:
+                dW = torch.cat((dwxyz, gemm(dP, x, False, False)), dim=1)
+        return dx, dW, db, None, None, None, None, None
+
+
+def interp_conv(x, W, b, xyz, nn3, B, N, G):
+    return InterpConvFn.apply(x, W, b, xyz, nn3, B, N, G)
 
 
 # ---- DGCNN classifier (csrc/edgeconv.hip): feature-space kNN, EdgeConv tail with BatchNorm, LeakyReLU row BatchNorm ------------------------------

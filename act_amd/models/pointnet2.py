@@ -160,7 +160,7 @@ class PointNetFeaturePropagationAny(nn.Module):
 
         forward(xyz1 [B,3,N], xyz2 [B,3,S], points1 [B,D1,N] or None, points2 [B,D2,S]) -> [B, mlp[-1], N]
 
-    Any N >= 1 and S >= 1: the three nearest of the S known points by K.three_nn_any (difference-form distances, ties to the lower index),
+    Any N >= 1 and S >= 1: the three nearest of the S known points by K.three_nn (difference-form distances, ties to the lower index),
     inverse-distance weights normalised over the slots that exist (S == 2: two columns; S == 1: the single row repeated), then the MLP on
     cat(points1, interpolated) as rows with train-mode BatchNorm over all B*N rows.  The weights are constants: the cloud is a leaf."""
 
@@ -190,8 +190,8 @@ class PointNetFeaturePropagationAny(nn.Module):
         S = x2.shape[1]
         if x2.shape[0] != B:
             raise _C.ActHipError(f"{name}: xyz2: expected {B} clouds, got {x2.shape[0]}")
-        nn3 = K.three_nn_any(x1, x2, want_adj=torch.is_grad_enabled() and p2.requires_grad)
-        rows = K.interp_rows_any(p2.reshape(B * S, D2), nn3, B, N, S)
+        nn3 = K.three_nn(x1, x2, want_adj=torch.is_grad_enabled() and p2.requires_grad)
+        rows = K.interp_rows(p2.reshape(B * S, D2), nn3, B, N, S)
         if p1 is not None:
             rows = torch.cat((p1.reshape(B * N, D1), rows), dim=1)
         rows = _chain(rows, self.mlp_convs, self.mlp_bns, self.training)

@@ -143,7 +143,7 @@ def three_nn(unknown, known):
     if unknown.shape[0] < 1 or unknown.shape[1] < 1 or known.shape[1] < 1:
         raise ValueError(f"three_nn: unknown {list(unknown.shape)} / known {list(known.shape)} must not be empty")
     _need(unknown, torch.float32, "unknown"); _need(known, torch.float32, "known")
-    idx, _, _, _, d2 = K.three_nn_any(unknown, known, want_adj=False, want_d2=True)
+    idx, _, _, _, d2 = K.three_nn(unknown, known, want_adj=False, want_d2=True)
     return torch.sqrt(d2), idx
 
 
@@ -168,7 +168,7 @@ class ThreeInterpolate(torch.autograd.Function):
         if B < 1 or C < 1 or m < 1 or n < 1:
             raise ValueError(f"three_interpolate: features {list(features.shape)} / idx {list(idx.shape)} must not be empty")
         rows = features.transpose(1, 2).reshape(B * m, C)
-        out = K.interp_rows_any_fwd(rows, idx, weight, B, n, m)
+        out = K.interp_rows_fwd(rows, idx, weight, B, n, m)
         ctx.save_for_backward(idx, weight)
         ctx.dims = (B, n, m)
         return out.view(B, n, C).transpose(1, 2).contiguous()
@@ -180,7 +180,7 @@ class ThreeInterpolate(torch.autograd.Function):
         B, n, m = ctx.dims
         C = grad_out.shape[1]
         off, ent = K.three_adjacency(idx, m)
-        d = K.interp_rows_any_bwd(grad_out.transpose(1, 2).reshape(B * n, C), off, ent, weight, B, n, m)
+        d = K.interp_rows_bwd(grad_out.transpose(1, 2).reshape(B * n, C), off, ent, weight, B, n, m)
         return d.view(B, m, C).transpose(1, 2).contiguous(), None, None
 
 

@@ -1,18 +1,16 @@
 #!/usr/bin/env python3
-"""PointNet++ feature propagation at any size and the three PointNet++ networks (csrc/sa.hip, models/pointnet2.py, models/pointnet2_nets.py):
+"""Three-NN feature propagation and the three PointNet++ networks (csrc/sa.hip, models/pointnet2.py, models/pointnet2_nets.py):
 one JSON line.
 
     python benchmarks/fp_bench.py [--reps 10] [--commit ID] [--out FILE]        # FILE defaults to profiles/fp_bench.json
 
 Clouds uniform in the unit ball, the known points by FPS.  Device-event medians (with min / max) of ``--reps`` repetitions after a warm-up:
-  * the general search (K.three_nn_any, no adjacency) at 32 x 2,048 <- 512, 32 x 4,096 <- 1,024 and 16 x 8,192 <- 2,048, against the
+  * the search (K.three_nn, without and with the adjacency) at 32 x 2,048 <- 512, 32 x 4,096 <- 1,024 and 16 x 8,192 <- 2,048, against the
     torch formulation of the same search on the same device (pairwise difference-form distances, a full sort, the first three) -- the index
     sets agree;
-  * the search at 32 x 2,048 <- 128 against act_three_nn_f32 (K.three_nn), medians of 5 in one session, with and without the adjacency;
   * one PointNetFeaturePropagationAny layer (32 x 2,048 <- 512, D1 = 128, D2 = 256, mlp [256, 128]) forward + backward;
   * one training step (forward, loss, backward) of each network at its published sizes: the classifier on 32 x 1,024 points, the part
     segmentation network on 16 x 2,048, the semantic segmentation network on 16 x 4,096 x 9 channels.
-The capability is new, so there is no earlier time of this project to compare with.
 
 Rate.  A distance test is one (unknown, known) distance and its insertion compare.  ``tests_per_s`` is B * n * m over the search time;
 notebook/fp.md sets it against the vector-issue model of the ball query (notebook/sa.md).
@@ -49,27 +47,15 @@ def clouds(B, n, m, pu, dev):
 
 def search(B, n, m, reps, K, pu, dev):
     u, k = clouds(B, n, m, pu, dev)
-    idx = K.three_nn_any(u, k, want_adj=False)[0]
+    idx = K.three_nn(u, k, want_adj=False)[0]
     same = bool(torch.equal(idx.long().sort(-1)[0], torch_sort_search(u, k)[1].sort(-1)[0]))
-    t = timed(lambda: K.three_nn_any(u, k, want_adj=False), reps)
-    t_adj = timed(lambda: K.three_nn_any(u, k), reps)
+    t = timed(lambda: K.three_nn(u, k, want_adj=False), reps)
+    t_adj = timed(lambda: K.three_nn(u, k), reps)
     t_sort = timed(lambda: torch_sort_search(u, k), max(2, reps // 3))
     per_s = B * n * m / (statistics.median(t) * 1e-3)
-    return {"B": B, "n": n, "m": m, "three_nn_any_ms": spread(t), "with_adjacency_ms": spread(t_adj), "torch_sort_ms": spread(t_sort, 3),
+    return {"B": B, "n": n, "m": m, "three_nn_ms": spread(t), "with_adjacency_ms": spread(t_adj), "torch_sort_ms": spread(t_sort, 3),
             "same_index_sets_as_torch": same, "speedup_over_torch_sort": round(statistics.median(t_sort) / statistics.median(t), 1),
             "tests_per_s": float("%.4g" % per_s)}
-
-
-def against_three_nn(K, pu, dev):
-    B, n, m = 32, 2048, 128
-    u, k = clouds(B, n, m, pu, dev)
-    a, b = K.three_nn(u, k), K.three_nn_any(u, k)
-    same = all(torch.equal(x, y) for x, y in zip(a, b))
-    return {"B": B, "n": n, "m": m, "reps": 5, "bit_identical": bool(same),
-            "three_nn_ms": spread(timed(lambda: K.three_nn(u, k, want_adj=False), 5)),
-            "three_nn_any_ms": spread(timed(lambda: K.three_nn_any(u, k, want_adj=False), 5)),
-            "three_nn_with_adjacency_ms": spread(timed(lambda: K.three_nn(u, k), 5)),
-            "three_nn_any_with_adjacency_ms": spread(timed(lambda: K.three_nn_any(u, k), 5))}
 
 
 def fp_layer(reps, P, pu, dev):
@@ -135,7 +121,6 @@ def main():
     dev = torch.device("cuda:0")
     res = {"workload": "feature_propagation", "commit": args.commit, "reps": args.reps,
            "search": [search(*shape, args.reps, K, pu, dev) for shape in SEARCH_SHAPES],
-           "against_three_nn": against_three_nn(K, pu, dev),
            "fp_layer": fp_layer(args.reps, P, pu, dev),
            "networks": network_steps(args.reps, K, M, dev)}
     line = json.dumps(res)

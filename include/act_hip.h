@@ -718,26 +718,8 @@ typedef struct {
 int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
                                  float* workspace, size_t workspace_bytes, act_stream_t stream);
 
-/* ---- dense per-point prediction (semantic segmentation head; csrc/seg.hip) --------------------------------------------------
- * semantic_segmentation/models/pointnet2_utils.py:262-315 (PointNetFeaturePropagation) and models/pt.py (log_softmax, nll_loss).
- * Three nearest centres of every point: xyz [B,N,3], centers [B,G,3] (3 <= G <= 512) -> idx int32 [B,N,3] in ascending (distance, index) order
- * (ties: lower index), weight [B,N,3] = (1/(d+1e-8)) / sum.  d is the DIFFERENCE form (dx*dx+dy*dy)+dz*dz in fp32 without FMA (the reference
- * uses the expansion form).  adj_off int32 [B,G+1] / adj_ent int32 [B,3N] (both or neither): per cloud, the entries e = 3n+k that
- * chose centre g, in increasing e, at adj_ent[off[g] .. off[g+1]) -- the inverse adjacency of the interpolation backward (counting sort). */
-int act_three_nn_f32(const float* xyz, const float* centers, int B, int N, int G, int32_t* idx, float* weight, int32_t* adj_off,
-                     int32_t* adj_ent, act_stream_t stream);
-/* Y [B*N,C] = sum_k weight[n,k] * P[b*G + idx[n,k], :]  (+ xyz[n] . wxyz[c,:] if wxyz, wxyz [C,3]; + bias[c] if bias).  C % 4 == 0, P / Y / bias
- * 16-byte aligned. */
-int act_interp_rows_fwd_f32(const float* P, const int32_t* idx, const float* weight, const float* xyz, const float* wxyz, const float* bias,
-                            int B, int N, int G, int C, float* Y, act_stream_t stream);
-/* dP [B*G,C] = sum over the adjacency of centre g (increasing e) of weight[e] * dY[b*N + e/3, :]: a gather, bit-identical run to run. */
-int act_interp_rows_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
-                            float* dP, act_stream_t stream);
-/* dwxyz [C,3] = dY^T xyz, dbias [C] = column sums of dY (either may be NULL); dY [R,C], xyz [R,3]; per-block partials + one ordered pass. */
-size_t act_interp_xyz_grad_workspace(long long R, int C);
-int act_interp_xyz_grad_f32(const float* dY, const float* xyz, long long R, int C, float* dwxyz, float* dbias, float* workspace,
-                            size_t workspace_bytes, act_stream_t stream);
-/* row log-softmax [R,C] (C <= 64) and its backward dz = dout - exp(logp) * rowsum(dout) */
+/* ---- dense per-point prediction (semantic segmentation head; csrc/seg.hip; models/pt.py log_softmax, nll_loss) -----------------
+ * row log-softmax [R,C] (C <= 64) and its backward dz = dout - exp(logp) * rowsum(dout) */
 int act_log_softmax_fwd_f32(const float* z, long long R, int C, float* out, act_stream_t stream);
 int act_log_softmax_bwd_f32(const float* logp, const float* dout, long long R, int C, float* dz, act_stream_t stream);
 /* F.nll_loss(logp, target, weight) (weighted mean; weight NULL = ones): loss[0], wsum[0] = sum of w[t], correct[0] (int64, may be NULL) = rows whose
@@ -1035,22 +1017,31 @@ int act_group_gather_f32(const float* features, const int32_t* idx, int B, int C
 int act_group_gather_bwd_f32(const float* dout, const int32_t* idx, int B, int C, int N, int S, int nsample, float* dfeatures, void* workspace,
                              size_t workspace_bytes, act_stream_t stream);
 
-/* ---- PointNet++ feature propagation at any size (csrc/sa.hip; reference models/pointnet2_utils.py:262-312, upstream three_nn / three_interpolate) ----
+/* ---- three-NN feature propagation (csrc/sa.hip; reference models/pointnet2_utils.py:262-312, upstream three_nn / three_interpolate; the
+ * PointNet++ networks and the Transformer segmentation head) ----
  * unknown [B,n,3], known [B,m,3], n >= 1, m >= 1, B <= 65535 -> idx int32 [B,n,3], weight fp32 [B,n,3], d2 fp32 [B,n,3] (may be NULL): the three
- * nearest known points in ascending (difference-form distance, index) order, equal distances to the lower index, and the weights
- * r_k / ((r0 + r1) + r2), r_k = 1 / (d2_k + 1e-8).  Slots past m (m < 3) get idx 0, d2 +inf and weight exactly 0.  At 3 <= m <= 512 every
- * output equals act_three_nn_f32's bit for bit.  adj_off int32 [B,m+1] / adj_ent int32 [B,3n] (both or neither): per known point the entries
- * 3 * unknown + slot that name it, ascending, built without atomics (count, exclusive scan, fill). */
-int act_three_nn_any_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2, int32_t* adj_off,
-                         int32_t* adj_ent, act_stream_t stream);
+ * nearest known points in ascending (distance, index) order, equal distances to the lower index, and the weights r_k / ((r0 + r1) + r2),
+ * r_k = 1 / (d2_k + 1e-8).  d2 is the DIFFERENCE form (dx*dx+dy*dy)+dz*dz in fp32 without FMA (the reference uses the expansion form).
+ * Slots past m (m < 3) get idx 0, d2 +inf and weight exactly 0.  adj_off int32 [B,m+1] / adj_ent int32 [B,3n] (both or neither): per known point
+ * g the entries e = 3 * unknown + slot that name it, ascending, at adj_ent[off[g] .. off[g+1]) -- the inverse adjacency of the interpolation
+ * backward, a counting sort without atomics (one launch at m <= 256, the grouping backward's three-launch builder above that: same lists). */
+int act_three_nn_f32(const float* unknown, const float* known, int B, int n, int m, int32_t* idx, float* weight, float* d2, int32_t* adj_off,
+                     int32_t* adj_ent, act_stream_t stream);
 /* the same adjacency of caller-supplied indices idx int32 [B,n,3]; an index outside [0,m) is in no list */
 int act_three_adj_i32(const int32_t* idx, int B, int n, int m, int32_t* adj_off, int32_t* adj_ent, act_stream_t stream);
-/* Y [B*N,C] = sum_k weight[.,k] * P[b*G + idx[.,k], :] over the slots with weight != 0 and idx in [0,G): a skipped slot is not read.  Any C >= 1
- * (float4 lanes when C % 4 == 0 and the rows are 16-byte aligned).  The backward gathers dP [B*G,C] over the adjacency in ascending entry
- * order, skipping entries of weight 0: bit-identical run to run.  B*N and B*G <= 2^27 rows (row blocks on grid.x), C <= 64 * 65535. */
-int act_interp_rows_any_fwd_f32(const float* P, const int32_t* idx, const float* weight, int B, int N, int G, int C, float* Y, act_stream_t stream);
-int act_interp_rows_any_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
-                                float* dP, act_stream_t stream);
+/* Y [B*N,C] = sum_k weight[.,k] * P[b*G + idx[.,k], :] over the slots with weight != 0 and idx in [0,G): a skipped slot is not read;
+ * then + xyz[n] . wxyz[c,:] if wxyz (xyz [B*N,3], wxyz [C,3]) and + bias[c] if bias.  Any C >= 1 (float4 lanes when C % 4 == 0 and P, Y and bias
+ * are 16-byte aligned).  B*N <= 2^27 rows (a one-dimensional grid of row blocks). */
+int act_interp_rows_fwd_f32(const float* P, const int32_t* idx, const float* weight, const float* xyz, const float* wxyz, const float* bias,
+                            int B, int N, int G, int C, float* Y, act_stream_t stream);
+/* dP [B*G,C] = sum over the adjacency of known point g (increasing e) of weight[e] * dY[b*N + e/3, :], skipping entries of weight 0: a gather,
+ * bit-identical run to run.  B*G <= 2^27 rows and row blocks (of 4) x channel blocks (of 64 lanes) <= 2^31 - 1. */
+int act_interp_rows_bwd_f32(const float* dY, const int32_t* adj_off, const int32_t* adj_ent, const float* weight, int B, int N, int G, int C,
+                            float* dP, act_stream_t stream);
+/* dwxyz [C,3] = dY^T xyz, dbias [C] = column sums of dY (either may be NULL); dY [R,C], xyz [R,3]; per-block partials + one ordered pass. */
+size_t act_interp_xyz_grad_workspace(long long R, int C);
+int act_interp_xyz_grad_f32(const float* dY, const float* xyz, long long R, int C, float* dwxyz, float* dbias, float* workspace,
+                            size_t workspace_bytes, act_stream_t stream);
 
 /* ---- DGCNN classifier (csrc/edgeconv.hip; Wang et al. 2019) ----------------------------------------------------------------------------
  * Batched Euclidean kNN in feature space: x fp32 [B,N,C] -> idx int32 [B,N,k], d2 fp32 [B,N,k] (may be NULL): for every point of a cloud

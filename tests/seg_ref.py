@@ -1,5 +1,6 @@
-"""numpy references for the dense-prediction kernels (csrc/seg.hip; not a test itself).  ``three_nn_f32`` restates the three-NN kernel and its
-inverse adjacency operation for operation in float32, so every output is expected bit for bit.  The other functions are float64 references of
+"""numpy references for the dense-prediction kernels (csrc/seg.hip and the three-NN feature propagation of csrc/sa.hip; not a test itself).
+``three_nn_f32`` restates the three-NN kernel and its inverse adjacency operation for operation in float32, so every output is expected bit
+for bit (tests/fp_ref.py restates the same kernel independently; tests/test_fp_host.py holds the two to each other).  The other functions are float64 references of
 the float32 inputs the device gets; each also returns the componentwise sum of absolute values of the terms it adds, which is what a rounding
 bound of a float32 summation is proportional to.  Rows whose target lies outside [0, C) are ignored."""
 import numpy as np
@@ -38,18 +39,19 @@ def adjacency(idx, G):
 def three_nn_f32(xyz, ctr):
     """xyz float32 [B, N, 3], ctr float32 [B, G, 3] -> (idx int32 [B,N,3], w float32 [B,N,3], off int32 [B,G+1], ent int32 [B,3N], d float32
     [B,N,3]).  Selection: the first three of a stable argsort over increasing centre index (the kernel's strict '<' insertion keeps the lower
-    index among equal distances).  Weights: r = 1 / (d + 1e-8f), s = (r0 + r1) + r2, w = r / s, every operation rounded to float32."""
+    index among equal distances).  Weights: r = 1 / (d + 1e-8f), s = (r0 + r1) + r2, w = r / s, every operation rounded to float32.
+    G < 3: the kernel's registers of the slots that never fill stay at idx 0 and d = +inf, so r = 1 / inf = 0 and w = 0 exactly."""
     xyz = np.asarray(xyz, dtype=np.float32)
     ctr = np.asarray(ctr, dtype=np.float32)
     B, N, _ = xyz.shape
     G = ctr.shape[1]
     idx = np.zeros((B, N, 3), np.int32)
-    d3 = np.zeros((B, N, 3), np.float32)
+    d3 = np.full((B, N, 3), np.inf, np.float32)
     for b in range(B):
         d = sqdist_f32(xyz[b], ctr[b])
         o = np.argsort(d, axis=-1, kind="stable")[:, :3]
-        idx[b] = o
-        d3[b] = np.take_along_axis(d, o, -1)
+        idx[b, :, :o.shape[1]] = o
+        d3[b, :, :o.shape[1]] = np.take_along_axis(d, o, -1)
     one, eps = np.float32(1.0), np.float32(1e-8)
     r = one / (d3 + eps)
     s = (r[..., 0] + r[..., 1]) + r[..., 2]

@@ -14,7 +14,7 @@ from tests.golden.fill import fill_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-4
-SYMBOLS = ("act_three_nn_any_f32", "act_three_adj_i32", "act_interp_rows_any_fwd_f32", "act_interp_rows_any_bwd_f32")
+SYMBOLS = ("act_three_nn_f32", "act_three_adj_i32", "act_interp_rows_fwd_f32", "act_interp_rows_bwd_f32")
 CASES = {"s16": (16, True), "s16np": (16, False), "s2": (2, True), "s1": (1, True)}
 
 
@@ -59,6 +59,24 @@ def test_three_nn_ref_agrees_with_seg_ref_and_the_fixture_has_no_third_fourth_ti
     d64 = ((u[:, :, None, :].astype(np.float64) - k[:, None, :, :].astype(np.float64)) ** 2).sum(-1)      # the lattice: float32 is exact
     kk = min(3, k.shape[1])
     assert np.array_equal(np.sort(d64, axis=-1)[:, :, :kk], d2[:, :, :kk].astype(np.float64))
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 64, 128, 512])
+def test_the_two_restatements_of_the_search_agree_bit_for_bit(m):
+    """tests/seg_ref.py and tests/fp_ref.py restate ONE kernel family independently (the GPU files of the Transformer head and of the PointNet++
+    networks each hold it to their own): idx, weights, distances, off and ent are the same on the lattice (ties) and on a float cloud (the
+    weights' arithmetic order), at the sizes where two kernels used to be compared on the device and at m < 3 (idx 0 / d2 inf / weight 0)"""
+    from tests import seg_ref as GR
+    rs = np.random.RandomState(50 + m)
+    for u, k in (R.lattice_pair(rs, 2, 700, m), (rs.uniform(-1, 1, (2, 700, 3)).astype(np.float32), rs.uniform(-1, 1, (2, m, 3)).astype(np.float32))):
+        idx, w, d2 = R.three_nn(u, k)
+        off, ent = R.adjacency(idx, m)
+        i2, w2, off2, ent2, d3 = GR.three_nn_f32(u, k)
+        assert i2.dtype == idx.dtype and w2.dtype == w.dtype == np.float32
+        assert np.array_equal(idx, i2) and np.array_equal(w.view(np.int32), w2.view(np.int32)) and np.array_equal(d2.view(np.int32), d3.view(np.int32))
+        assert np.array_equal(off, off2) and np.array_equal(ent, ent2)
+        if m < 3:
+            assert (i2[..., m:] == 0).all() and np.isinf(d3[..., m:]).all() and (w2[..., m:] == 0).all()
 
 
 def test_adjacency_ref_lists_every_entry_once_in_ascending_order():
@@ -158,7 +176,7 @@ def test_upstream_ops_check_shapes_dtypes_and_devices():
     with pytest.raises(RuntimeError, match="unknown"):
         pu.three_nn(u, k)                                               # CPU tensors
     with pytest.raises(RuntimeError, match="unknown"):
-        K.three_nn_any(u, k)
+        K.three_nn(u, k)
     feats, idx, w = torch.zeros(2, 5, 4), torch.zeros(2, 8, 3, dtype=torch.int32), torch.zeros(2, 8, 3)
     with pytest.raises(ValueError, match="features"):
         pu.three_interpolate(feats[0], idx, w)

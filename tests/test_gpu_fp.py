@@ -1,11 +1,12 @@
-"""GPU: PointNet++ feature propagation at any size -- the general three-NN search, its inverse adjacency and the interpolation with skipped
-slots (csrc/sa.hip), the upstream-form ops over them, ``PointNetFeaturePropagationAny`` against the reference's recorded run
+"""GPU: three-NN feature propagation at any size -- the search, its inverse adjacency and the interpolation with skipped slots (csrc/sa.hip),
+the upstream-form ops over them, ``PointNetFeaturePropagationAny`` against the reference's recorded run
 (tests/golden/g26_fp.npz), the three PointNet++ networks against their float64 restatement (tests/fp_ref.py) and the runners' model switch.
 
 The search is compared index for index and bit for bit: the clouds sit on the 1/8 lattice, where every squared distance is exact in float32,
 so the restatement (checked on the host against the reference's run and against tests/seg_ref.py) is an exact oracle, duplicated points and
 equal distances included.  Sizes: one lane per unknown point in blocks of 256 (n = 255, 256, 257), the known cloud in LDS tiles of 1024 points
-(m one below, at, one above a tile, and past two tiles), the m < 3 forms, and the sizes at which act_three_nn_f32 must be matched bit for bit."""
+(m one below, at, one above a tile, and past two tiles), the m < 3 forms, and m on both sides of the switch between the two adjacency builders
+(one launch at m <= 256, three launches above; m = 512 / 513 straddled the former limit of the Transformer head's search)."""
 import copy
 import re
 
@@ -62,30 +63,32 @@ def _bits(t):
 
 
 def _check_search(K, dev, u, k):
-    """idx, d2, weights and adjacency of K.three_nn_any equal to the restatement, bit for bit; the pieces on request agree with the full call"""
+    """idx, d2, weights and adjacency of K.three_nn equal to the restatement, bit for bit; the pieces on request agree with the full call"""
     m = k.shape[1]
     idx, w, d2 = R.three_nn(u, k)
     off, ent = R.adjacency(idx, m)
-    got = K.three_nn_any(_d(u, dev), _d(k, dev), want_adj=True, want_d2=True)
+    got = K.three_nn(_d(u, dev), _d(k, dev), want_adj=True, want_d2=True)
     assert [t.dtype for t in got] == [torch.int32, torch.float32, torch.int32, torch.int32, torch.float32]
     assert torch.equal(got[0].cpu(), torch.from_numpy(idx))
     assert torch.equal(_bits(got[4]), _bits(torch.from_numpy(d2)))
     assert torch.equal(_bits(got[1]), _bits(torch.from_numpy(w)))
     assert torch.equal(got[2].cpu(), torch.from_numpy(off)) and torch.equal(got[3].cpu(), torch.from_numpy(ent))
-    lean = K.three_nn_any(_d(u, dev), _d(k, dev), want_adj=False)
+    lean = K.three_nn(_d(u, dev), _d(k, dev), want_adj=False)
     assert len(lean) == 4 and lean[2] is None and lean[3] is None and torch.equal(lean[0], got[0]) and torch.equal(_bits(lean[1]), _bits(got[1]))
     return idx, w, d2, off, ent
 
 
 # ---- the search ---------------------------------------------------------------------------------------------------------------------------------
-SEARCH_CASES = [(1, 1), (5, 2), (7, 3), (300, 4), (257, 64), (1000, 512), (1000, 513), (70, TILE - 1), (70, TILE), (70, TILE + 1),
-                (70, 2 * TILE + 52), (255, 20), (256, 20), (257, 20)]
+SEARCH_CASES = [(1, 1), (5, 2), (7, 3), (300, 4), (257, 64), (1000, 256), (1000, 257), (5, 256), (5, 257), (1000, 512), (1000, 513), (5, 512), (5, 513),
+                (70, TILE - 1), (70, TILE), (70, TILE + 1), (70, 2 * TILE + 52), (255, 20), (256, 20), (257, 20)]
 
 
 @pytest.mark.parametrize("n,m", SEARCH_CASES)
 def test_three_nn_any_equals_the_restatement(K, dev, n, m):
     """B = 3 different clouds on the 1/8 lattice in [-1, 1] (4,913 sites: at m >= 1,000 most sites are taken more than once, so equal
-    distances and duplicated known points are everywhere)"""
+    distances and duplicated known points are everywhere).  m = 256 / 257 straddle the two adjacency builders, which must give the same lists:
+    the one-launch kernel up to 256 known points, the grouping backward's three-launch builder above (m = 512 / 513: one and two full blocks of
+    it, and the former limit of the Transformer head's search); at n = 5 most lists are empty"""
     rs = np.random.RandomState(1000 * n + m)
     u, k = R.lattice_pair(rs, 3, n, m)
     idx, w, d2, _, _ = _check_search(K, dev, u, k)
@@ -109,16 +112,6 @@ def test_three_nn_any_duplicates_and_coincident_points(K, dev):
     assert not np.isin(idx[..., 0], [2, 4, 5]).any()                    # a duplicate is never the nearest: its lower twin is
 
 
-@pytest.mark.parametrize("m", [3, 64, 128, 512])
-def test_three_nn_any_is_bit_identical_to_three_nn(K, dev, m):
-    """where both kernels apply every output is the same: on the lattice (ties) and on a float cloud (the weights' arithmetic order)"""
-    rs = np.random.RandomState(50 + m)
-    for u, k in (R.lattice_pair(rs, 2, 700, m), (rs.uniform(-1, 1, (2, 700, 3)).astype(np.float32), rs.uniform(-1, 1, (2, m, 3)).astype(np.float32))):
-        a = K.three_nn(_d(u, dev), _d(k, dev))
-        b = K.three_nn_any(_d(u, dev), _d(k, dev))
-        assert torch.equal(a[0], b[0]) and torch.equal(_bits(a[1]), _bits(b[1])) and torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])
-
-
 def test_three_nn_any_on_a_random_float_cloud(K, dev):
     """no lattice: the index SETS equal those of a float64 ranking, leaving out the rows whose third and fourth float64 distances lie within
     a relative 1e-6; at most 1 % of the rows may be left out"""
@@ -131,7 +124,7 @@ def test_three_nn_any_on_a_random_float_cloud(K, dev):
     unsafe = (ds[..., 3] - ds[..., 2]) <= 1e-6 * ds[..., 3]
     print("[fp] random cloud: %d of %d rows excluded" % (unsafe.sum(), unsafe.size))
     assert unsafe.mean() <= 0.01
-    idx = K.three_nn_any(_d(u, dev), _d(k, dev), want_adj=False)[0].cpu().numpy()
+    idx = K.three_nn(_d(u, dev), _d(k, dev), want_adj=False)[0].cpu().numpy()
     assert np.array_equal(np.sort(idx, -1)[~unsafe], np.sort(o[..., :3], -1)[~unsafe])
 
 
@@ -206,7 +199,7 @@ def test_interpolation_with_the_kernel_weights(K, pu, dev):
     dist, idx = pu.three_nn(_d(u, dev), _d(k, dev))
     ri, rw, rd2 = R.three_nn(u, k)
     assert torch.equal(idx.cpu(), torch.from_numpy(ri)) and torch.allclose(dist.cpu(), torch.sqrt(torch.from_numpy(rd2)), rtol=3e-7, atol=0)
-    w = K.three_nn_any(_d(u, dev), _d(k, dev), want_adj=False)[1]
+    w = K.three_nn(_d(u, dev), _d(k, dev), want_adj=False)[1]
     runs = []
     for _ in range(2):
         f = _d(feats, dev).requires_grad_(True)
@@ -221,9 +214,9 @@ def test_interpolation_with_the_kernel_weights(K, pu, dev):
     print("[fp] interpolation with kernel weights: forward %.3e, backward %.3e of the largest magnitude" % (ef, eb))
     assert ef <= 2e-7 and eb <= 2e-7
     # the row form that the module uses: the same numbers, through the adjacency of the search
-    nn3 = K.three_nn_any(_d(u, dev), _d(k, dev))
+    nn3 = K.three_nn(_d(u, dev), _d(k, dev))
     rows = _d(np.ascontiguousarray(feats.transpose(0, 2, 1)).reshape(B * m, C), dev).requires_grad_(True)
-    y = K.interp_rows_any(rows, nn3, B, n, m)
+    y = K.interp_rows(rows, nn3, B, n, m)
     (gr,) = torch.autograd.grad(y, rows, _d(np.ascontiguousarray(cot.transpose(0, 2, 1)).reshape(B * n, C), dev))
     assert torch.equal(_bits(y.view(B, n, C).transpose(1, 2)), _bits(runs[0][0]))
     assert torch.equal(_bits(gr.view(B, m, C).transpose(1, 2)), _bits(runs[0][1]))
@@ -238,11 +231,11 @@ def test_single_and_double_known_points(K, pu, dev):
     k = rs.standard_normal((B, 3, 3)).astype(np.float32)
     feats = rs.standard_normal((B, C, 3)).astype(np.float32)
     d1, i1 = pu.three_nn(_d(u, dev), _d(k[:, :1], dev))
-    w1 = K.three_nn_any(_d(u, dev), _d(k[:, :1], dev), want_adj=False)[1]
+    w1 = K.three_nn(_d(u, dev), _d(k[:, :1], dev), want_adj=False)[1]
     assert (i1 == 0).all() and torch.isinf(d1[..., 1:]).all() and (w1[..., 0] == 1).all() and (w1[..., 1:] == 0).all()
     out = pu.three_interpolate(_d(feats[:, :, :1], dev), i1, w1)
     assert torch.equal(_bits(out), _bits(_d(feats[:, :, :1], dev).expand(B, C, n)))
-    i2, w2, _, _ = K.three_nn_any(_d(u, dev), _d(k[:, :2], dev), want_adj=False)
+    i2, w2, _, _ = K.three_nn(_d(u, dev), _d(k[:, :2], dev), want_adj=False)
     assert (w2[..., 2] == 0).all() and (i2[..., 2] == 0).all() and torch.allclose(w2.sum(-1), torch.ones(B, n, device=dev), atol=1e-6)
     base = pu.three_interpolate(_d(feats[:, :, :2], dev), i2, w2)
     poisoned = feats.copy()
@@ -421,15 +414,15 @@ def test_argument_checks(K, pu, dev):
     from act_amd.models import pointnet2 as P
     u, k = torch.zeros(2, 8, 3, device=dev), torch.zeros(2, 4, 3, device=dev)
     with pytest.raises(RuntimeError, match="unknown"):
-        K.three_nn_any(u[0], k)                                         # wrong rank
+        K.three_nn(u[0], k)                                             # wrong rank
     with pytest.raises(RuntimeError, match="known"):
-        K.three_nn_any(u, k[:1])                                        # mismatched B
+        K.three_nn(u, k[:1])                                            # mismatched B
     with pytest.raises(RuntimeError, match="empty"):
-        K.three_nn_any(u, k[:, :0])                                     # m = 0
+        K.three_nn(u, k[:, :0])                                         # m = 0
     with pytest.raises(RuntimeError, match="known"):
-        K.three_nn_any(u, k.cpu())
+        K.three_nn(u, k.cpu())
     with pytest.raises(RuntimeError, match="float32"):
-        K.three_nn_any(u.double(), k)
+        K.three_nn(u.double(), k)
     with pytest.raises(ValueError, match="empty"):
         pu.three_nn(u, k[:, :0])
     with pytest.raises(RuntimeError, match="contiguous"):
@@ -438,12 +431,12 @@ def test_argument_checks(K, pu, dev):
     idx = torch.full((2, 8, 3), -7, dtype=torch.int32, device=dev)
     w = torch.full((2, 8, 3), -7.0, device=dev)
     lib, ptr, st = _C.lib, _C.ptr, _C.stream()
-    assert lib.act_three_nn_any_f32(ptr(u), ptr(k), 2, 8, 0, ptr(idx), ptr(w), None, None, None, st) != 0
-    assert lib.act_three_nn_any_f32(ptr(u), ptr(k), 0, 8, 4, ptr(idx), ptr(w), None, None, None, st) != 0
-    assert lib.act_three_nn_any_f32(ptr(u), None, 2, 8, 4, ptr(idx), ptr(w), None, None, None, st) != 0
+    assert lib.act_three_nn_f32(ptr(u), ptr(k), 2, 8, 0, ptr(idx), ptr(w), None, None, None, st) != 0
+    assert lib.act_three_nn_f32(ptr(u), ptr(k), 0, 8, 4, ptr(idx), ptr(w), None, None, None, st) != 0
+    assert lib.act_three_nn_f32(ptr(u), None, 2, 8, 4, ptr(idx), ptr(w), None, None, None, st) != 0
     off = torch.full((2, 5), -7, dtype=torch.int32, device=dev)
-    assert lib.act_three_nn_any_f32(ptr(u), ptr(k), 2, 8, 4, ptr(idx), ptr(w), None, ptr(off), None, st) != 0       # half an adjacency
-    assert lib.act_interp_rows_any_fwd_f32(ptr(w), ptr(idx), ptr(w), 2, 8, 4, 0, ptr(w), st) != 0
+    assert lib.act_three_nn_f32(ptr(u), ptr(k), 2, 8, 4, ptr(idx), ptr(w), None, ptr(off), None, st) != 0       # half an adjacency
+    assert lib.act_interp_rows_fwd_f32(ptr(w), ptr(idx), ptr(w), None, None, None, 2, 8, 4, 0, ptr(w), st) != 0
     torch.cuda.synchronize()
     assert (idx == -7).all() and (w == -7).all() and (off == -7).all()
     feats = torch.zeros(2, 5, 4, device=dev)
@@ -461,8 +454,8 @@ def test_argument_checks(K, pu, dev):
     for bad_off, bad_ent, word in ((None, ent, "adj_off"), (off.cpu(), ent, "adj_off"), (off, None, "adj_ent"), (off, ent[:, :-1], "adj_ent"),
                                    (off.float(), ent, "adj_off")):
         with pytest.raises(_C.ActHipError, match=word):
-            K.interp_rows_any_bwd(dY, bad_off, bad_ent, wq, 2, 8, 4)
-    assert lib.act_interp_rows_any_fwd_f32(ptr(wq), ptr(i3), ptr(wq), 1 << 14, 1 << 14, 4, 4, ptr(wq), st) != 0       # 2^28 rows: refused
+            K.interp_rows_bwd(dY, bad_off, bad_ent, wq, 2, 8, 4)
+    assert lib.act_interp_rows_fwd_f32(ptr(wq), ptr(i3), ptr(wq), None, None, None, 1 << 14, 1 << 14, 4, 4, ptr(wq), st) != 0       # 2^28 rows: refused
     fp = P.PointNetFeaturePropagationAny(5 + 7, [8]).to(dev)
     x1, x2 = torch.zeros(2, 3, 8, device=dev), torch.zeros(2, 3, 4, device=dev)
     with pytest.raises(RuntimeError, match="in_channel"):

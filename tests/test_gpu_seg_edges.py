@@ -1,6 +1,7 @@
-"""GPU: the kernels of csrc/seg.hip at the sizes where their index arithmetic changes (ragged tiles, one past a block or a chunk, grid-stride
-loops, the limits of G and C) and on ignored labels.  Every comparison is bit-exact (three-NN against its float32 restatement, integer-valued
-data whose float32 partial sums are exact, counts) or against a rounding bound computed in float64 from the inputs (tests/seg_ref.py); the one
+"""GPU: the kernels of the Transformer segmentation head (csrc/seg.hip and the three-NN feature propagation of csrc/sa.hip) at the sizes where
+their index arithmetic changes (ragged tiles, one past a block or a chunk, grid-stride loops, the limits of G and C) and on ignored labels.
+Every comparison is bit-exact (three-NN against its float32 restatement, integer-valued data whose float32 partial sums are exact, counts)
+or against a rounding bound computed in float64 from the inputs (tests/seg_ref.py); the one
 exception is interp_conv, which goes through the GEMM and reuses the project's relative bar.  Each test prints its largest error / bound ratio
 (pytest -s) so that the tightness of the bounds stays visible."""
 import functools
@@ -67,13 +68,14 @@ def _check_three_nn(dev, xyz, ctr):
     return ref
 
 
-NN_CASES = [(1, 1, 3), (2, 255, 3), (3, 257, 5), (2, 1000, 127), (1, 683, 512), (2, 700, 511)]
+NN_CASES = [(1, 1, 3), (2, 255, 3), (3, 257, 5), (2, 1000, 127), (1, 683, 512), (2, 700, 511), (1, 683, 256), (2, 300, 257)]
 
 
 @pytest.mark.parametrize("B,N,G", NN_CASES)
 def test_three_nn_bit_exact_on_all_rows(dev, B, N, G):
     """idx, w, off and ent equal the float32 restatement on every row (not only off near-ties); E = 3N = 2049 is one entry past a chunk of the
-    adjacency kernel at N = 683, and G = 3 / 511 / 512 are the limits of the centre loop and of the scan"""
+    one-launch adjacency kernel at N = 683 and G = 256, its largest G (257 and above go to the three-launch builder); G = 3 / 511 / 512 were the
+    limits of the centre loop and of the scan of the former kernel"""
     xyz, ctr = _cloud(B, N, G, 1000 + N + G)
     _check_three_nn(dev, xyz, ctr)
 
@@ -113,12 +115,16 @@ def test_three_nn_degenerate_adjacency(dev, G):
     assert np.array_equal(off, np.broadcast_to(want_off.astype(np.int32), (B, G + 1)))
 
 
-def test_three_nn_rejects_G_outside_3_512(dev):
-    from act_amd import kernels as K, _C
-    xyz = torch.zeros(1, 8, 3, device=dev)
-    for G in (2, 513):
-        with pytest.raises(_C.ActHipError):
-            K.three_nn(xyz, torch.zeros(1, G, 3, device=dev))
+@pytest.mark.parametrize("G", [1, 2, 513])
+def test_three_nn_outside_the_former_3_512_limit(dev, G):
+    """G < 3: the slots that never fill carry idx 0 and weight exactly 0, the others are normalised over what exists; G = 513 is one past the
+    former limit.  Bit for bit, as at every other size"""
+    xyz, ctr = _cloud(2, 300, G, 2000 + G)
+    idx, w, _, _, d = _check_three_nn(dev, xyz, ctr)
+    if G < 3:
+        assert (idx[..., G:] == 0).all() and np.isinf(d[..., G:]).all() and (w[..., G:] == 0).all()
+    if G == 1:
+        assert (w[..., 0] == 1).all()
 
 
 # ---- row interpolation: index coverage in exact arithmetic -----------------------------------------------------------------------------------
@@ -145,13 +151,14 @@ def _exact_case(B, N, G, C):
     return dict(xyz=xyz, ctr=ctr, idx=idx, off=off, ent=ent, w=w, P=P, dY=dY, pts=pts, wx=wx, bias=bias, Y=Y, Y2=Y2, dP=dP)
 
 
-INTERP_CASES = [(1, 1, 3, 4), (3, 5, 3, 4), (2, 257, 7, 260), (1, 1000, 512, 12), (1, 262148, 3, 4)]
+INTERP_CASES = [(1, 1, 3, 4), (3, 5, 3, 4), (2, 257, 7, 260), (1, 1000, 512, 12), (1, 262148, 3, 4), (2, 5, 3, 1), (2, 37, 7, 3), (1, 257, 7, 130)]
 
 
 @pytest.mark.parametrize("B,N,G,C", INTERP_CASES)
 def test_interp_rows_exact(dev, B, N, G, C):
     """forward (with and without the xyz / bias epilogue) and backward equal float64 element for element: R = 15 is no multiple of the 4 rows of
-    a block, C / 4 = 65 is one past a 64-lane block, G = 512 is the longest centre table, and B * N = 262148 needs 65537 row blocks"""
+    a block, C / 4 = 65 is one past a 64-lane block, G = 512 is a long centre table, and B * N = 262148 needs 65537
+    row blocks; C = 1, 3 and 130 are no multiple of 4 (one float per lane; 130 is two past two 64-lane blocks)"""
     from act_amd import kernels as K
     c = _exact_case(B, N, G, C)
     idx, w, off, ent = _d(c["idx"], dev), _d(c["w"], dev), _d(c["off"], dev), _d(c["ent"], dev)
@@ -194,13 +201,10 @@ def test_interp_rows_rounding_bounds(dev, B, N, G, C):
     assert _ratio("interp_bwd %s" % ((B, N, G, C),), np.abs(got - dP), (L[:, None] + 2) * U * Ab) <= 1
 
 
-def test_interp_conv_forward_backward(dev):
-    """the per-group form (GEMM once per centre, then interpolation + xyz columns + bias in one kernel) against the plain form
-    W . cat(xyz, sum_k w_k x[idx_k]) + b in float64 autograd, at a ragged shape"""
+def _check_interp_conv(dev, B, N, G, C, Kf, want_adj):
     from act_amd import kernels as K
-    B, N, G, C, Kf = 2, 257, 7, 260, 64
-    rs = np.random.RandomState(64)
-    xyz, ctr = _cloud(B, N, G, 65)
+    rs = np.random.RandomState(Kf)
+    xyz, ctr = _cloud(B, N, G, Kf + 1)
     idx, w, _, _, _ = SR.three_nn_f32(xyz, ctr)
     x = torch.from_numpy(rs.standard_normal((B * G, Kf)).astype(np.float32))
     W = torch.from_numpy((rs.standard_normal((C, 3 + Kf)) / 8).astype(np.float32))
@@ -212,13 +216,56 @@ def test_interp_conv_forward_backward(dev):
     feat = (x64[rows] * torch.from_numpy(w).double().reshape(B * N, 3, 1)).sum(1)
     ref = torch.cat((pts.double(), feat), dim=1) @ W64.t() + b64
     ref.backward(dY.double())
-    nn3 = K.three_nn(_d(xyz, dev), _d(ctr, dev))
+    nn3 = K.three_nn(_d(xyz, dev), _d(ctr, dev), want_adj=want_adj)
+    assert (nn3[2] is None) == (not want_adj)
     assert np.array_equal(nn3[0].cpu().numpy(), idx) and np.array_equal(_bits(nn3[1].cpu().numpy()), _bits(w))
     xd, Wd, bd = (t.to(dev).requires_grad_(True) for t in (x, W, b))
     y = K.interp_conv(xd, Wd, bd, pts.to(dev), nn3, B, N, G)
     y.backward(dY.to(dev))
     assert _rel(y, ref) <= TOL
     assert _rel(xd.grad, x64.grad) <= TOL and _rel(Wd.grad, W64.grad) <= TOL and _rel(bd.grad, b64.grad) <= TOL
+
+
+def test_interp_conv_forward_backward(dev):
+    """the per-group form (GEMM once per centre, then interpolation + xyz columns + bias in one kernel) against the plain form
+    W . cat(xyz, sum_k w_k x[idx_k]) + b in float64 autograd, at a ragged shape"""
+    _check_interp_conv(dev, 2, 257, 7, 260, 64, True)
+
+
+def test_interp_conv_builds_the_adjacency_its_search_left_out(dev):
+    """nn3 from a search without the adjacency (want_adj=False): the backward builds it.  G = 2 leaves every third slot at weight 0, and C = 6 /
+    Kf = 5 are no multiples of 4"""
+    _check_interp_conv(dev, 2, 37, 2, 6, 5, False)
+
+
+def test_interp_rows_skip_a_slot_of_weight_zero(dev):
+    """the third slot of every point has weight exactly 0 (a search over two centres) and is aimed at a row of inf in P: it is neither read nor
+    added, so the forward with the xyz / bias epilogue stays finite and equals the unpoisoned result bit for bit, and the backward leaves that
+    row's gradient 0"""
+    from act_amd import kernels as K
+    B, N, G, C = 2, 37, 3, 6
+    rs = np.random.RandomState(37)
+    xyz, ctr = _cloud(B, N, 2, 38)
+    idx, w, _, _, _ = SR.three_nn_f32(xyz, ctr)
+    assert (w[..., 2] == 0).all() and (idx[..., 2] == 0).all() and (w[..., :2] > 0).all()
+    P = rs.standard_normal((B * G, C)).astype(np.float32)
+    wx, bias = rs.standard_normal((C, 3)).astype(np.float32), rs.standard_normal(C).astype(np.float32)
+    dY = rs.standard_normal((B * N, C)).astype(np.float32)
+    epi = dict(xyz=_d(xyz, dev), wxyz=_d(wx, dev), bias=_d(bias, dev))
+    base = K.interp_rows_fwd(_d(P, dev), _d(idx, dev), _d(w, dev), B, N, G, **epi)
+    poisoned = P.copy()
+    poisoned.reshape(B, G, C)[:, 2] = np.inf
+    aimed = idx.copy()
+    aimed[..., 2] = 2
+    Y = K.interp_rows_fwd(_d(poisoned, dev), _d(aimed, dev), _d(w, dev), B, N, G, **epi)
+    assert torch.isfinite(Y).all() and np.array_equal(_bits(Y.cpu().numpy()), _bits(base.cpu().numpy()))
+    want, A = SR.interp_fwd_f64(P, idx, w, B, N, G, xyz=xyz.reshape(-1, 3), wxyz=wx, bias=bias)
+    assert _ratio("interp_fwd skipped slot", np.abs(Y.cpu().numpy().astype(np.float64) - want), 8 * U * A) <= 1
+    off, ent = SR.adjacency(aimed, G)
+    dP = K.interp_rows_bwd(_d(dY, dev), _d(off, dev), _d(ent, dev), _d(w, dev), B, N, G).cpu().numpy()
+    assert np.isfinite(dP).all() and (dP.reshape(B, G, C)[:, 2] == 0).all() and (dP.reshape(B, G, C)[:, :2] != 0).any()
+    off2, ent2 = K.three_adjacency(_d(aimed, dev), G)
+    assert np.array_equal(off2.cpu().numpy(), off) and np.array_equal(ent2.cpu().numpy(), ent)
 
 
 # ---- xyz / bias gradient -----------------------------------------------------------------------------------------------------------------------
