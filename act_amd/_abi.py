@@ -339,6 +339,14 @@ _TABLE = {
     "act_edge_bn_lrelu_max_fwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _sz, _vp],
     "act_edge_bn_lrelu_max_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    # DGCNN segmentation networks: two-layer EdgeConv tail, 3x3 transform of a cloud (csrc/edge_mlp2.hip)
+    "act_edge_mlp2_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "act_edge_mlp2_fwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_edge_mlp2_bwd_f32": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _sz, _vp],
+    "act_cloud_transform3_fwd_f32": [_vp, _vp, _i, _i, _vp, _vp],
+    "act_cloud_transform3_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp],
     "act_affine_lrelu_f32": [_vp, _vp, _vp, _f, _i, _i, _vp, _vp],
     "act_bn_lrelu_bwd_workspace": (_sz, [_i, _i]),
     "act_bn_lrelu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],

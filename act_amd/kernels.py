@@ -2719,6 +2719,138 @@ def edge_conv_bn(pq, qoff, idx, B, N, k, C, bn, training, slope=0.2, validate=Tr
     return (out, arg, vsum) if want_aux else out
 
 
+# ---- DGCNN segmentation networks (csrc/edge_mlp2.hip): two-layer EdgeConv tail, 3x3 transform of a cloud ---------------------------------------------
+EDGE_MLP2_MAX_K = 64
+EDGE_MLP2_MAX_C = 128
+
+
+class EdgeMlp2Fn(torch.autograd.Function):
+    """out[b*N+i, :] = max_j LeakyReLU(BN2(w2 . LeakyReLU(BN1(P[b, idx[b,i,j], :] + Q[b,i,:])))), both BatchNorms over all B*N*k edges; the per-edge
+    product runs on the matrix cores from tiles built in LDS and no edge tensor is stored by the forward (csrc/edge_mlp2.hip).  Differentiable in
+    pq, gamma1, beta1, w2, gamma2 and beta2."""
+
+    @staticmethod
+    def forward(ctx, pq, gamma1, beta1, w2, gamma2, beta2, rm1, rv1, rm2, rv2, idx, qoff, B, N, k, C1, C2, training, mom1, eps1, mom2, eps2, slope):
+        pq, w2 = _f32c(pq, "edge_mlp2_bn: pq"), _f32c(w2, "edge_mlp2_bn: w2")
+        dev = pq.device
+        R = B * N
+        out = torch.empty(R, C2, dtype=torch.float32, device=dev)
+        arg = torch.empty(R, C2, dtype=torch.int32, device=dev)
+        ysel = torch.empty(R, C2, dtype=torch.float32, device=dev)
+        st1, st2 = torch.empty(3, C1, dtype=torch.float32, device=dev), torch.empty(3, C2, dtype=torch.float32, device=dev)
+        ws = workspace(dev, lib.act_edge_mlp2_workspace(B, N, k, C1, C2))
+        check(lib.act_edge_mlp2_fwd_f32(ptr(pq), pq.stride(0), int(qoff), ptr(idx), B, N, k, C1, C2, ptr(gamma1), ptr(beta1), ptr(rm1), ptr(rv1), ptr(w2),
+                                        ptr(gamma2), ptr(beta2), ptr(rm2), ptr(rv2), int(training), float(mom1), float(eps1), float(mom2), float(eps2),
+                                        float(slope), ptr(out), ptr(arg), ptr(ysel), ptr(st1), ptr(st2), ptr(ws), ws.numel() * 4, stream()),
+              "act_edge_mlp2_fwd_f32")
+        ctx.save_for_backward(pq, gamma1, beta1, w2, gamma2, beta2, idx, arg, ysel, st1, st2)
+        ctx.cfg = (int(qoff), B, N, k, C1, C2, bool(training), float(slope))
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, dout, _darg):
+        pq, gamma1, beta1, w2, gamma2, beta2, idx, arg, ysel, st1, st2 = ctx.saved_tensors
+        qoff, B, N, k, C1, C2, training, slope = ctx.cfg
+        if not training:
+            raise NotImplementedError("EdgeConv BatchNorm backward in eval mode is off the training path")
+        if qoff < C1:
+            raise ValueError(f"edge_mlp2_bn: backward needs P and Q in separate columns (qoff >= C1), got qoff={qoff}, C1={C1}")
+        dout = _f32c(dout, "edge_mlp2_bn: grad")
+        dev = pq.device
+        dpq = torch.empty_like(pq) if (pq.shape[1] == 2 * C1 and qoff == C1) else torch.zeros_like(pq)
+        dg1, db1 = (torch.empty(C1, dtype=torch.float32, device=dev) for _ in range(2))
+        dg2, db2 = (torch.empty(C2, dtype=torch.float32, device=dev) for _ in range(2))
+        dw2 = torch.empty(C2, C1, dtype=torch.float32, device=dev)
+        ws = workspace(dev, lib.act_edge_mlp2_workspace(B, N, k, C1, C2))
+        check(lib.act_edge_mlp2_bwd_f32(ptr(pq), pq.stride(0), qoff, ptr(idx), B, N, k, C1, C2, ptr(gamma1), ptr(beta1), ptr(w2), ptr(gamma2), ptr(beta2),
+                                        ptr(st1), ptr(st2), slope, ptr(arg), ptr(ysel), ptr(dout), dout.stride(0), ptr(dpq), ptr(dg1), ptr(db1), ptr(dw2),
+                                        ptr(dg2), ptr(db2), ptr(ws), ws.numel() * 4, stream()), "act_edge_mlp2_bwd_f32")
+        return (dpq, dg1, db1, dw2, dg2, db2) + (None,) * 17
+
+
+def edge_mlp2_bn(pq, qoff, idx, B, N, k, C1, bn1, w2, bn2, training, slope=0.2, validate=True, want_aux=False):
+    """pq [B*N, ld] (P [.., C1] at column 0, Q at column ``qoff``), idx int [B,N,k], w2 [C2, C1] (or a 1x1 convolution's [C2, C1, 1, 1]) -> [B*N, C2]:
+    the tail of a two-layer EdgeConv with the parameters and buffers of the BatchNorm modules ``bn1`` and ``bn2`` (see EdgeMlp2Fn).  1 <= k <= 64,
+    4 <= C1, C2 <= 128 and multiples of 4, slope >= 0.  ``validate``: range-check idx on the device (one host read) and raise ValueError for an
+    index outside [0,N).  ``want_aux``: also return arg int32 [B*N, C2], the first j that attains the maximum."""
+    B, N, k, C1, qoff = int(B), int(N), int(k), int(C1), int(qoff)
+    if not isinstance(pq, torch.Tensor) or not pq.is_cuda:
+        raise _C.ActHipError("edge_mlp2_bn: pq: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if pq.dtype != torch.float32 or pq.dim() != 2:
+        raise _C.ActHipError(f"edge_mlp2_bn: pq: expected float32 [B*N, ld], got {pq.dtype} {list(pq.shape)}")
+    if not isinstance(w2, torch.Tensor) or not w2.is_cuda or w2.dtype != torch.float32:
+        raise _C.ActHipError("edge_mlp2_bn: w2: expected a float32 CUDA tensor")
+    if w2.dim() == 4 and w2.shape[2:] == (1, 1):
+        w2 = w2.view(w2.shape[0], w2.shape[1])
+    if w2.dim() != 2 or w2.shape[1] != C1:
+        raise ValueError(f"edge_mlp2_bn: w2: expected [C2, C1={C1}], got {list(w2.shape)}")
+    C2 = int(w2.shape[0])
+    if B < 1 or N < 1 or not 1 <= k <= EDGE_MLP2_MAX_K:
+        raise ValueError(f"edge_mlp2_bn: need B, N >= 1 and 1 <= k <= {EDGE_MLP2_MAX_K}, got B={B}, N={N}, k={k}")
+    if not (4 <= C1 <= EDGE_MLP2_MAX_C and 4 <= C2 <= EDGE_MLP2_MAX_C) or C1 % 4 or C2 % 4:
+        raise ValueError(f"edge_mlp2_bn: C1 and C2 must be multiples of 4 in [4, {EDGE_MLP2_MAX_C}], got C1={C1}, C2={C2}")
+    if B > 65535:
+        raise ValueError(f"edge_mlp2_bn: B must be <= 65535, got {B}")
+    if not slope >= 0:
+        raise ValueError(f"edge_mlp2_bn: slope must be >= 0 (the backward reads the sign of z1 off h), got {slope}")
+    if pq.shape[0] != B * N or qoff < 0 or qoff + C1 > pq.shape[1]:
+        raise ValueError(f"edge_mlp2_bn: pq {list(pq.shape)} does not hold [B*N={B * N}] rows with Q at columns [{qoff}, {qoff + C1})")
+    if bn1.num_features != C1 or bn1.weight is None or bn2.num_features != C2 or bn2.weight is None:
+        raise ValueError(f"edge_mlp2_bn: bn1 / bn2 must be affine BatchNorms over {C1} / {C2} channels")
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+        raise _C.ActHipError("edge_mlp2_bn: idx: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+    if idx.dtype not in (torch.int32, torch.int64) or tuple(idx.shape) != (B, N, k):
+        raise ValueError(f"edge_mlp2_bn: idx: expected int32 [{B}, {N}, {k}], got {idx.dtype} {list(idx.shape)}")
+    if validate and bool(((idx < 0) | (idx >= N)).any()):
+        raise ValueError(f"edge_mlp2_bn: idx holds an index outside [0, {N})")
+    idx = _i32c(idx)
+    if training and (_sync_group(bn1) is not None or _sync_group(bn2) is not None):
+        raise NotImplementedError("edge_mlp2_bn: SyncBatchNorm across ranks is not implemented for the EdgeConv tail")
+    if not training and (bn1.running_mean is None or bn2.running_mean is None):
+        raise ValueError("edge_mlp2_bn: eval mode needs running statistics")
+    if training:
+        for bn in (bn1, bn2):
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+    mom1, mom2 = (0.1 if bn.momentum is None else bn.momentum for bn in (bn1, bn2))
+    out, arg = EdgeMlp2Fn.apply(pq, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias, bn1.running_mean, bn1.running_var, bn2.running_mean,
+                                bn2.running_var, idx, qoff, B, N, k, C1, C2, bool(training), mom1, bn1.eps, mom2, bn2.eps, slope)
+    return (out, arg) if want_aux else out
+
+
+class CloudTransform3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, T):
+        x, T = _f32c(x, "cloud_transform3: x"), _f32c(T, "cloud_transform3: T")
+        B, N, _ = x.shape
+        y = torch.empty_like(x)
+        check(lib.act_cloud_transform3_fwd_f32(ptr(x), ptr(T), B, N, ptr(y), stream()), "act_cloud_transform3_fwd_f32")
+        ctx.save_for_backward(x, T)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, T = ctx.saved_tensors
+        dy = _f32c(dy, "cloud_transform3: grad")
+        B, N, _ = x.shape
+        dx, dT = torch.empty_like(x), torch.empty_like(T)
+        check(lib.act_cloud_transform3_bwd_f32(ptr(x), ptr(T), ptr(dy), B, N, ptr(dx), ptr(dT), stream()), "act_cloud_transform3_bwd_f32")
+        return dx, dT
+
+
+def cloud_transform3(x, T):
+    """x [B,N,3], T [B,3,3] -> y [B,N,3], y[b,n,:] = x[b,n,:] . T[b]; differentiable in both (dT summed in a fixed order)."""
+    for t, name in ((x, "x"), (T, "T")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _C.ActHipError(f"cloud_transform3: {name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 3:
+            raise _C.ActHipError(f"cloud_transform3: {name}: expected a float32 tensor of three dimensions, got {t.dtype} {list(t.shape)}")
+    if x.shape[2] != 3 or tuple(T.shape[1:]) != (3, 3) or T.shape[0] != x.shape[0] or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"cloud_transform3: expected x [B,N,3] and T [B,3,3], got {list(x.shape)} and {list(T.shape)}")
+    return CloudTransform3Fn.apply(x, T)
+
+
 class BNLreluFn(torch.autograd.Function):
     """BNActFn with LeakyReLU(slope) in place of ReLU: the statistics kernel is shared, the apply and the backward carry the slope."""
 

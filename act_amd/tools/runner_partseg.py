@@ -2,7 +2,8 @@
 
     python -m act_amd.tools.runner_partseg --root data/ShapeNetPart --ckpts act_pretrain.pth
     python -m act_amd.tools.runner_partseg --synthetic --max_steps 150
-    python -m act_amd.tools.runner_partseg --synthetic --model pointnet2_part_seg_msg      # the PointNet++ MSG baseline; any other --model: the Transformer
+    python -m act_amd.tools.runner_partseg --synthetic --model pointnet2_part_seg_msg      # the PointNet++ MSG baseline
+    python -m act_amd.tools.runner_partseg --synthetic --model dgcnn_partseg               # the DGCNN baseline; any other --model: the Transformer
 
 Same arguments and defaults as the reference except ``--ckpts``, which defaults to None (the reference's default names a file of its authors'
 machine), plus ``--synthetic`` (generated shapes, act_amd.datasets.ShapeNetPartDataset.SyntheticShapeNetPart), ``--max_steps`` (stop training after
@@ -116,10 +117,14 @@ def evaluate(model, loader, device, max_batches=0):
 
 
 def build_model(args):
-    """``--model pointnet2_part_seg_msg``: the PointNet++ MSG baseline (models/pointnet2_nets.py); every other value: the Transformer"""
+    """``--model pointnet2_part_seg_msg``: the PointNet++ MSG baseline (models/pointnet2_nets.py); ``--model dgcnn_partseg``: the DGCNN baseline
+    (models/dgcnn_nets.py); every other value: the Transformer"""
     if args.model == 'pointnet2_part_seg_msg':
         from ..models.pointnet2_nets import pointnet2_part_seg_msg
         return pointnet2_part_seg_msg(NUM_PARTS, normal_channel=False)
+    if args.model == 'dgcnn_partseg':
+        from ..models.dgcnn_nets import dgcnn_partseg
+        return dgcnn_partseg(NUM_PARTS)
     return get_model(NUM_PARTS)
 
 

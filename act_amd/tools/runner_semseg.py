@@ -2,7 +2,8 @@
 
     python -m act_amd.tools.runner_semseg --root data/stanford_indoor3d --ckpts act_pretrain.pth
     python -m act_amd.tools.runner_semseg --synthetic --max_steps 150
-    python -m act_amd.tools.runner_semseg --synthetic --model pointnet2_sem_seg            # the PointNet++ SSG baseline; any other --model: the Transformer
+    python -m act_amd.tools.runner_semseg --synthetic --model pointnet2_sem_seg            # the PointNet++ SSG baseline
+    python -m act_amd.tools.runner_semseg --synthetic --model dgcnn_semseg                 # the DGCNN baseline; any other --model: the Transformer
 
 Same arguments and defaults as the reference, plus ``--synthetic`` (generated rooms, act_amd.datasets.S3DISDataset.SyntheticS3DIS), ``--max_steps``
 (stop training after that many steps, then evaluate once), ``--log_every``, ``--seed``, ``--eval_batches`` and ``--device_sampler`` (blocks sampled
@@ -135,11 +136,14 @@ def evaluate(model, loader, weights, device, max_batches=0):
 
 
 def build_model(args):
-    """``--model pointnet2_sem_seg``: the PointNet++ SSG baseline (models/pointnet2_nets.py) on the xyz channels the blocks carry; every other
-    value: the Transformer"""
+    """``--model pointnet2_sem_seg``: the PointNet++ SSG baseline (models/pointnet2_nets.py) on the xyz channels the blocks carry; ``--model
+    dgcnn_semseg``: the DGCNN baseline (models/dgcnn_nets.py) on the same channels; every other value: the Transformer"""
     if args.model == 'pointnet2_sem_seg':
         from ..models.pointnet2_nets import pointnet2_sem_seg
         return pointnet2_sem_seg(NUM_CLASSES, in_channel=3)
+    if args.model == 'dgcnn_semseg':
+        from ..models.dgcnn_nets import dgcnn_semseg
+        return dgcnn_semseg(NUM_CLASSES, in_channel=3)
     return get_model(NUM_CLASSES)
 
 

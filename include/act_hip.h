@@ -1082,6 +1082,34 @@ int act_bn_lrelu_bwd_f32(const float* x, const float* dy, const float* scale, co
                          float slope, int R, int C, float* dx, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                          act_stream_t stream);
 
+/* ---- DGCNN segmentation networks (csrc/edge_mlp2.hip) ------------------------------------------------------------------------------- */
+/* Two-layer EdgeConv tail.  pq, idx as for act_edge_bn_lrelu_max_fwd_f32 (P [.., C1] at column 0, Q at column qoff), w2 fp32 [C2, C1].
+ *   v = P[b, idx[b,i,j], :] + Q[b,i,:]    h = LeakyReLU(BN1(v))    y = w2 . h    out[b*N+i, :] = max_j LeakyReLU(BN2(y))
+ * both BatchNorms over the M = B*N*k edges, with the statistics, running-statistics update and centred evaluation of the one-layer tail.  y is
+ * formed tile by tile on the f32 matrix cores and never stored: per (point, channel) the largest and smallest y with their first j are kept, and
+ * the one the sign of BN2's scale selects is evaluated.  Written: out [B*N, C2], arg int32 [B*N, C2] (the selected j), ysel [B*N, C2] (the
+ * selected y), stats1 [3, C1] and stats2 [3, C2] (mean | mean_lo | rstd).  Fixed order, no atomics, a cloud's y does not depend on B.
+ * 1 <= k <= 64, 4 <= C1, C2 <= 128 and multiples of 4, B <= 65535, slope >= 0, else ACT_E_BADARG with nothing written. */
+size_t act_edge_mlp2_workspace(int B, int N, int k, int C1, int C2);
+int act_edge_mlp2_fwd_f32(const float* pq, int ld, int qoff, const int32_t* idx, int B, int N, int k, int C1, int C2, const float* gamma1,
+                          const float* beta1, float* running_mean1, float* running_var1, const float* w2, const float* gamma2,
+                          const float* beta2, float* running_mean2, float* running_var2, int training, float momentum1, float eps1,
+                          float momentum2, float eps2, float slope, float* out, int32_t* arg, float* ysel, float* stats1, float* stats2,
+                          void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* its backward in train mode from the forward's arg, ysel, stats1, stats2 and dout [B*N, ldd]: dpq [B*N, ld] (dP at column 0, dQ at column
+ * qoff >= C1; other columns are not written), dgamma1, dbeta1 [C1], dw2 [C2, C1], dgamma2, dbeta2 [C2].  h and y are recomputed per tile with
+ * the forward's instruction sequence; one fp32 [B*N*k, C1] tensor (the gradient ahead of BN1) goes through the workspace.  No atomics,
+ * bit-identical run to run. */
+int act_edge_mlp2_bwd_f32(const float* pq, int ld, int qoff, const int32_t* idx, int B, int N, int k, int C1, int C2, const float* gamma1,
+                          const float* beta1, const float* w2, const float* gamma2, const float* beta2, const float* stats1,
+                          const float* stats2, float slope, const int32_t* arg, const float* ysel, const float* dout, int ldd, float* dpq,
+                          float* dgamma1, float* dbeta1, float* dw2, float* dgamma2, float* dbeta2, void* workspace, size_t workspace_bytes,
+                          act_stream_t stream);
+/* y[b,n,:] = x[b,n,:] . T[b] for x [B,N,3], T [B,3,3] (products and sums rounded, i ascending), and its backward: dx = dy . T[b]^T,
+ * dT[b] = sum_n x_n^T dy_n in float64, in a fixed order. */
+int act_cloud_transform3_fwd_f32(const float* x, const float* T, int B, int N, float* y, act_stream_t stream);
+int act_cloud_transform3_bwd_f32(const float* x, const float* T, const float* dy, int B, int N, float* dx, float* dT, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
