@@ -350,6 +350,14 @@ _TABLE = {
     "act_affine_lrelu_f32": [_vp, _vp, _vp, _f, _i, _i, _vp, _vp],
     "act_bn_lrelu_bwd_workspace": (_sz, [_i, _i]),
     "act_bn_lrelu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    # PointMLP: geometric affine grouping, residual BatchNorm tail (csrc/pointmlp.hip)
+    "act_geo_affine_fwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "act_geo_affine_group_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_geo_affine_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "act_geo_affine_group_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_affine_add_relu_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "act_bn_add_relu_bwd_workspace": (_sz, [_i, _i]),
+    "act_bn_add_relu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

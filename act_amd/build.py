@@ -24,7 +24,8 @@ PER_FILE = {"point_ops.hip": ["-ffp-contract=off"], "chamfer.hip": ["-ffp-contra
             "seg.hip": ["-ffp-contract=off"], "wholescene.hip": ["-ffp-contract=off"], "recon_eval.hip": ["-ffp-contract=off"],
             "augment.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "sa.hip": ["-ffp-contract=off"],
             "s3dis_sample.hip": ["-ffp-contract=off"], "cloud_sample.hip": ["-ffp-contract=off"],
-            "edgeconv.hip": ["-ffp-contract=off"], "edge_mlp2.hip": ["-ffp-contract=off"]}
+            "edgeconv.hip": ["-ffp-contract=off"], "edge_mlp2.hip": ["-ffp-contract=off"],
+            "pointmlp.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

@@ -2890,3 +2890,122 @@ class BNLreluFn(torch.autograd.Function):
         check(lib.act_bn_lrelu_bwd_f32(ptr(x), ptr(dy), ptr(scale), ptr(shift), ptr(mean), ptr(rstd), ctx.slope, R, C, ptr(dx), ptr(dg), ptr(db),
                                        ptr(ws), ws.numel() * 4, stream()), "act_bn_lrelu_bwd_f32")
         return dx, dg, db, None, None, None, None, None, None
+
+
+# ---- PointMLP (csrc/pointmlp.hip): geometric affine grouping, residual BatchNorm tail -------------------------------------------------------------------
+class GeoAffineGroupFn(torch.autograd.Function):
+    """LocalGrouper's normalize="anchor" module in row form: out [B*S*k, D (or 2D with cat)], sigma [B].  Differentiable in feat, alpha and beta; the
+    backward gathers per point over the inverse adjacency of idx (no edge tensor, no atomics, bit-identical run to run)."""
+
+    @staticmethod
+    def forward(ctx, feat, alpha, beta, fps_idx, idx, eps, cat, validate):
+        B, N, D = feat.shape
+        _, S, k = idx.shape
+        dev = feat.device
+        out = torch.empty(B * S * k, 2 * D if cat else D, dtype=torch.float32, device=dev)
+        sigma, mean = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+        ws = workspace(dev, lib.act_geo_affine_fwd_workspace(B, N, S, k, D))
+        rc = lib.act_geo_affine_group_fwd_f32(ptr(feat), ptr(fps_idx), ptr(idx), ptr(alpha), ptr(beta), float(eps), B, N, S, k, D, int(cat), int(validate),
+                                              ptr(out), ptr(sigma), ptr(mean), ptr(ws), ws.numel() * 4, stream())
+        if rc == -4:
+            raise ValueError(f"geo_affine_group: idx or fps_idx holds an index outside [0, {N})")
+        if rc == -1:
+            raise ValueError(f"act_geo_affine_group_fwd_f32 refused B={B}, N={N}, S={S}, k={k}, D={D}")
+        check(rc, "act_geo_affine_group_fwd_f32")
+        ctx.save_for_backward(feat, alpha, fps_idx, idx, sigma, mean)
+        ctx.cfg = (float(eps), int(cat))
+        ctx.mark_non_differentiable(sigma)
+        return out, sigma
+
+    @staticmethod
+    def backward(ctx, dout, _dsigma):
+        feat, alpha, fps_idx, idx, sigma, mean = ctx.saved_tensors
+        eps, cat = ctx.cfg
+        B, N, D = feat.shape
+        _, S, k = idx.shape
+        dev = feat.device
+        dout = _f32c(dout, "geo_affine_group: grad")
+        dfeat = torch.empty_like(feat)
+        da, db = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        ws = workspace(dev, lib.act_geo_affine_bwd_workspace(B, N, S, k, D))
+        check(lib.act_geo_affine_group_bwd_f32(ptr(feat), ptr(fps_idx), ptr(idx), ptr(alpha), ptr(sigma), ptr(mean), eps, ptr(dout), B, N, S, k, D, cat,
+                                               ptr(dfeat), ptr(da), ptr(db), ptr(ws), ws.numel() * 4, stream()), "act_geo_affine_group_bwd_f32")
+        return dfeat, da, db, None, None, None, None, None
+
+
+def geo_affine_group(feat, fps_idx, idx, alpha, beta, eps=1e-5, cat=False, want_aux=False, validate=True):
+    """feat [B,N,D], fps_idx int [B,S] (the anchors' rows, distinct per cloud), idx int [B,S,k], alpha / beta with D elements -> rows [B*S*k, D]:
+    alpha * (feat[idx] - feat[fps_idx]) / (std over the cloud's S*k*D differences + eps) + beta, upstream's three roundings.  ``cat``: [B*S*k, 2D] with
+    the anchor's row in the columns [D, 2D) (upstream's layout).  ``want_aux``: also sigma [B].  ``validate``: range-check the indices on the device
+    (one host read) and raise ValueError; pass False for indices the library's own FPS / kNN made."""
+    feat = _sa_f32(feat, "geo_affine_group: feat", (None, None, None))
+    B, N, D = feat.shape
+    for t, name in ((fps_idx, "fps_idx"), (idx, "idx")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _C.ActHipError(f"geo_affine_group: {name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"geo_affine_group: {name}: expected int32 or int64 indices, got {t.dtype}")
+    if idx.dim() != 3 or idx.shape[0] != B or fps_idx.dim() != 2 or tuple(fps_idx.shape) != (B, idx.shape[1]):
+        raise ValueError(f"geo_affine_group: expected idx [{B}, S, k] and fps_idx [{B}, S], got {list(idx.shape)} and {list(fps_idx.shape)}")
+    S, k = idx.shape[1], idx.shape[2]
+    if B < 1 or B > 65535 or N < 1 or D < 1 or S < 1 or not 1 <= k <= N or S * k * D < 2:
+        raise ValueError(f"geo_affine_group: need 1 <= B <= 65535, D >= 1, 1 <= k <= N and S*k*D >= 2, got B={B}, N={N}, S={S}, k={k}, D={D}")
+    if validate and (bool(((idx < 0) | (idx >= N)).any()) or bool(((fps_idx < 0) | (fps_idx >= N)).any())):     # (int64 values are checked before the cast)
+        raise ValueError(f"geo_affine_group: idx or fps_idx holds an index outside [0, {N})")
+    alpha, beta = (_sa_f32(t.reshape(-1), f"geo_affine_group: {n}", (D,)) for t, n in ((alpha, "alpha"), (beta, "beta")))
+    out, sigma = GeoAffineGroupFn.apply(feat, alpha, beta, _i32c(fps_idx), _i32c(idx), float(eps), bool(cat), bool(validate))
+    return (out, sigma) if want_aux else out
+
+
+class BNAddReluFn(torch.autograd.Function):
+    """ReLU(BatchNorm(y) + res) on rows [R,C]: the statistics kernel of BNActFn, an apply with the residual, and a backward that takes the ReLU mask from
+    the saved output (scale * y + shift alone does not give it) and writes dy and dres in one pass."""
+
+    @staticmethod
+    def forward(ctx, y, res, gamma, beta, running_mean, running_var, training, momentum, eps):
+        y, res = _f32c(y), _f32c(res)
+        R, C = y.shape
+        dev = y.device
+        out = torch.empty_like(y)
+        if training:
+            mean, rstd, scale, shift = (torch.empty(C, dtype=torch.float32, device=dev) for _ in range(4))
+            ws = workspace(dev, lib.act_colstats_workspace(R, C))
+            check(lib.act_bn_stats_f32(ptr(y), R, C, ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean),
+                                       ptr(running_var), ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(ws), ws.numel() * 4,
+                                       stream()), "act_bn_stats_f32")
+        else:
+            rstd = torch.rsqrt(running_var + eps)
+            mean = running_mean
+            scale = (gamma * rstd).contiguous()
+            shift = (beta - running_mean * scale).contiguous()
+        check(lib.act_affine_add_relu_f32(ptr(y), ptr(res), ptr(scale), ptr(shift), R, C, ptr(out), stream()), "act_affine_add_relu_f32")
+        ctx.save_for_backward(y, out, gamma, mean)
+        ctx.training, ctx.eps = training, float(eps)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, out, gamma, mean = ctx.saved_tensors
+        if not ctx.training:
+            raise NotImplementedError("BatchNorm backward in eval mode is off the training path")
+        dout = _f32c(dout)
+        R, C = y.shape
+        dy, dres = torch.empty_like(y), torch.empty_like(y)
+        dg = torch.empty(C, dtype=torch.float32, device=y.device)
+        db = torch.empty(C, dtype=torch.float32, device=y.device)
+        ws = workspace(y.device, lib.act_bn_add_relu_bwd_workspace(R, C))
+        check(lib.act_bn_add_relu_bwd_f32(ptr(y), ptr(out), ptr(dout), ptr(gamma), ptr(mean), ctx.eps, R, C, ptr(dy), ptr(dres), ptr(dg), ptr(db),
+                                          ptr(ws), ws.numel() * 4, stream()), "act_bn_add_relu_bwd_f32")
+        return dy, dres, dg, db, None, None, None, None, None
+
+
+def batch_norm_add_relu(y, res, bn, training):
+    """functional ReLU(nn.BatchNorm1d(y) + res) on rows [R,C] with the module's parameters and buffers: the tail of PointMLP's residual block.  Statistics,
+    running statistics and num_batches_tracked move exactly as in ``batch_norm_act``."""
+    if y.dim() != 2 or y.shape != res.shape or y.shape[0] < 1 or y.shape[1] != bn.num_features:
+        raise ValueError(f"batch_norm_add_relu: expected y and res [R, {bn.num_features}], got {list(y.shape)} and {list(res.shape)}")
+    if training and _sync_group(bn) is not None:
+        raise NotImplementedError("batch_norm_add_relu: a SyncBatchNorm across ranks is not implemented")
+    if training and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return BNAddReluFn.apply(y, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps)

@@ -1110,6 +1110,41 @@ int act_edge_mlp2_bwd_f32(const float* pq, int ld, int qoff, const int32_t* idx,
 int act_cloud_transform3_fwd_f32(const float* x, const float* T, int B, int N, float* y, act_stream_t stream);
 int act_cloud_transform3_bwd_f32(const float* x, const float* T, const float* dy, int B, int N, float* dx, float* dT, act_stream_t stream);
 
+/* ---- PointMLP (csrc/pointmlp.hip; Ma et al., ICLR 2022) --------------------------------------------------------------------------------- */
+#define ACT_E_INDEX    (-4)            /* an index operand holds a value outside its range (only where an entry is asked to check) */
+/* The geometric affine module of LocalGrouper, normalize="anchor".  feat fp32 [B,N,D], fps_idx int32 [B,S] (the anchors' rows), idx int32 [B,S,k]:
+ *   e = feat[b, idx[b,i,j], c] - feat[b, fps_idx[b,i], c]     sigma_b = sqrt(sum (e - mean e)^2 / (n - 1)), n = S*k*D (over the whole cloud)
+ *   r_b = 1 / (sigma_b + eps)                                 out[(b,i,j), c] = alpha[c] * (e * r_b) + beta[c]
+ * every operation rounded once, no FMA; the moments of e in float64 around a value of e, in a fixed order, so that a common offset of the
+ * features does not reach sigma and a cloud's result does not depend on B.  out is [B*S*k, D], or with cat != 0 [B*S*k, 2D] with the anchor's row in
+ * the columns [D, 2D).  Also written: sigma [B] and mean [B] (the mean of e), which the backward takes.  validate != 0: idx and fps_idx are
+ * range-checked on the device first (one host synchronisation) and ACT_E_INDEX is returned with nothing written if a value lies outside [0,N);
+ * validate == 0: such a value is clamped into range.  Any D >= 1 (float4 lanes when D % 4 == 0 and the operands are 16-byte aligned),
+ * 1 <= k <= N, S*k*D >= 2, B <= 65535, else ACT_E_BADARG with nothing written.  No atomics. */
+size_t act_geo_affine_fwd_workspace(int B, int N, int S, int k, int D);
+int act_geo_affine_group_fwd_f32(const float* feat, const int32_t* fps_idx, const int32_t* idx, const float* alpha, const float* beta, float eps,
+                                 int B, int N, int S, int k, int D, int cat, int validate, float* out, float* sigma, float* mean,
+                                 void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* its backward from the forward's sigma and mean and dout [B*S*k, D or 2D]: dfeat [B,N,D], dalpha [D], dbeta [D].
+ *   dalpha = sum g e r, dbeta = sum g, dsigma_b = -r^2 sum g alpha e, de = alpha g r + dsigma_b (e - mean) / ((n - 1) sigma_b)
+ * (the second term is 0 where sigma_b == 0), g the cotangent of the normalised columns.  Every point gathers de over the inverse adjacency of idx
+ * (built in the workspace: count, exclusive scan, fill) in ascending (i, j); an anchor adds the cotangent of its k copies minus the sum of its own
+ * k rows of de.  The column sums are float64 in two fixed-order stages.  No [B*S*k, D] tensor, no atomics, bit-identical run to run.  Indices are
+ * clamped into [0,N). */
+size_t act_geo_affine_bwd_workspace(int B, int N, int S, int k, int D);
+int act_geo_affine_group_bwd_f32(const float* feat, const int32_t* fps_idx, const int32_t* idx, const float* alpha, const float* sigma,
+                                 const float* mean, float eps, const float* dout, int B, int N, int S, int k, int D, int cat, float* dfeat,
+                                 float* dalpha, float* dbeta, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* The residual block tail on rows [R,C], any C: out = max((y * scale + shift) + res, 0), product and sums rounded; and its train-mode backward
+ * with the mask taken from the saved output: g = dout where out > 0, dres = g, dbeta = sum g, dgamma = sum g xhat (float64 column sums in a fixed
+ * order), dy = gamma rstd (g - dbeta / R - xhat * dgamma / R).  dy and dres are written in one pass.  The backward takes the forward's mean [C] as a
+ * pivot only: it forms the moments of y around it again in float64, in the pass of the column sums, and takes xhat and rstd from those. */
+int act_affine_add_relu_f32(const float* y, const float* res, const float* scale, const float* shift, int R, int C, float* out,
+                            act_stream_t stream);
+size_t act_bn_add_relu_bwd_workspace(int R, int C);
+int act_bn_add_relu_bwd_f32(const float* y, const float* out, const float* dout, const float* gamma, const float* mean, float eps, int R, int C,
+                            float* dy, float* dres, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
