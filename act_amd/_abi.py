@@ -76,7 +76,8 @@ class Dgcnn(ctypes.Structure):                         # act_dgcnn_t
 
 
 class DgcnnF16x3(ctypes.Structure):                    # act_dgcnn_f16x3_t
-    _fields_ = [("w5_planes", _vp), ("w5_inv_scale", _vp), ("a_scale", _f), ("a_planes", _vp), ("a_planes_elems", _sz)]
+    _fields_ = [("w5_planes", _vp), ("w5_inv_scale", _vp), ("a_scale", _f), ("a_planes", _vp), ("a_planes_elems", _sz), ("layers", _i),
+                ("st_planes", _vp * 3), ("st_inv_scale", _vp * 3)]
 
 
 class PointnetF16x3(ctypes.Structure):                 # act_pointnet_f16x3_t
@@ -194,10 +195,12 @@ _TABLE = {
     "act_sgemm_nt_bf16x3_planes_f32": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _epi, _vp],
     # default split-f16 products of the frozen teacher (same file, F16 form)
     "act_split_f16x2_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "act_split_f16x2_ld_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _i, _vp],
     "act_sgemm_nt_f16x3_supported": [_i, _i, _i],
     "act_sgemm_nt_f16x3_planes_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp],
     "act_sgemm_nt_f16x3_pick_tile": [_i, _i, _i, _i],
     "act_sgemm_nt_f16x3_planes_tile_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
+    "act_sgemm_nt_f16x3_planes_lda_f32": [_i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
     "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
     "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
     "act_prompt_layernorm_fwd_f16_planes_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp],

@@ -303,8 +303,8 @@ TEACHER_BF16X3_BWD = os.environ.get("ACT_TEACHER_BF16X3_BWD", "1") == "1"
 TEACHER_F16X3 = os.environ.get("ACT_TEACHER_F16X3", "1") != "0"
 _VIT_F16 = weakref.WeakKeyDictionary()         # tokenizer -> (signature, planes, inverse row scales, activation scales, pointer arrays)
 # DEFAULT ON: the head product of the FROZEN dVAE tokenizer's DGCNN (dgcnn_features below: T x Cout x 2304 against the frozen layer5[0] weight, the codebook
-# logits of dgcnn_1) on the same split-f16 kernel, taken for Cout >= 1024 (below that the split pass over cat eats the gain: dgcnn_2's 384-wide head and the
-# four edge-conv products stay on the f32 kernel).  fp32-grade, not bit-identical (notebook/tokenizer_f16x3.md); ACT_TOKENIZER_F16X3=0 restores the f32 path
+# logits of dgcnn_1) on the same split-f16 kernel, taken for Cout >= 1024 (dgcnn_2's 384-wide head makes 192 workgroups, under one round, and stays on the
+# f32 kernel; the edge-conv products have their own switch below).  fp32-grade, not bit-identical (notebook/tokenizer_f16x3.md); ACT_TOKENIZER_F16X3=0 restores the f32 path
 # bit for bit.  Stage I trains the tokenizer under autograd and never comes here.
 TOKENIZER_F16X3 = os.environ.get("ACT_TOKENIZER_F16X3", "1") != "0"
 # DEFAULT ON: the last product of the FROZEN tokenizer's mini-PointNet (pointnet_forward below: R x C x 512 against the frozen second_conv[3] weight, the group
@@ -312,8 +312,17 @@ TOKENIZER_F16X3 = os.environ.get("ACT_TOKENIZER_F16X3", "1") != "0"
 # parameter of the encoder frozen and training-mode statistics (the bound on the operand comes from them); fp32-grade, not bit-identical
 # (notebook/pn_f16x3.md); ACT_TOKENIZER_PN_F16X3=0 restores the f32 path bit for bit.  The student's encoder and Stage I's tokenizer train and never come here.
 TOKENIZER_PN_F16X3 = os.environ.get("ACT_TOKENIZER_PN_F16X3", "1") != "0"
+# DEFAULT ON: the stacked edge-conv products [Y | Z] = x . [Wa ; Wb - Wa]^T of layers 2-4 of BOTH frozen DGCNNs of the tokenizer (T x 2 cout x cin, K = 256 / 512)
+# on the same split-f16 kernel: every tail's slice of cat is split into the head's plane buffer at the head's scale and the next product reads its A planes there
+# (notebook/dgcnn_f16x3.md).  Taken from DGCNN_F16X3_MIN_T rows on: below it the smallest of the three products (1024 columns: 8 (T / 128) workgroups of
+# 128 x 128) does not fill one round of 256 CUs, the regime in which the split kernel has nothing over the f32 one (the rule that keeps the 384-wide head of dgcnn_2
+# off it).  ACT_TOKENIZER_DGCNN_F16X3=0 restores the f32 products bit for bit; each switch governs its own products.
+TOKENIZER_DGCNN_F16X3 = os.environ.get("ACT_TOKENIZER_DGCNN_F16X3", "1") != "0"
+DGCNN_F16X3_MIN_T = 4096
 _PN_F16 = weakref.WeakKeyDictionary()          # Encoder -> (signature, c4 planes, inverse row scales, max|gamma|, max|beta| of bn2, {R: a_scale})
-_DGCNN_F16 = weakref.WeakKeyDictionary()       # DGCNN -> (signature, w5 planes, inverse row scales, max|gamma|, max|beta|, couts, groups, {(G, k): a_scale})
+# DGCNN -> [signature, w5 planes, inverse row scales, max|gamma|, max|beta|, couts, groups, {(G, k): a_scale}, (planes, inverse row scales) of stacked[1..3]];
+# the planes of w5 and of the stacked matrices are made when first asked for (None until then)
+_DGCNN_F16 = weakref.WeakKeyDictionary()
 
 
 def _stack_leaves(blocks):
@@ -759,7 +768,7 @@ def pointnet_forward(enc, point_groups, need=None):
 def dgcnn_features(dg, f, idx, stacked):
     """``dg`` = models.dvae.DGCNN (frozen / no grad); f [B,G,Cin], idx int64 [B,k,G], stacked = the four [Wa ; Wb-Wa] matrices
     -> pre-norm head rows [B*G, Cout] (everything up to layer5's GroupNorm), one host call (10 launches; 11 with the head on split-f16 planes:
-    TOKENIZER_F16X3 and Cout >= 1024)."""
+    TOKENIZER_F16X3 and Cout >= 1024; 13 - 14 with layers 2-4 on them: TOKENIZER_DGCNN_F16X3 and B*G >= DGCNN_F16X3_MIN_T)."""
     B, G, Cin = f.shape
     dev = f.device
     w5 = dg.layer5[0].weight
@@ -777,8 +786,9 @@ def dgcnn_features(dg, f, idx, stacked):
     args = (ctypes.byref(m), _p(f), _p(idx), _p(h), _p(scratch), _p(ws), ws.numel() * 4)
     # (the f32 shapes are collected and tuned in either mode: a head the split-f16 kernel does not take falls back to them)
     ensure_tuned(("dgcnn", B, G, Cin, m.Cout), lambda: lib.act_dgcnn_features_f32(*args, _C.stream()), dev)
-    if TOKENIZER_F16X3 and m.Cout >= 1024:
-        x3, keep = _dgcnn_f16_planes(dg, B * G, G, m.k, dev)
+    head, layers = TOKENIZER_F16X3 and m.Cout >= 1024, TOKENIZER_DGCNN_F16X3 and B * G >= DGCNN_F16X3_MIN_T
+    if head or layers:
+        x3, keep = _dgcnn_f16_planes(dg, B * G, G, m.k, dev, head=head, layers=layers)
         check(lib.act_dgcnn_features_f16x3_f32(args[0], ctypes.byref(x3), *args[1:], _C.stream()), "act_dgcnn_features_f16x3_f32")
         del keep
         return h
@@ -794,27 +804,41 @@ def f16x3_dgcnn_bound(gmax, bmax, couts, groups, G, k):
     return max(math.sqrt((c // g) * G * k) * gm + bm for gm, bm, c, g in zip(gmax, bmax, couts, groups))
 
 
-def _dgcnn_f16_planes(dg, T, G, k, dev):
-    """f16 (h1, h2) planes of the frozen head weight layer5[0] with one power-of-two scale per output row, the inverse scales and the four max|gamma|, max|beta|
-    of the range guard (read to the host HERE, never per step) -- computed ONCE and cached per DGCNN under the (address, version) signature of the head weight
-    and the four GroupNorm affines (load_state_dict copies in place); the activation scale is host arithmetic from those and the call's (G, k).
+def _dgcnn_f16_planes(dg, T, G, k, dev, head=True, layers=None):
+    """f16 (h1, h2) planes of the frozen head weight layer5[0] (``head``) and of the stacked matrices [Wa ; Wb - Wa] of layers 2-4 (``layers``; None: the
+    rule of dgcnn_features), each with one power-of-two scale per output row, the inverse scales, and the four max|gamma|, max|beta| of the range guard (read to
+    the host HERE, never per step) -- computed ONCE and cached per DGCNN under the (address, version) signature of the head weight, the four GroupNorm affines
+    and the three conv weights (load_state_dict copies in place); the activation scale is host arithmetic from those and the call's (G, k).
     -> (DgcnnF16x3, keep-alive)"""
+    if layers is None:
+        layers = TOKENIZER_DGCNN_F16X3 and T >= DGCNN_F16X3_MIN_T
+    convs = [layer[0] for layer in (dg.layer2, dg.layer3, dg.layer4)]
     gns = [layer[1] for layer in (dg.layer1, dg.layer2, dg.layer3, dg.layer4)]
     w5 = dg.layer5[0].weight
-    sig = tuple((t.data_ptr(), t._version) for t in [w5] + [t for gn in gns for t in (gn.weight, gn.bias)])
+    sig = tuple((t.data_ptr(), t._version) for t in [w5] + [t for gn in gns for t in (gn.weight, gn.bias)] + [c.weight for c in convs])
     cache = _DGCNN_F16.get(dg)
     if cache is None or cache[0] != sig:
         with torch.no_grad():
-            w = w5.detach().reshape(w5.shape[0], w5.shape[1])
-            scale, inv = K.f16x3_row_scales(w)
-            planes = K.split_f16x2(w, 1.0, scale)
-            inv = inv.contiguous()
             mx = torch.stack([t.detach().double().abs().max() for gn in gns for t in (gn.weight, gn.bias)]).tolist()
-        cache = _DGCNN_F16[dg] = (sig, planes, inv, mx[0::2], mx[1::2], [gn.num_channels for gn in gns], [gn.num_groups for gn in gns], {})
-    _, planes, inv, gmax, bmax, couts, groups, scales = cache
+        cache = _DGCNN_F16[dg] = [sig, None, None, mx[0::2], mx[1::2], [gn.num_channels for gn in gns], [gn.num_groups for gn in gns], {}, None]
+
+    def planes_of(w):
+        scale, inv = K.f16x3_row_scales(w)
+        return K.split_f16x2(w, 1.0, scale), inv.contiguous()
+    if head and cache[1] is None:
+        with torch.no_grad():
+            cache[1], cache[2] = planes_of(w5.detach().reshape(w5.shape[0], w5.shape[1]))
+    if layers and cache[8] is None:
+        with torch.no_grad():
+            cache[8] = [planes_of(dg._stacked_weight(c).detach()) for c in convs]
+    _, planes, inv, gmax, bmax, couts, groups, scales, st = cache
     a_scale = scales.get((G, k))
     if a_scale is None:
         a_scale = scales[(G, k)] = f16x3_act_scale(f16x3_dgcnn_bound(gmax, bmax, couts, groups, G, k))
-    a_planes = torch.empty(2 * T * planes.shape[2], dtype=torch.float16, device=dev)
-    x3 = DgcnnF16x3(planes.data_ptr(), inv.data_ptr(), a_scale, a_planes.data_ptr(), a_planes.numel())
+    a_planes = torch.empty(2 * T * sum(couts), dtype=torch.float16, device=dev)
+    x3 = DgcnnF16x3(planes.data_ptr() if head else None, inv.data_ptr() if head else None, a_scale, a_planes.data_ptr(), a_planes.numel())
+    if layers:
+        x3.layers = 1
+        for i, (p, v) in enumerate(st):
+            x3.st_planes[i], x3.st_inv_scale[i] = p.data_ptr(), v.data_ptr()
     return x3, (a_planes, cache)

@@ -1033,9 +1033,12 @@ int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* 
                            act_stream_t stream) {
     return dgcnn_features(m, nullptr, f, idx, h, scratch, ws, wsb, stream);
 }
-// same launch sequence with the head product (T x Cout x 2304, frozen w5) on the split-f16 kernel: `cat` is split at the static scale x3->a_scale and
-// multiplied with the cached planes of w5.  Everything up to `cat` is the f32 entry's, bit for bit; an unusable x3 (null pointer, a_scale <= 0 = the range
-// guard gave no scale, scratch too small, a shape the kernel does not take) runs the f32 head product and equals act_dgcnn_features_f32 bit for bit.
+// same launch sequence with frozen products on the split-f16 kernel.  layers == 0: the head product alone (T x Cout x 2304, frozen w5): `cat` is split at the
+// static scale x3->a_scale and multiplied with the cached planes of w5.  layers != 0: the stacked products of layers 2-4 as well -- each tail's slice of cat is
+// split into a_planes at its column (row stride 2304, the same scale: its bound is the maximum over the four tails), the next layer's product reads its A planes
+// there, and the head finds the planes of the whole cat already written, the same bytes its own pass wrote.  Layer 1 (K = 128) and input_trans stay on the f32
+// kernel.  An unusable x3 (null pointer, a_scale <= 0 = the range guard gave no scale, scratch too small, T % 128 != 0) runs the f32 sequence and equals
+// act_dgcnn_features_f32 bit for bit; with layers != 0 a null or refused head alone stays on the f32 kernel.
 int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
                                  float* ws, size_t wsb, act_stream_t stream) {
     return dgcnn_features(m, x3, f, idx, h, scratch, ws, wsb, stream);
@@ -1048,20 +1051,40 @@ static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, con
     const int T = m->B * m->G;
     float *x0, *yz, *cat, *stats;
     carve_dgcnn(scratch, *m, x0, yz, cat, stats);
+    // what the struct allows: planes scratch for the whole cat at a usable scale; then the head's planes (where its shape is taken) and / or all three layers'
+    const bool planes_ok = x3 && x3->a_planes && x3->a_scale > 0.f && x3->a_planes_elems >= (size_t)2 * T * 2304 && T % 128 == 0 &&
+                           ((uintptr_t)x3->a_planes & 15) == 0;
+    bool layers = planes_ok && x3->layers;
+    for (int l = 1; layers && l < 4; ++l)
+        layers = x3->st_planes[l - 1] && x3->st_inv_scale[l - 1] && act_sgemm_nt_f16x3_supported(T, 2 * kDgcnnCout[l], kDgcnnCin[l]);
+    const bool head = planes_ok && x3->w5_planes && x3->w5_inv_scale && act_sgemm_nt_f16x3_supported(T, m->Cout, 2304) &&
+                      (layers || !x3->layers);                                // (layers asked for and refused: the whole f32 sequence)
+    uint16_t* const ap1 = planes_ok ? x3->a_planes : nullptr;
+    uint16_t* const ap2 = planes_ok ? x3->a_planes + (size_t)T * 2304 : nullptr;
     act_gemm_epilogue_t e = epi0(); e.bias = m->b_in;
     CK(gemm_nt(T, 128, m->Cin, f, m->Cin, m->w_in, m->Cin, x0, 128, e, ws, wsb, s));
     const float* xin = x0; int ldx = 128, off = 0;
     for (int l = 0; l < 4; ++l) {
         const int cin = kDgcnnCin[l], cout = kDgcnnCout[l];
         // W.cat(x_j - x_i, x_i) = Wa x_j + (Wb - Wa) x_i: one GEMM over the B*G points -> [Y | Z], then gather + GroupNorm + LeakyReLU + max_k
-        CK(gemm_nt(T, 2 * cout, cin, xin, ldx, m->stacked[l], cin, yz, 2 * cout, epi0(), ws, wsb, s));
+        if (layers && l > 0 && !t_collect) {                         // A = the planes of the previous tail's slice of cat, written below
+            const size_t prev = (size_t)(off - cin);
+            const uint16_t* w1 = x3->st_planes[l - 1];
+            const act_gemm_epilogue_t e0 = epi0();
+            RUN(act_sgemm_nt_f16x3_planes_lda_f32(T, 2 * cout, cin, ap1 + prev, ap2 + prev, 2304, x3->a_scale, w1, w1 + (size_t)2 * cout * cin,
+                                                  x3->st_inv_scale[l - 1], yz, 2 * cout, nullptr, nullptr, 0.f, &e0, s, 0));
+        } else {                                                     // (also while the GEMM shapes are collected: a fall-back finds its configuration)
+            CK(gemm_nt(T, 2 * cout, cin, xin, ldx, m->stacked[l], cin, yz, 2 * cout, epi0(), ws, wsb, s));
+        }
         RUN(act_edge_gn_lrelu_max_f32(yz, 2 * cout, cout, idx, m->B, m->G, m->k, cout, m->groups, m->gn_w[l], m->gn_b[l], m->eps, m->slope, stats,
                                      cat, 2304, off, s));
+        if (layers && (l < 3 || head) && !t_collect)                 // this tail's slice as planes, for the next layer and the head
+            RUN(act_split_f16x2_ld_f32(cat + off, T, cout, 2304, x3->a_scale, ap1 + off, ap2 + off, 2304, s));
         xin = cat + off; ldx = 2304; off += cout;
     }
-    if (x3 && x3->w5_planes && x3->w5_inv_scale && x3->a_planes && x3->a_scale > 0.f && x3->a_planes_elems >= (size_t)2 * T * 2304) {
+    if (head) {
         const X3Linear w5 = x3_linear_of(x3->w5_planes, (size_t)m->Cout * 2304, PlaneFmt::f16(x3->a_scale), x3->w5_inv_scale);
-        if (x3_takes(w5, T, m->Cout, 2304)) return x3_linear(w5, T, m->Cout, 2304, cat, nullptr, x3->a_planes, h, nullptr, w5.a_fmt, epi0(), s);
+        return x3_linear(w5, T, m->Cout, 2304, cat, layers ? x3->a_planes : nullptr, x3->a_planes, h, nullptr, w5.a_fmt, epi0(), s);
     }
     CK(gemm_nt(T, m->Cout, 2304, cat, 2304, m->w5, 2304, h, m->Cout, epi0(), ws, wsb, s));
     return 0;

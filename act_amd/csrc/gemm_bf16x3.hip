@@ -54,21 +54,23 @@ __device__ __forceinline__ float4 x3_affine_relu4(const float4& a, const float4&
 __device__ __forceinline__ float4 x3_scale4(const float4& a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 
 // fp32 [R][K] (row stride ldx) -> two planes [R][K] (split_planes.h), four elements per thread (K % 4 == 0): (hi, lo) bf16 planes of x, or (F16) the (h1, h2)
-// f16 planes of x * scale * row_scale[row]; both scales are powers of two chosen by the caller and are not read in the bf16 form
+// f16 planes of x * scale * row_scale[row]; both scales are powers of two chosen by the caller and are not read in the bf16 form.  The planes' rows are ldp
+// elements apart (ldp == K: dense; wider: a column slice of a wider plane buffer, the same bytes per element)
 // AFF (F16 only): the planes of relu(x * col_scale[k] + col_shift[k]) * scale instead -- the power of two folded into the affine map first, one fma per element,
 // exactly what the product's on-load form computes, so the two forms give the same planes bit for bit
 template <bool F16, bool AFF = false>
-__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int K4, int ldx, long long n4, float scale,
+__global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int K4, int ldx, int ldp4, long long n4, float scale,
                                                            const float* __restrict__ row_scale, unsigned short* __restrict__ p1, unsigned short* __restrict__ p2,
                                                            const float* __restrict__ col_scale = nullptr, const float* __restrict__ col_shift = nullptr) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / K4; const int c4 = (int)(i - row * K4);
         const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
+        const size_t o4 = (size_t)(row * ldp4 + c4);          // ldp4 = the planes' row stride in groups of four elements (K4: dense, o4 == i)
         if constexpr (AFF) {
             const float4 sc = x3_scale4(*reinterpret_cast<const float4*>(col_scale + c4 * 4), scale), sh = x3_scale4(*reinterpret_cast<const float4*>(col_shift + c4 * 4), scale);
-            store_planes4<F16>(p1, p2, (size_t)i, x3_affine_relu4(v, sc, sh), 1.0f);
+            store_planes4<F16>(p1, p2, o4, x3_affine_relu4(v, sc, sh), 1.0f);
         } else {
-            store_planes4<F16>(p1, p2, (size_t)i, v, F16 && row_scale ? scale * row_scale[row] : scale);
+            store_planes4<F16>(p1, p2, o4, v, F16 && row_scale ? scale * row_scale[row] : scale);
         }
     }
 }
@@ -77,14 +79,14 @@ constexpr int BK = 32;                      // bf16 per K tile = 64-byte rows
 constexpr int LROW = 40;                    // bf16 per LDS row: 32 + 8 pad (80-byte pitch: conflict-free ds_read_b128 / ds_write_b128)
 
 struct X3Params {
-    const unsigned short *Ah, *Al, *Bh, *Bl;   // planes, row-major [rows][K]
+    const unsigned short *Ah, *Al, *Bh, *Bl;   // planes, row-major: B [N][K] dense, A [M][K] with row stride lda (>= K: a column slice of a wider plane buffer)
     float* C; int ldc;                         // fp32 result (nullable when the planes below are given)
     unsigned short *Oh, *Ol;                   // optional: the result ALSO / INSTEAD as (hi, lo) bf16 planes [M][N] -- the A operand of the next split-bf16 product
     int M, N, K;
     act_gemm_epilogue_t epi;
     const float* b_inv; float a_inv, o_scale;  // F16 form: 1 / s_B[n], 1 / s_A, and the scale the planes-out are split at (the next product's s_A)
     // A32 form: A arrives as fp32 [M][K] (row stride lda) and its planes are those of relu(A * a_sc[k] + a_sh[k]) * a_fold, made while the tile is staged
-    const float *A32, *a_sc, *a_sh; int lda; float a_fold;
+    const float *A32, *a_sc, *a_sh; int lda; float a_fold;   // (lda: the row stride of A in either form, in elements of that form)
     int group;                                 // GMAX form: rows per group (32 or 64); C = out [M / group][N] (row stride ldc), the max over each group's rows
 };
 
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
             for (int j = 0; j < TN; ++j) acc[x][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int srow = tid >> 2, sch = tid & 3;                 // staging: (row, 16-byte chunk) of a [rows][32 bf16] plane tile
-    const int lda = A32 ? p.lda : K;                          // A32: this thread's eight k of a row are two 16-byte fp32 loads (set 0: k .. k+3, set 1: k+4 .. k+7)
+    const int lda = p.lda;                                    // A32: this thread's eight k of a row are two 16-byte fp32 loads (set 0: k .. k+3, set 1: k+4 .. k+7)
     const size_t goa = (size_t)(m0 + srow) * lda + sch * 8, gob = (size_t)(n0 + srow) * K + sch * 8;
     const float* gA32[2] = {A32 ? p.A32 + goa : nullptr, A32 ? p.A32 + goa + 4 : nullptr};
     const unsigned short* gA[2] = {A32 ? nullptr : p.Ah + goa, A32 ? nullptr : p.Al + goa};
@@ -181,7 +183,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
             if constexpr (A32)                                                                                                         \
                 RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA32[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * BK); \
             else                                                                                                                       \
-                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * K : ta) + (T) * BK);  \
+                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * BK); \
         _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
             RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (X3_WHOLE(i_, BN) ? (long long)(RP * i_) * K : tb) + (T) * BK);      \
     }
@@ -350,25 +352,31 @@ int launch_x3_gmax(const X3Params& p, bool a32, hipStream_t s) {
 
 // the argument-checked split pass of both formats (the bf16 form reads neither scale)
 template <bool F16>
-int split_planes(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* p1, uint16_t* p2, act_stream_t stream) {
+int split_planes(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* p1, uint16_t* p2, int ldp, act_stream_t stream) {
     if (!x || !p1 || !p2) return ACT_E_NULLPTR;
     if (R < 0 || K <= 0 || (K & 3) || ldx < K || (ldx & 3) || (F16 && !(scale > 0.f)) || (((uintptr_t)x | (uintptr_t)p1 | (uintptr_t)p2) & 15)) return ACT_E_BADARG;
+    if (ldp < K || (ldp != K && (ldp & 7))) return ACT_E_BADARG;      // strided rows keep every row of a plane 16-byte aligned
     const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
     long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
-    hipLaunchKernelGGL(split_planes_kernel<F16>, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, row_scale, p1, p2);
+    hipLaunchKernelGGL(split_planes_kernel<F16>, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, ldp / 4, n4, scale, row_scale, p1, p2);
     ACT_LAUNCH_CHECK(); return 0;
 }
 
 }  // namespace
 
 extern "C" int act_split_bf16x2_f32(const float* x, int R, int K, int ldx, uint16_t* hi, uint16_t* lo, act_stream_t stream) {
-    return split_planes<false>(x, R, K, ldx, 0.f, nullptr, hi, lo, stream);
+    return split_planes<false>(x, R, K, ldx, 0.f, nullptr, hi, lo, K, stream);
 }
 extern "C" int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2,
                                    act_stream_t stream) {
-    return split_planes<true>(x, R, K, ldx, scale, row_scale, h1, h2, stream);
+    return split_planes<true>(x, R, K, ldx, scale, row_scale, h1, h2, K, stream);
+}
+// the same planes (bit for bit) with rows ldp elements apart: a column slice of a wider plane buffer (ldp >= K, ldp % 8 == 0)
+extern "C" int act_split_f16x2_ld_f32(const float* x, int R, int K, int ldx, float scale, uint16_t* h1, uint16_t* h2, int ldp, act_stream_t stream) {
+    if (ldp & 7) return ACT_E_BADARG;
+    return split_planes<true>(x, R, K, ldx, scale, nullptr, h1, h2, ldp, stream);
 }
 
 extern "C" int act_sgemm_nt_bf16x3_supported(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && M % 128 == 0 && N % 128 == 0 && K % 64 == 0; }
@@ -407,14 +415,17 @@ bool x3_only_128() {                                               // ACT_X3_TIL
 // scale the planes-out are split at; tile: 0 = the rule above, 128 / 192 forced); the bf16 form reads none of them and runs the 128 x 128 tile
 template <bool F16>
 int multiply_planes(int M, int N, int K, const uint16_t* a1, const uint16_t* a2, float a_scale, const uint16_t* b1, const uint16_t* b2, const float* b_inv,
-                    float* C, int ldc, uint16_t* o1, uint16_t* o2, float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
+                    float* C, int ldc, uint16_t* o1, uint16_t* o2, float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile,
+                    int lda = 0) {                                  // lda: row stride of the A planes (0 = dense, K)
+    if (lda == 0) lda = K;
+    if (lda < K || (lda & 7)) return ACT_E_BADARG;                  // (K % 64 == 0: the dense stride passes) every row of a plane 16-byte aligned
     if (!a1 || !a2 || !b1 || !b2 || (F16 && !b_inv) || (!C && !o1) || ((o1 == nullptr) != (o2 == nullptr))) return ACT_E_NULLPTR;
     if (!act_sgemm_nt_bf16x3_supported(M, N, K) || (C && ldc < N) || (F16 && (!(a_scale > 0.f) || (o1 && !(out_scale > 0.f))))) return ACT_E_BADARG;
     if ((((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)b_inv) & 15)) return ACT_E_BADARG;
     if (F16 && tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;       // a forced tile that the shape does not take
     if (F16 && tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
-    p.Ah = a1; p.Al = a2; p.Bh = b1; p.Bl = b2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = o1; p.Ol = o2;
+    p.Ah = a1; p.Al = a2; p.Bh = b1; p.Bl = b2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = o1; p.Ol = o2; p.lda = lda;
     if (F16) { p.b_inv = b_inv; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale; }
     if (epilogue) p.epi = *epilogue; else { p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; }
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
@@ -435,7 +446,7 @@ extern "C" int act_split_f16x2_affine_relu_f32(const float* x, int R, int K, int
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
     long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
-    hipLaunchKernelGGL((split_planes_kernel<true, true>), dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, n4, scale, nullptr, h1, h2, col_scale, col_shift);
+    hipLaunchKernelGGL((split_planes_kernel<true, true>), dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, K / 4, n4, scale, nullptr, h1, h2, col_scale, col_shift);
     ACT_LAUNCH_CHECK(); return 0;
 }
 extern "C" int act_sgemm_nt_f16x3_gmax_supported(int M, int N, int K, int group) {
@@ -454,7 +465,7 @@ extern "C" int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, 
     if (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;
     if (tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_gmax_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
-    p.A32 = A; p.lda = lda; p.a_sc = a_col_scale; p.a_sh = a_col_shift; p.a_fold = a_scale; p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2;
+    p.A32 = A; p.lda = a32 ? lda : K; p.a_sc = a_col_scale; p.a_sh = a_col_shift; p.a_fold = a_scale; p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2;
     p.C = out; p.ldc = ldo; p.M = M; p.N = N; p.K = K; p.group = group; p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale;
     p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; p.epi.bias = bias;
     hipStream_t s = (hipStream_t)stream;
@@ -481,4 +492,11 @@ extern "C" int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uin
                                                   const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
                                                   float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
     return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile);
+}
+// A planes as a column slice of a wider plane buffer: rows lda elements apart (lda >= K, lda % 8 == 0, a_h1 / a_h2 16-byte aligned); otherwise the entry above
+extern "C" int act_sgemm_nt_f16x3_planes_lda_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, int lda, float a_scale, const uint16_t* b_h1,
+                                                 const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                                 float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
+    if (lda <= 0) return ACT_E_BADARG;
+    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile, lda);
 }

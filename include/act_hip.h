@@ -427,6 +427,8 @@ int act_sgemm_nt_bf16x3_planes_f32(int M, int N, int K, const uint16_t* a_hi, co
  * act_split_f16x2_f32: planes of x * scale * row_scale[row] (row_scale nullable).  b_inv_scale [N] = 1 / (B's row scales), 16-byte aligned.
  * out_h1 / out_h2 (nullable pair): the result also (C != NULL) or only as planes [M][N] of result * out_scale.  Shapes as act_sgemm_nt_bf16x3_supported. */
 int act_split_f16x2_f32(const float* x, int R, int K, int ldx, float scale, const float* row_scale, uint16_t* h1, uint16_t* h2, act_stream_t stream);
+/* the same planes, bit for bit, written with rows ldp elements apart (ldp >= K, ldp % 8 == 0, h1 / h2 16-byte aligned): a column slice of a wider plane buffer */
+int act_split_f16x2_ld_f32(const float* x, int R, int K, int ldx, float scale, uint16_t* h1, uint16_t* h2, int ldp, act_stream_t stream);
 int act_sgemm_nt_f16x3_supported(int M, int N, int K);
 int act_sgemm_nt_f16x3_planes_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
                                   const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2, float out_scale,
@@ -440,6 +442,11 @@ int act_sgemm_nt_f16x3_pick_tile(int M, int N, int K, int cus);
 int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1,
                                        const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
                                        float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile);
+/* ..._planes_lda_f32: the same product with the rows of the A planes lda elements apart -- a column slice of a wider plane buffer (lda >= K, lda % 8 == 0, a_h1 and
+ * a_h2 16-byte aligned; anything else is ACT_E_BADARG and launches nothing).  lda == K is the entry above, bit for bit. */
+int act_sgemm_nt_f16x3_planes_lda_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, int lda, float a_scale, const uint16_t* b_h1,
+                                      const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
+                                      float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile);
 /* the plane producers in this format: bit-identical to producing fp32 and splitting it with act_split_f16x2_f32 at plane_scale */
 int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                      uint16_t* y_h1, uint16_t* y_h2, float plane_scale, float* mean /* nullable */, float* rstd /* nullable */, int T, int D,
@@ -707,13 +714,22 @@ int act_dgcnn_features_f32(const act_dgcnn_t* m, const float* f, const int64_t* 
  * with the planes of w5 (act_split_f16x2_f32 with the row scales whose inverses are w5_inv_scale [Cout]).  w5_planes = the h1 plane, the h2 plane Cout * 2304
  * elements behind it; a_planes = scratch for the planes of cat, >= 2 * T * 2304 elements.  Everything up to cat is act_dgcnn_features_f32's, bit for bit.
  * x3 unusable -- NULL, a NULL pointer in it, a_scale <= 0, a_planes_elems too small, or !act_sgemm_nt_f16x3_supported(T, Cout, 2304) -- runs the f32 head
- * product: the result then equals act_dgcnn_features_f32 bit for bit. */
+ * product: the result then equals act_dgcnn_features_f32 bit for bit.
+ * layers != 0: the stacked edge-conv products of layers 2-4 (T x 2 cout x cin against the frozen [Wa ; Wb - Wa]) run on the same kernel as well.  st_planes[i] /
+ * st_inv_scale[i] (i = 0..2: layers 2, 3, 4) are the planes (h2 plane 2 cout cin elements behind h1) and inverse row scales of stacked[i + 1].  Each tail's
+ * fp32 slice of cat is split into a_planes at its column, at the same a_scale (the bound covers all four tails), row stride 2304; the next layer reads its A
+ * operand there (act_sgemm_nt_f16x3_planes_lda_f32) and the head multiplies the planes that are then already complete -- the same bytes the whole-cat pass
+ * writes.  With layers != 0, w5_planes may be NULL (or the head's shape refused): the head alone then stays on the f32 kernel.  With layers != 0 a NULL layer
+ * pointer, a_scale <= 0, a short or NULL a_planes or T % 128 != 0 run the whole f32 sequence: act_dgcnn_features_f32 bit for bit. */
 typedef struct {
     const uint16_t* w5_planes;
     const float* w5_inv_scale;
     float a_scale;
     uint16_t* a_planes;
     size_t a_planes_elems;
+    int layers;
+    const uint16_t* st_planes[3];
+    const float* st_inv_scale[3];
 } act_dgcnn_f16x3_t;
 int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
                                  float* workspace, size_t workspace_bytes, act_stream_t stream);
