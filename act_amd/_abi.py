@@ -361,6 +361,10 @@ _TABLE = {
     "act_affine_add_relu_f32": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "act_bn_add_relu_bwd_workspace": (_sz, [_i, _i]),
     "act_bn_add_relu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    # PCT: offset attention (csrc/offset_attn.hip)
+    "act_offset_attn_workspace": (_sz, [_i, _i, _i, _i]),
+    "act_offset_attn_fwd_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "act_offset_attn_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp],
 }
 
 # name -> (restype, argtypes) for every function of the header

@@ -25,7 +25,7 @@ PER_FILE = {"point_ops.hip": ["-ffp-contract=off"], "chamfer.hip": ["-ffp-contra
             "augment.hip": ["-ffp-contract=off"], "emd.hip": ["-ffp-contract=off"], "sa.hip": ["-ffp-contract=off"],
             "s3dis_sample.hip": ["-ffp-contract=off"], "cloud_sample.hip": ["-ffp-contract=off"],
             "edgeconv.hip": ["-ffp-contract=off"], "edge_mlp2.hip": ["-ffp-contract=off"],
-            "pointmlp.hip": ["-ffp-contract=off"]}
+            "pointmlp.hip": ["-ffp-contract=off"], "offset_attn.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

@@ -3009,3 +3009,65 @@ def batch_norm_add_relu(y, res, bn, training):
     if training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return BNAddReluFn.apply(y, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, bn.momentum, bn.eps)
+
+
+# ---- PCT (csrc/offset_attn.hip): offset attention ---------------------------------------------------------------------------------------------------------
+class OffsetAttentionFn(torch.autograd.Function):
+    """PCT's offset attention on rows: softmax over the keys without a scale, L1 over the queries, x_r = P^t v / (1e-9 + colsum), optionally x - x_r.
+    Saved for the backward: colsum [B*N] and x_r (the output itself when x is not fused); the backward forms the row statistics again instead of
+    trusting lse rounded to float32.  No [N,N] tensor in either direction."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, x, B, N):
+        Dq, C = q.shape[1], v.shape[1]
+        dev = q.device
+        out = torch.empty_like(v)
+        lse, colsum = torch.empty(B * N, dtype=torch.float32, device=dev), torch.empty(B * N, dtype=torch.float32, device=dev)
+        xr = torch.empty_like(v) if x is not None and any(ctx.needs_input_grad[:3]) else None
+        ws = workspace(dev, lib.act_offset_attn_workspace(B, N, Dq, C))
+        rc = lib.act_offset_attn_fwd_f32(ptr(q), ptr(k), ptr(v), ptr(x), B, N, Dq, C, ptr(out), ptr(lse), ptr(colsum), ptr(xr), ptr(ws), ws.numel() * 4,
+                                         stream())
+        if rc == -1:
+            raise ValueError(f"act_offset_attn_fwd_f32 refused B={B}, N={N}, Dq={Dq}, C={C}")
+        check(rc, "act_offset_attn_fwd_f32")
+        ctx.save_for_backward(q, k, v, colsum, out if x is None else xr)
+        ctx.cfg = (B, N, x is not None)
+        ctx.mark_non_differentiable(lse, colsum)
+        return out, lse, colsum
+
+    @staticmethod
+    def backward(ctx, dout, _dlse, _dcolsum):
+        q, k, v, colsum, xr = ctx.saved_tensors
+        B, N, fused = ctx.cfg
+        dout = _f32c(dout, "offset_attention: grad")
+        dx = dout if fused and ctx.needs_input_grad[3] else None
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, dx, None, None
+        Dq, C = q.shape[1], v.shape[1]
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        ws = workspace(q.device, lib.act_offset_attn_workspace(B, N, Dq, C))
+        check(lib.act_offset_attn_bwd_f32(ptr(q), ptr(k), ptr(v), ptr(colsum), ptr(xr), ptr(dout), int(fused), B, N, Dq, C, ptr(dq), ptr(dk), ptr(dv),
+                                          ptr(ws), ws.numel() * 4, stream()), "act_offset_attn_bwd_f32")
+        return dq, dk, dv, dx, None, None
+
+
+def offset_attention(q, k, v, B, N, x=None, want_aux=False):
+    """q, k [B*N, Dq], v [B*N, C] and optionally x [B*N, C] -> x_r [B*N, C] (or x - x_r): per cloud P = softmax_j(q_i . k_j) without a scale,
+    x_r[j] = sum_i P[i,j] v_i / (1e-9 + sum_i P[i,j]).  Differentiable in q, k, v and x; q and k may be one tensor (autograd adds dq and dk).
+    ``want_aux``: also lse [B*N] and the column sums [B*N].  1 <= N <= 1024, Dq % 4 == 0 in [4, 64], C % 4 == 0 in [4, 256], else ValueError."""
+    B, N = int(B), int(N)
+    for t, name in ((q, "q"), (k, "k"), (v, "v")) + (((x, "x"),) if x is not None else ()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _C.ActHipError(f"offset_attention: {name}: expected a CUDA tensor (the HIP kernels have no CPU fallback)")
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise _C.ActHipError(f"offset_attention: {name}: expected a float32 tensor of two dimensions, got {t.dtype} {list(t.shape)}")
+    Dq, C = q.shape[1], v.shape[1]
+    if not (1 <= B <= 65535 and 1 <= N <= 1024 and 4 <= Dq <= 64 and Dq % 4 == 0 and 4 <= C <= 256 and C % 4 == 0):
+        raise ValueError(f"offset_attention: need 1 <= N <= 1024, Dq % 4 == 0 in [4, 64] and C % 4 == 0 in [4, 256], got B={B}, N={N}, Dq={Dq}, C={C}")
+    if tuple(q.shape) != (B * N, Dq) or tuple(k.shape) != (B * N, Dq) or tuple(v.shape) != (B * N, C) or (x is not None and x.shape != v.shape):
+        raise ValueError(f"offset_attention: expected q, k [{B * N}, Dq] and v, x [{B * N}, C], got {list(q.shape)}, {list(k.shape)}, {list(v.shape)}"
+                         + (f", {list(x.shape)}" if x is not None else ""))
+    same = k is q
+    q = q.contiguous()
+    out, lse, colsum = OffsetAttentionFn.apply(q, q if same else k.contiguous(), v.contiguous(), None if x is None else x.contiguous(), B, N)
+    return (out, lse, colsum) if want_aux else out

@@ -5,3 +5,4 @@ from . import bert  # noqa: F401
 from . import pointnet2_nets  # noqa: F401
 from . import dgcnn_nets  # noqa: F401
 from . import pointmlp  # noqa: F401
+from . import pct  # noqa: F401

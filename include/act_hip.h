@@ -1161,6 +1161,27 @@ size_t act_bn_add_relu_bwd_workspace(int R, int C);
 int act_bn_add_relu_bwd_f32(const float* y, const float* out, const float* dout, const float* gamma, const float* mean, float eps, int R, int C,
                             float* dy, float* dres, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, act_stream_t stream);
 
+/* ---- PCT offset attention (csrc/offset_attn.hip; Guo et al., CVM 2021) ------------------------------------------------------------------------ */
+/* Per cloud, rows q [N,Dq], k [N,Dq], v [N,C] and, optionally, x [N,C] (all fp32, clouds stacked: [B*N, .]):
+ *   E[i,j] = q_i . k_j (no scale)     P[i,j] = exp(E[i,j] - lse_i), lse_i = max_j E[i,j] + log sum_j exp(E[i,j] - max)     (softmax over the keys)
+ *   c_j = sum_i P[i,j]                s_j = 1 / (1e-9f + c_j)                                                               (L1 over the queries)
+ *   x_r[j] = s_j sum_i P[i,j] v_i     out[j] = x_r[j], or x[j] - x_r[j] when x != NULL
+ * Written: out [B*N,C], lse [B*N], colsum [B*N] (c_j) and, when xr != NULL, x_r [B*N,C].  Both products run on v_mfma_f32_16x16x4_f32; no [N,N]
+ * tensor reaches memory.  Fixed summation order, no atomics: a cloud's result does not depend on B and is bit-identical run to run.
+ * 1 <= N <= 1024 (any N), 4 <= Dq <= 64 and Dq % 4 == 0, 4 <= C <= 256 and C % 4 == 0, 1 <= B <= 65535, else ACT_E_BADARG with nothing written.
+ * The workspace (16-byte aligned) is shared by both directions. */
+size_t act_offset_attn_workspace(int B, int N, int Dq, int C);
+int act_offset_attn_fwd_f32(const float* q, const float* k, const float* v, const float* x, int B, int N, int Dq, int C, float* out, float* lse,
+                            float* colsum, float* xr, void* workspace, size_t workspace_bytes, act_stream_t stream);
+/* its backward from colsum and x_r; the row statistics behind lse are formed again (one Dq-deep sweep), because lse rounded to fp32 is a common
+ * factor of up to 1 +- 4e-8 |lse| on a whole row of P.  g_j is the cotangent of x_r[j]: dout_j, or -dout_j with negate != 0 (the fused x, whose own gradient is
+ * dout).  D_j = g_j . x_r[j], dP[i,j] = s_j (v_i . g_j - D_j), R_i = sum_j P dP, dE = P (dP - R_i); dq_i = sum_j dE k_j, dk_j = sum_i dE q_i,
+ * dv_i = sum_j P[i,j] s_j g_j.  dq and dk are written separately (dq == dk is ACT_E_BADARG); q and k may be one tensor.  P and dP are recomputed
+ * tile by tile in three sweeps (R and dv; dq; dk), all products on the matrix cores. */
+int act_offset_attn_bwd_f32(const float* q, const float* k, const float* v, const float* colsum, const float* xr, const float* dout, int negate,
+                            int B, int N, int Dq, int C, float* dq, float* dk, float* dv, void* workspace, size_t workspace_bytes,
+                            act_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
