@@ -54,7 +54,7 @@ class VitBf16x3(ctypes.Structure):                     # act_vit_bf16x3_t
 
 
 class VitF16x3(ctypes.Structure):                      # act_vit_f16x3_t
-    _fields_ = [("w_planes", _vp), ("w_inv_scale", _vp), ("a_scale", _vp), ("a_planes", _vp), ("a_planes_elems", _sz)]
+    _fields_ = [("w_planes", _vp), ("w_inv_scale", _vp), ("a_scale", _vp), ("a_planes", _vp), ("a_planes_elems", _sz), ("w_layout", _i)]
 
 
 class PointnetParams(ctypes.Structure):                # act_pointnet_params_t
@@ -77,11 +77,11 @@ class Dgcnn(ctypes.Structure):                         # act_dgcnn_t
 
 class DgcnnF16x3(ctypes.Structure):                    # act_dgcnn_f16x3_t
     _fields_ = [("w5_planes", _vp), ("w5_inv_scale", _vp), ("a_scale", _f), ("a_planes", _vp), ("a_planes_elems", _sz), ("layers", _i),
-                ("st_planes", _vp * 3), ("st_inv_scale", _vp * 3)]
+                ("st_planes", _vp * 3), ("st_inv_scale", _vp * 3), ("w_layout", _i)]
 
 
 class PointnetF16x3(ctypes.Structure):                 # act_pointnet_f16x3_t
-    _fields_ = [("c4_planes", _vp), ("c4_inv_scale", _vp), ("a_scale", _f)]
+    _fields_ = [("c4_planes", _vp), ("c4_inv_scale", _vp), ("a_scale", _f), ("w_layout", _i)]
 
 
 class AugmentOp(ctypes.Structure):                     # act_augment_op_t
@@ -201,6 +201,11 @@ _TABLE = {
     "act_sgemm_nt_f16x3_pick_tile": [_i, _i, _i, _i],
     "act_sgemm_nt_f16x3_planes_tile_f32": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
     "act_sgemm_nt_f16x3_planes_lda_f32": [_i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _epi, _vp, _i],
+    # K-tile-major planes
+    "act_repack_ktile_u16": [_vp, _vp, _i, _i, _vp],
+    "act_split_f16x2_kt_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _i, _vp],
+    "act_sgemm_nt_f16x3_planes_layout_f32": [_i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _f, _i, _epi, _vp, _i],
+    "act_x3_kt": [_i],
     "act_layernorm_fwd_f16_planes_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _f, _vp],
     "act_attention_fwd_prefix_f16_planes_f32": [_vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _f, _vp],
     "act_prompt_layernorm_fwd_f16_planes_f32": [_vp, _vp, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp],
@@ -208,6 +213,7 @@ _TABLE = {
     "act_sgemm_nt_f16x3_gmax_supported": [_i, _i, _i, _i],
     "act_sgemm_nt_f16x3_gmax_pick_tile": [_i, _i, _i, _i],
     "act_sgemm_nt_f16x3_gmax_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "act_sgemm_nt_f16x3_gmax_layout_f32": [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
     # GEMM launch-configuration table
     "act_gemm_tune_set": [_i] * 7,
     "act_gemm_tune_get": [_i] * 5 + [_P(_i), _P(_i)],
@@ -236,6 +242,7 @@ _TABLE = {
     "act_prompt_kv_fwd_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp],
     "act_prompt_kv_f16x3": [_i],
     "act_prompt_kv_fwd_f16x3_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _i, _vp],
+    "act_prompt_kv_fwd_f16x3_layout_f32": [_vp, _vp, _i, _i, _i, _i, _f, _u64, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _f, _vp, _vp, _vp, _sz, _i, _vp],
     "act_prefix_block_bwd_scratch_floats": (_sz, [_dims, _i]),
     "act_prefix_block_bwd_f32": [_dims, _i, _blk, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "act_prefix_vit_scratch_floats": (_sz, [_P(PrefixVit)]),

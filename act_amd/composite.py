@@ -318,6 +318,13 @@ TOKENIZER_PN_F16X3 = os.environ.get("ACT_TOKENIZER_PN_F16X3", "1") != "0"
 # 128 x 128) does not fill one round of 256 CUs, the regime in which the split kernel has nothing over the f32 one (the rule that keeps the 384-wide head of dgcnn_2
 # off it).  ACT_TOKENIZER_DGCNN_F16X3=0 restores the f32 products bit for bit; each switch governs its own products.
 TOKENIZER_DGCNN_F16X3 = os.environ.get("ACT_TOKENIZER_DGCNN_F16X3", "1") != "0"
+# K-TILE-MAJOR PLANES of the frozen weights above (ACT_X3_KT, default 1; kernels.x3_kt; notebook/x3_ktile.md): the weight planes are repacked once, when they are
+# built, into the layout in which the split-f16 kernel stages a tile in whole 128-byte lines -- the same bits, fewer half-used lines.  Which products keep it is what
+# the per-launch trace decided (a product keeps it where its median gain passed the parent launch's own max - min): of the teacher's Linears fc1 and fc2
+# (bits of X3_KT_VIT: qkv, proj, fc1, fc2 -- qkv, with the prompt keys / values, and proj gained less than their spread), the tokenizer head and the stacked
+# DGCNN matrices; the mini-PointNet's last product gained less than its spread and stays row-major.
+X3_KT_VIT = 0b1100
+X3_KT_PN = False
 DGCNN_F16X3_MIN_T = 4096
 _PN_F16 = weakref.WeakKeyDictionary()          # Encoder -> (signature, c4 planes, inverse row scales, max|gamma|, max|beta| of bn2, {R: a_scale})
 # DGCNN -> [signature, w5 planes, inverse row scales, max|gamma|, max|beta|, couts, groups, {(G, k): a_scale}, (planes, inverse row scales) of stacked[1..3]];
@@ -630,13 +637,15 @@ def _vit_f16_planes(tok, ts, depth, act_elems, dev):
     activation scale of every Linear from the range guard -- all computed ONCE and cached per tokenizer under the (address, version) signature of every block
     tensor (the guard reads the LayerNorm parameters and biases too).  -> (VitF16x3, keep-alive)"""
     blk = ts[10:10 + _NPB * depth]
-    sig = tuple((t.data_ptr(), t._version) if t is not None else None for t in blk)
+    kt = X3_KT_VIT if K.x3_kt() else 0           # ACT_X3_KT: these planes are kept K-tile-major (the only copy); a turn of the switch rebuilds them
+    sig = tuple((t.data_ptr(), t._version) if t is not None else None for t in blk) + (kt,)
     cache = _VIT_F16.get(tok)
     if cache is None or cache[0] != sig:
         ws_ = [ts[10 + _NPB * i + j] for i in range(depth) for j in (2, 4, 8, 10)]                # qkv_w, proj_w, fc1_w, fc2_w
         with torch.no_grad():
             scales = [K.f16x3_row_scales(w) for w in ws_]
             planes = [K.split_f16x2(w.detach(), 1.0, sc[0]) for w, sc in zip(ws_, scales)]
+            planes = [K.repack_ktile(pl) if (kt >> (j % 4)) & 1 else pl for j, pl in enumerate(planes)]
             inv = [sc[1].contiguous() for sc in scales]
             a_scale = [f16x3_act_scale(b) for b in f16x3_vit_bounds(ts, depth, ws_[0].shape[1]).flatten().tolist()]
         parr = (_vp * len(planes))(*[pl.data_ptr() for pl in planes])
@@ -645,7 +654,7 @@ def _vit_f16_planes(tok, ts, depth, act_elems, dev):
         cache = _VIT_F16[tok] = (sig, planes, inv, a_scale, (parr, iarr, sarr))
     a_planes = torch.empty(2 * act_elems, dtype=torch.float16, device=dev)
     parr, iarr, sarr = cache[4]
-    x3 = VitF16x3(ctypes.cast(parr, _vp), ctypes.cast(iarr, _vp), ctypes.cast(sarr, _vp), a_planes.data_ptr(), a_planes.numel())
+    x3 = VitF16x3(ctypes.cast(parr, _vp), ctypes.cast(iarr, _vp), ctypes.cast(sarr, _vp), a_planes.data_ptr(), a_planes.numel(), cache[0][-1])
     return x3, (a_planes, cache)
 
 
@@ -718,13 +727,16 @@ def _pointnet_f16_planes(enc, R):
     (read to the host HERE, never per step) -- computed ONCE and cached per Encoder under the (address, version) signature of the three tensors
     (load_state_dict copies in place); the activation scale is host arithmetic from those and the call's row count.  -> (PointnetF16x3, keep-alive)"""
     bn2, c4 = enc.second_conv[1], enc.second_conv[3]
-    sig = tuple((t.data_ptr(), t._version) for t in (c4.weight, bn2.weight, bn2.bias))
+    kt = bool(X3_KT_PN and K.x3_kt())            # ACT_X3_KT: the planes are kept K-tile-major (the only copy); a turn of the switch rebuilds them
+    sig = tuple((t.data_ptr(), t._version) for t in (c4.weight, bn2.weight, bn2.bias)) + (kt,)
     cache = _PN_F16.get(enc)
     if cache is None or cache[0] != sig:
         with torch.no_grad():
             w = c4.weight.detach().reshape(c4.weight.shape[0], c4.weight.shape[1])
             scale, inv = K.f16x3_row_scales(w)
             planes = K.split_f16x2(w, 1.0, scale)
+            if kt:
+                planes = K.repack_ktile(planes)
             inv = inv.contiguous()
             gmax, bmax = torch.stack([bn2.weight.detach().double().abs().max(), bn2.bias.detach().double().abs().max()]).tolist()
         cache = _PN_F16[enc] = (sig, planes, inv, gmax, bmax, {})
@@ -732,7 +744,7 @@ def _pointnet_f16_planes(enc, R):
     a_scale = scales.get(R)
     if a_scale is None:
         a_scale = scales[R] = f16x3_act_scale(f16x3_pointnet_bound(gmax, bmax, R))
-    return PointnetF16x3(planes.data_ptr(), inv.data_ptr(), a_scale), cache
+    return PointnetF16x3(planes.data_ptr(), inv.data_ptr(), a_scale, int(cache[0][-1])), cache
 
 
 def pointnet_forward(enc, point_groups, need=None):
@@ -815,7 +827,8 @@ def _dgcnn_f16_planes(dg, T, G, k, dev, head=True, layers=None):
     convs = [layer[0] for layer in (dg.layer2, dg.layer3, dg.layer4)]
     gns = [layer[1] for layer in (dg.layer1, dg.layer2, dg.layer3, dg.layer4)]
     w5 = dg.layer5[0].weight
-    sig = tuple((t.data_ptr(), t._version) for t in [w5] + [t for gn in gns for t in (gn.weight, gn.bias)] + [c.weight for c in convs])
+    kt = K.x3_kt()                               # ACT_X3_KT: the planes are kept K-tile-major (the only copy); a turn of the switch rebuilds them
+    sig = tuple((t.data_ptr(), t._version) for t in [w5] + [t for gn in gns for t in (gn.weight, gn.bias)] + [c.weight for c in convs]) + (kt,)
     cache = _DGCNN_F16.get(dg)
     if cache is None or cache[0] != sig:
         with torch.no_grad():
@@ -824,7 +837,8 @@ def _dgcnn_f16_planes(dg, T, G, k, dev, head=True, layers=None):
 
     def planes_of(w):
         scale, inv = K.f16x3_row_scales(w)
-        return K.split_f16x2(w, 1.0, scale), inv.contiguous()
+        planes = K.split_f16x2(w, 1.0, scale)
+        return (K.repack_ktile(planes) if kt else planes), inv.contiguous()
     if head and cache[1] is None:
         with torch.no_grad():
             cache[1], cache[2] = planes_of(w5.detach().reshape(w5.shape[0], w5.shape[1]))
@@ -837,6 +851,7 @@ def _dgcnn_f16_planes(dg, T, G, k, dev, head=True, layers=None):
         a_scale = scales[(G, k)] = f16x3_act_scale(f16x3_dgcnn_bound(gmax, bmax, couts, groups, G, k))
     a_planes = torch.empty(2 * T * sum(couts), dtype=torch.float16, device=dev)
     x3 = DgcnnF16x3(planes.data_ptr() if head else None, inv.data_ptr() if head else None, a_scale, a_planes.data_ptr(), a_planes.numel())
+    x3.w_layout = int(kt)
     if layers:
         x3.layers = 1
         for i, (p, v) in enumerate(st):

@@ -137,10 +137,21 @@ size_t carve_prefix_bwd(float* base, const act_block_dims_t& d, int P, PrefixBwd
 // One frozen Linear whose weight is given as planes: w1 = its first plane (hi / h1), w2 = its second (lo / h2); null = this Linear stays on the f32 kernel (no
 // planes given, or the range guard of the f16 form gave no activation scale).  a_fmt = the format its A operand is split in: bf16 for the opt-in path, f16 at
 // this Linear's static activation scale s_A for the default one, which also needs inv = 1 / s_B per output row.
-struct X3Linear { const uint16_t *w1, *w2; const float* inv; PlaneFmt a_fmt; };
-inline X3Linear x3_linear_of(const uint16_t* planes, size_t plane_elems, PlaneFmt a_fmt, const float* inv = nullptr) {
-    return X3Linear{planes, planes ? planes + plane_elems : nullptr, inv, a_fmt};
+// layout / rows_total (f16 form): where the weight planes lie -- ACT_X3_KTILE: K-tile-major planes of a [rows_total][K] matrix (gemm_bf16x3.hip), w1 / w2 at this
+// Linear's first row of them
+struct X3Linear { const uint16_t *w1, *w2; const float* inv; PlaneFmt a_fmt; int layout = ACT_X3_ROWMAJOR, rows_total = 0; };
+inline X3Linear x3_linear_of(const uint16_t* planes, size_t plane_elems, PlaneFmt a_fmt, const float* inv = nullptr, int layout = ACT_X3_ROWMAJOR,
+                             int rows_total = 0) {
+    return X3Linear{planes, planes ? planes + plane_elems : nullptr, inv, a_fmt, layout, rows_total};
 }
+// rows r0 .. of a Linear's weight as a Linear of its own (the K,V rows of qkv): r0 rows of K elements further row-major, r0 pieces of a K tile further K-tile-major
+inline X3Linear x3_rows_from(const X3Linear& l, size_t r0, size_t K) {
+    const size_t o = l.layout == ACT_X3_KTILE ? r0 * 32 : r0 * K;
+    return X3Linear{l.w1 + o, l.w2 + o, l.inv ? l.inv + r0 : nullptr, l.a_fmt, l.layout, l.rows_total};
+}
+// ACT_X3_KT (default on): frozen weight planes are kept K-tile-major by the callers that build them, and the producers of this file (the MLP's hidden activation,
+// the tokenizer's cat planes) hand their planes on that way to a product whose weight is K-tile-major.  Off: the row-major step, bit for bit the same results.
+static std::atomic<int> g_x3_kt{[] { const char* e = getenv("ACT_X3_KT"); return !(e && e[0] == '0') ? 1 : 0; }()};
 // "is this shape taken": the Linear has planes and the kernel of its format takes M x N x K
 inline bool x3_takes(const X3Linear& l, int M, int N, int K) {
     return l.w1 && (l.a_fmt.is_f16() ? act_sgemm_nt_f16x3_supported(M, N, K) : act_sgemm_nt_bf16x3_supported(M, N, K));
@@ -152,21 +163,23 @@ int x3_split(PlaneFmt fmt, const float* A, int M, int K, uint16_t* dst, hipStrea
 }
 // C [M, N] = epi(a . W^T) with a = the planes of A in l.a_fmt; `emit`: the result leaves as planes in emit_fmt there INSTEAD of fp32 C -- the A operand of the
 // next Linear, so emit_fmt is that Linear's a_fmt
+// (f16 form) a_kt: the planes at a are K-tile-major [M][K]; emit_kt: the planes at emit leave K-tile-major [M][N]
 int x3_multiply(const X3Linear& l, int M, int N, int K, const uint16_t* a, float* C, uint16_t* emit, PlaneFmt emit_fmt, const act_gemm_epilogue_t& e,
-                hipStream_t s) {
+                hipStream_t s, bool a_kt = false, bool emit_kt = false) {
     const uint16_t* a2 = a + (size_t)M * K; uint16_t* emit2 = emit ? emit + (size_t)M * N : nullptr;
     if (l.a_fmt.is_f16())
-        return act_sgemm_nt_f16x3_planes_f32(M, N, K, a, a2, l.a_fmt.f16_scale, l.w1, l.w2, l.inv, emit ? nullptr : C, N, emit, emit2,
-                                             emit ? emit_fmt.f16_scale : 0.f, &e, s);
+        return act_sgemm_nt_f16x3_planes_layout_f32(M, N, K, a, a2, a_kt ? ACT_X3_KTILE : ACT_X3_ROWMAJOR, 0, M, l.a_fmt.f16_scale, l.w1, l.w2, l.layout,
+                                                    l.rows_total, l.inv, emit ? nullptr : C, N, emit, emit2, emit ? emit_fmt.f16_scale : 0.f,
+                                                    emit_kt ? ACT_X3_KTILE : ACT_X3_ROWMAJOR, &e, s, 0);
     return act_sgemm_nt_bf16x3_planes_f32(M, N, K, a, a2, l.w1, l.w2, emit ? nullptr : C, N, emit, emit2, &e, s);
 }
 // split-and-multiply: A is split into `stage` first unless its planes are already there, at `pre`.  (Nothing is recorded while the GEMM shapes are collected:
 // these products are not tuned.)
 int x3_linear(const X3Linear& l, int M, int N, int K, const float* A, const uint16_t* pre, uint16_t* stage, float* C, uint16_t* emit, PlaneFmt emit_fmt,
-              const act_gemm_epilogue_t& e, hipStream_t s) {
+              const act_gemm_epilogue_t& e, hipStream_t s, bool pre_kt = false, bool emit_kt = false) {
     if (t_collect) return 0;
     if (!pre) CK(x3_split(l.a_fmt, A, M, K, stage, s));
-    return x3_multiply(l, M, N, K, pre ? pre : stage, C, emit, emit_fmt, e, s);
+    return x3_multiply(l, M, N, K, pre ? pre : stage, C, emit, emit_fmt, e, s, pre && pre_kt, emit_kt);
 }
 // LayerNorm / prefix attention whose result leaves as planes at dst (second plane T D elements further) for the Linear that multiplies it next
 int x3_layernorm(PlaneFmt fmt, const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, uint16_t* dst, float* mean, float* rstd,
@@ -225,11 +238,14 @@ int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t
     // fc2 on the split-operand kernel ONLY with its operand already there as planes: a lone fc2 would split sv.a [TG, Hd] into tmp, which holds
     // 2 * max(TG, TP) * D elements -- too small whenever Hd > D (reachable with a non-4x mlp_ratio, D % 128 == 0, Hd % 64 == 0, Hd % 128 != 0)
     const X3Linear fc2 = fc2_in ? b.fc2 : X3Linear{};
+    // the hidden activation, K = Hd the deepest product of the block, goes from fc1's epilogue to fc2 K-tile-major where fc2's weight is (the f16 default)
+    const bool hid_kt = fc2_in && fc2.layout == ACT_X3_KTILE && g_x3_kt.load() && ((uintptr_t)fc2_in & 127) == 0;
     // C = epi(A . W^T) of Linear l: on the split-operand kernel where l has planes and the shape is taken (`pre`: A's planes are already there, else A is split
     // into tmp; `emit`: the result leaves as planes there, in the format of the Linear `next` that multiplies it, instead of fp32 C), else on the f32 kernel
+    // (pre_kt / emit_kt: those planes are K-tile-major)
     auto linear = [&](const X3Linear& l, int M, int N, int K, const float* A, const float* W, float* C, const act_gemm_epilogue_t& e,
-                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr, const X3Linear* next = nullptr) -> int {
-        if (x3_takes(l, M, N, K)) return x3_linear(l, M, N, K, A, pre, tmp, C, emit, next ? next->a_fmt : PlaneFmt::bf16(), e, s);
+                      const uint16_t* pre = nullptr, uint16_t* emit = nullptr, const X3Linear* next = nullptr, bool pre_kt = false, bool emit_kt = false) -> int {
+        if (x3_takes(l, M, N, K)) return x3_linear(l, M, N, K, A, pre, tmp, C, emit, next ? next->a_fmt : PlaneFmt::bf16(), e, s, pre_kt, emit_kt);
         return gemm_nt(M, N, K, A, K, W, K, C, N, e, ws, wsb, s);
     };
     // (keep: the differentiable forward of Stage-I prompt tuning.  Its backward never needs n1x / n2 / a in fp32 -- the block weights are frozen, no dW --, only the
@@ -251,9 +267,9 @@ int prefix_block_core(const act_block_dims_t& d, int P, const act_block_params_t
     RUN(fc1_in ? x3_layernorm(b.fc1.a_fmt, sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, fc1_in, mean2, rstd2, TG, D, d.eps, s)  // planes for fc1
                : act_layernorm_fwd_f32(sv.x1, nullptr, w.norm2_w, w.norm2_b, nullptr, sv.n2, mean2, rstd2, TG, D, d.eps, s));    // f32
     e = epi0(); e.bias = w.fc1_b; e.act = ACT_EPI_GELU; e.aux = keep ? sv.hpre : nullptr; e.ldaux = Hd;
-    CK(linear(b.fc1, TG, Hd, D, sv.n2, w.fc1_w, sv.a, e, fc1_in, fc2_in, &fc2));                                                 // planes for fc2, else f32
+    CK(linear(b.fc1, TG, Hd, D, sv.n2, w.fc1_w, sv.a, e, fc1_in, fc2_in, &fc2, false, hid_kt));                                  // planes for fc2, else f32
     e = epi0(); e.bias = w.fc2_b; e.res = sv.x1; e.ldr = D;
-    CK(linear(fc2, TG, D, Hd, sv.a, w.fc2_w, out, e, fc2_in));                                                                   // f32: the block's output
+    CK(linear(fc2, TG, D, Hd, sv.a, w.fc2_w, out, e, fc2_in, nullptr, nullptr, hid_kt));                                         // f32: the block's output
     return 0;
 }
 
@@ -521,9 +537,17 @@ int act_prompt_kv_fwd_f32(const float* tok, const float* ppos, int B, int P, int
 // block's qkv Linear -- the bound sqrt(D) |gamma| + |beta| holds for any LayerNorm row), one planes product with the bias epilogue writes kv.  Two launches.
 static std::atomic<int> g_prompt_kv_f16x3{[] { const char* e = getenv("ACT_PROMPT_KV_F16X3"); return !(e && e[0] == '0') ? 1 : 0; }()};
 int act_prompt_kv_f16x3(int on) { return on < 0 ? g_prompt_kv_f16x3.load() : g_prompt_kv_f16x3.exchange(on ? 1 : 0); }
+int act_x3_kt(int on) { return on < 0 ? g_x3_kt.load() : g_x3_kt.exchange(on ? 1 : 0); }
 int act_prompt_kv_fwd_f16x3_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
                                 const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, const float* w_inv,
                                 float a_scale, const float* bias, float* kv, uint16_t* planes, size_t planes_elems, int tile, act_stream_t stream) {
+    return act_prompt_kv_fwd_f16x3_layout_f32(tok, ppos, B, P, D, N, drop_p, seed, seed_dev, gamma, beta, eps, w_h1, w_h2, ACT_X3_ROWMAJOR, 0, w_inv, a_scale, bias,
+                                              kv, planes, planes_elems, tile, stream);
+}
+int act_prompt_kv_fwd_f16x3_layout_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                       const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, int w_layout,
+                                       int w_rows_total, const float* w_inv, float a_scale, const float* bias, float* kv, uint16_t* planes,
+                                       size_t planes_elems, int tile, act_stream_t stream) {
     if (B <= 0 || P <= 0 || D <= 0 || N <= 0) return ACT_E_BADARG;
     const size_t rows = (size_t)B * P;
     if (!g_prompt_kv_f16x3.load() || !(a_scale > 0.f) || !w_h1 || !w_h2 || !w_inv || !planes || planes_elems < 2 * rows * (size_t)D ||
@@ -531,12 +555,14 @@ int act_prompt_kv_fwd_f16x3_f32(const float* tok, const float* ppos, int B, int 
         return ACT_E_UNSUPPORTED;
     if (!tok || !ppos || !gamma || !beta || !kv) return ACT_E_NULLPTR;
     if (drop_p < 0.f || drop_p >= 1.f || (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) ||
-        (((uintptr_t)planes | (uintptr_t)w_h1 | (uintptr_t)w_h2 | (uintptr_t)w_inv) & 15))
+        (((uintptr_t)planes | (uintptr_t)w_h1 | (uintptr_t)w_h2 | (uintptr_t)w_inv) & 15) || (w_layout != ACT_X3_ROWMAJOR && w_layout != ACT_X3_KTILE) ||
+        (w_layout == ACT_X3_KTILE && (w_rows_total < N || (((uintptr_t)w_h1 | (uintptr_t)w_h2) & 127))))
         return ACT_E_BADARG;                                            // (checked before the first launch: the product below would refuse the same)
     uint16_t* p2 = planes + rows * D;                                   // (rows % 128 == 0: the second plane is 16-byte aligned with the first)
     RUN(act_prompt_layernorm_fwd_f16_planes_f32(tok, ppos, B, P, D, drop_p, seed, seed_dev, gamma, beta, eps, planes, p2, a_scale, stream));
     act_gemm_epilogue_t e = epi0(); e.bias = bias;
-    RUN(act_sgemm_nt_f16x3_planes_tile_f32((int)rows, N, D, planes, p2, a_scale, w_h1, w_h2, w_inv, kv, N, nullptr, nullptr, 0.f, &e, stream, tile));
+    RUN(act_sgemm_nt_f16x3_planes_layout_f32((int)rows, N, D, planes, p2, ACT_X3_ROWMAJOR, 0, 0, a_scale, w_h1, w_h2, w_layout, w_rows_total, w_inv, kv, N, nullptr,
+                                             nullptr, 0.f, ACT_X3_ROWMAJOR, &e, stream, tile));
     return 0;
 }
 
@@ -661,6 +687,7 @@ int act_prefix_vit_fwd_bf16x3_f32(const act_prefix_vit_t* m, const act_vit_bf16x
 int act_prefix_vit_fwd_f16x3_f32(const act_prefix_vit_t* m, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
                                  float* scratch, float* ws, size_t wsb, act_stream_t stream) {
     if (!h3 || !h3->w_planes || !h3->w_inv_scale || !h3->a_scale || !h3->a_planes) return ACT_E_NULLPTR;
+    if (h3->w_layout & ~15) return ACT_E_BADARG;                    // one bit per Linear of a block: qkv, proj, fc1, fc2
     return prefix_vit_fwd(m, nullptr, h3, tokens, center, out, scratch, ws, wsb, stream);
 }
 static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3, const act_vit_f16x3_t* h3, const float* tokens, const float* center, float* out,
@@ -688,20 +715,22 @@ static int prefix_vit_fwd(const act_prefix_vit_t* m, const act_vit_bf16x3_t* x3,
         X3Block hb{};           // split-f16 default: this block's planes and scales; a Linear without an activation scale (range guard) keeps the f32 kernel
         if (h3) {
             hb.a_planes = h3->a_planes; hb.a_elems = h3->a_planes_elems;
-            const size_t sD = D, sHd = m->hidden, elems[4] = {3 * sD * sD, sD * sD, sHd * sD, sD * sHd};
+            const size_t sD = D, sHd = m->hidden, elems[4] = {3 * sD * sD, sD * sD, sHd * sD, sD * sHd}, kdim[4] = {sD, sD, sD, sHd};
             X3Linear* lin[4] = {&hb.qkv, &hb.proj, &hb.fc1, &hb.fc2};
             for (int j = 0; j < 4; ++j) {
                 const float sa = h3->a_scale[4 * i + j];
                 if (sa > 0.f && h3->w_planes[4 * i + j] && h3->w_inv_scale[4 * i + j])
-                    *lin[j] = x3_linear_of(h3->w_planes[4 * i + j], elems[j], PlaneFmt::f16(sa), h3->w_inv_scale[4 * i + j]);
+                    *lin[j] = x3_linear_of(h3->w_planes[4 * i + j], elems[j], PlaneFmt::f16(sa), h3->w_inv_scale[4 * i + j],
+                                           (h3->w_layout >> j) & 1 ? ACT_X3_KTILE : ACT_X3_ROWMAJOR, (int)(elems[j] / kdim[j]));
             }
-            if (hb.qkv.w1) hb.kv = X3Linear{hb.qkv.w1 + sD * sD, hb.qkv.w2 + sD * sD, hb.qkv.inv + sD, hb.qkv.a_fmt};   // rows D .. 3D of both plane images
+            if (hb.qkv.w1) hb.kv = x3_rows_from(hb.qkv, sD, sD);                                                        // rows D .. 3D of both plane images
         }
         if (h3 && !x3) {        // prompt keys / values, split-f16 default: LayerNorm to planes + one dense planes product, where the kernel takes the shape
             uint16_t* tp = x3_fits(d, m->P, hb.a_elems) ? hb.a_planes + (size_t)2 * TG * m->hidden : nullptr;             // the activation region (x3_fits)
-            const int rc = act_prompt_kv_fwd_f16x3_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
-                                                       m->eps, hb.kv.w1, hb.kv.w2, hb.kv.inv, hb.kv.a_fmt.f16_scale, w.qkv_b ? w.qkv_b + D : nullptr, sv.kvp, tp,
-                                                       tp ? hb.a_elems - (size_t)2 * TG * m->hidden : 0, kPromptKvTile, stream);
+            const int rc = act_prompt_kv_fwd_f16x3_layout_f32(m->prompt_tok[i], m->prompt_pos[i], m->B, m->P, D, 2 * D, m->drop_p, seed, m->seed_dev, w.norm1_w, w.norm1_b,
+                                                              m->eps, hb.kv.w1, hb.kv.w2, hb.kv.layout, hb.kv.rows_total, hb.kv.inv, hb.kv.a_fmt.f16_scale,
+                                                              w.qkv_b ? w.qkv_b + D : nullptr, sv.kvp, tp, tp ? hb.a_elems - (size_t)2 * TG * m->hidden : 0,
+                                                              kPromptKvTile, stream);
             if (rc == 0) {
                 (void)collecting(1, 1, m->B * m->P, 2 * D, D);          // the dense f32 product stays tuned: a fall-back can be switched to at run time
                 CK(prefix_block_core(d, m->P, w, cur, pos, nullptr, false, sv, nxt, ws, wsb, s, &hb, true));
@@ -906,8 +935,8 @@ static int pointnet_fwd(const act_pointnet_dims_t* d, const act_pointnet_params_
         // the same product on the split-f16 kernel (frozen c4_w as planes).  The f32 shape is still recorded while shapes are collected: a call that falls
         // back (below) finds its configuration tuned
         if (collecting(1, 1, R, C, 512)) return 0;
-        return act_sgemm_nt_f16x3_gmax_f32(R, C, 512, sv.h3, 512, scale2, shift2, nullptr, nullptr, x3->a_scale, x3->c4_planes,
-                                           x3->c4_planes + (size_t)C * 512, x3->c4_inv_scale, w->c4_b, n, out, C, 0, s);
+        return act_sgemm_nt_f16x3_gmax_layout_f32(R, C, 512, sv.h3, 512, scale2, shift2, nullptr, nullptr, x3->a_scale, x3->c4_planes,
+                                                  x3->c4_planes + (size_t)C * 512, x3->w_layout, C, x3->c4_inv_scale, w->c4_b, n, out, C, 0, s);
     }
     {   // conv 512->C on relu(bn2(h3)) applied on load; only the max over the group leaves the kernel
         act_gemm_fx_t fx{}; fx.a_scale = scale2; fx.a_shift = shift2; fx.gmax = out; fx.garg = keep_for_backward ? sv.arg2 : nullptr; fx.group = n; fx.store_c = 0;
@@ -1016,7 +1045,7 @@ int act_pointnet_bwd_f32(const act_pointnet_dims_t* d, const act_pointnet_params
 }
 
 // ============================================================================================== DGCNN (inference form)
-static const int kDgcnnCin[4] = {128, 256, 512, 512}, kDgcnnCout[4] = {256, 512, 512, 1024};
+static constexpr int kDgcnnCin[4] = {128, 256, 512, 512}, kDgcnnCout[4] = {256, 512, 512, 1024};
 static size_t carve_dgcnn(float* base, const act_dgcnn_t& m, float*& x0, float*& yz, float*& cat, float*& stats) {
     const size_t T = (size_t)m.B * m.G;
     Carver c(base);
@@ -1061,6 +1090,12 @@ static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, con
                       (layers || !x3->layers);                                // (layers asked for and refused: the whole f32 sequence)
     uint16_t* const ap1 = planes_ok ? x3->a_planes : nullptr;
     uint16_t* const ap2 = planes_ok ? x3->a_planes + (size_t)T * 2304 : nullptr;
+    // the planes of cat K-tile-major where the tails write them slice by slice and the weights that read them are K-tile-major: the slice at column c (a
+    // multiple of 32) of the [T][2304] planes starts (c / 32) T 32 elements in, and a layer's A operand is that slice as it stands
+    const bool cat_kt = layers && x3->w_layout == ACT_X3_KTILE && g_x3_kt.load() && ((uintptr_t)x3->a_planes & 127) == 0;
+    static_assert(kDgcnnCout[0] % 64 == 0 && kDgcnnCout[1] % 64 == 0 && kDgcnnCout[2] % 64 == 0 && kDgcnnCout[3] % 64 == 0, "slice offsets on whole K-tile pairs");
+    const int w_layout = planes_ok ? x3->w_layout : ACT_X3_ROWMAJOR;
+    if (w_layout != ACT_X3_ROWMAJOR && w_layout != ACT_X3_KTILE) return ACT_E_BADARG;
     act_gemm_epilogue_t e = epi0(); e.bias = m->b_in;
     CK(gemm_nt(T, 128, m->Cin, f, m->Cin, m->w_in, m->Cin, x0, 128, e, ws, wsb, s));
     const float* xin = x0; int ldx = 128, off = 0;
@@ -1068,23 +1103,27 @@ static int dgcnn_features(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, con
         const int cin = kDgcnnCin[l], cout = kDgcnnCout[l];
         // W.cat(x_j - x_i, x_i) = Wa x_j + (Wb - Wa) x_i: one GEMM over the B*G points -> [Y | Z], then gather + GroupNorm + LeakyReLU + max_k
         if (layers && l > 0 && !t_collect) {                         // A = the planes of the previous tail's slice of cat, written below
-            const size_t prev = (size_t)(off - cin);
+            const size_t prev = cat_kt ? (size_t)((off - cin) / 32) * T * 32 : (size_t)(off - cin);
             const uint16_t* w1 = x3->st_planes[l - 1];
             const act_gemm_epilogue_t e0 = epi0();
-            RUN(act_sgemm_nt_f16x3_planes_lda_f32(T, 2 * cout, cin, ap1 + prev, ap2 + prev, 2304, x3->a_scale, w1, w1 + (size_t)2 * cout * cin,
-                                                  x3->st_inv_scale[l - 1], yz, 2 * cout, nullptr, nullptr, 0.f, &e0, s, 0));
+            RUN(act_sgemm_nt_f16x3_planes_layout_f32(T, 2 * cout, cin, ap1 + prev, ap2 + prev, cat_kt ? ACT_X3_KTILE : ACT_X3_ROWMAJOR, 2304, T, x3->a_scale, w1,
+                                                     w1 + (size_t)2 * cout * cin, w_layout, 2 * cout, x3->st_inv_scale[l - 1], yz, 2 * cout, nullptr, nullptr, 0.f,
+                                                     ACT_X3_ROWMAJOR, &e0, s, 0));
         } else {                                                     // (also while the GEMM shapes are collected: a fall-back finds its configuration)
             CK(gemm_nt(T, 2 * cout, cin, xin, ldx, m->stacked[l], cin, yz, 2 * cout, epi0(), ws, wsb, s));
         }
         RUN(act_edge_gn_lrelu_max_f32(yz, 2 * cout, cout, idx, m->B, m->G, m->k, cout, m->groups, m->gn_w[l], m->gn_b[l], m->eps, m->slope, stats,
                                      cat, 2304, off, s));
-        if (layers && (l < 3 || head) && !t_collect)                 // this tail's slice as planes, for the next layer and the head
-            RUN(act_split_f16x2_ld_f32(cat + off, T, cout, 2304, x3->a_scale, ap1 + off, ap2 + off, 2304, s));
+        if (layers && (l < 3 || head) && !t_collect) {               // this tail's slice as planes, for the next layer and the head
+            const size_t o = (size_t)(off / 32) * T * 32;
+            RUN(cat_kt ? act_split_f16x2_kt_f32(cat + off, T, cout, 2304, x3->a_scale, ap1 + o, ap2 + o, T, s)
+                       : act_split_f16x2_ld_f32(cat + off, T, cout, 2304, x3->a_scale, ap1 + off, ap2 + off, 2304, s));
+        }
         xin = cat + off; ldx = 2304; off += cout;
     }
     if (head) {
-        const X3Linear w5 = x3_linear_of(x3->w5_planes, (size_t)m->Cout * 2304, PlaneFmt::f16(x3->a_scale), x3->w5_inv_scale);
-        return x3_linear(w5, T, m->Cout, 2304, cat, layers ? x3->a_planes : nullptr, x3->a_planes, h, nullptr, w5.a_fmt, epi0(), s);
+        const X3Linear w5 = x3_linear_of(x3->w5_planes, (size_t)m->Cout * 2304, PlaneFmt::f16(x3->a_scale), x3->w5_inv_scale, w_layout, m->Cout);
+        return x3_linear(w5, T, m->Cout, 2304, cat, layers ? x3->a_planes : nullptr, x3->a_planes, h, nullptr, w5.a_fmt, epi0(), s, cat_kt);
     }
     CK(gemm_nt(T, m->Cout, 2304, cat, 2304, m->w5, 2304, h, m->Cout, epi0(), ws, wsb, s));
     return 0;

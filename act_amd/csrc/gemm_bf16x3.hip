@@ -58,14 +58,17 @@ __device__ __forceinline__ float4 x3_scale4(const float4& a, float s) { return m
 // elements apart (ldp == K: dense; wider: a column slice of a wider plane buffer, the same bytes per element)
 // AFF (F16 only): the planes of relu(x * col_scale[k] + col_shift[k]) * scale instead -- the power of two folded into the affine map first, one fma per element,
 // exactly what the product's on-load form computes, so the two forms give the same planes bit for bit
+// kt_rows > 0: the planes leave in the K-tile-major layout of a [kt_rows][K] plane (x3_kt_index below; K % 32 == 0) instead, the same values at other places
 template <bool F16, bool AFF = false>
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, int K4, int ldx, int ldp4, long long n4, float scale,
                                                            const float* __restrict__ row_scale, unsigned short* __restrict__ p1, unsigned short* __restrict__ p2,
-                                                           const float* __restrict__ col_scale = nullptr, const float* __restrict__ col_shift = nullptr) {
+                                                           const float* __restrict__ col_scale = nullptr, const float* __restrict__ col_shift = nullptr,
+                                                           int kt_rows = 0) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / K4; const int c4 = (int)(i - row * K4);
         const float4 v = *reinterpret_cast<const float4*>(x + row * ldx + c4 * 4);
-        const size_t o4 = (size_t)(row * ldp4 + c4);          // ldp4 = the planes' row stride in groups of four elements (K4: dense, o4 == i)
+        // ldp4 = the planes' row stride in groups of four elements (K4: dense, o4 == i); K-tile-major: eight groups of four per row and K tile
+        const size_t o4 = kt_rows ? ((size_t)(c4 >> 3) * kt_rows + row) * 8 + (c4 & 7) : (size_t)(row * ldp4 + c4);
         if constexpr (AFF) {
             const float4 sc = x3_scale4(*reinterpret_cast<const float4*>(col_scale + c4 * 4), scale), sh = x3_scale4(*reinterpret_cast<const float4*>(col_shift + c4 * 4), scale);
             store_planes4<F16>(p1, p2, o4, x3_affine_relu4(v, sc, sh), 1.0f);
@@ -76,10 +79,26 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
 }
 
 constexpr int BK = 32;                      // bf16 per K tile = 64-byte rows
+
+// K-TILE-MAJOR ("KT") PLANES (notebook/x3_ktile.md).  Element (r, k) of a plane [R][K] lies at ((k / BK) * R + r) * BK + k % BK: the 64-byte pieces that the
+// rows of one K tile contribute are adjacent, so a workgroup's A or B tile of one K tile is ONE contiguous block of rows * 64 bytes and thread tid of a staging
+// pass reads bytes 16 tid .. of it -- every wave-wide load is eight whole 128-byte lines, where the row-major plane gives sixteen half-used ones.  The product
+// kernel walks either layout through two strides per operand (X3Params): row stride and K-tile stride, (ld, BK) row-major and (BK, R * BK) KT.  Same values,
+// same order of summation: the same bits.
+constexpr long long x3_kt_index(long long r, long long k, long long rows) { return ((k / BK) * rows + r) * BK + k % BK; }
+
+// plane [R][K] row-major -> KT, one 16-byte chunk per thread (K8 = K / 8 chunks per row, four per K tile)
+__global__ __launch_bounds__(256) void repack_ktile_kernel(const u32x4v* __restrict__ src, u32x4v* __restrict__ dst, int R, int K8, long long n8) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
+        const long long row = i / K8; const int c8 = (int)(i - row * K8);
+        dst[((long long)(c8 >> 2) * R + row) * 4 + (c8 & 3)] = src[i];
+    }
+}
 constexpr int LROW = 40;                    // bf16 per LDS row: 32 + 8 pad (80-byte pitch: conflict-free ds_read_b128 / ds_write_b128)
 
 struct X3Params {
-    const unsigned short *Ah, *Al, *Bh, *Bl;   // planes, row-major: B [N][K] dense, A [M][K] with row stride lda (>= K: a column slice of a wider plane buffer)
+    const unsigned short *Ah, *Al, *Bh, *Bl;   // planes of A [M][K] and B [N][K], each walked by a row stride (lda, ldb) and a K-tile stride (kta, ktb), in elements:
+                                               // row-major (ld, BK) with ld >= K (a column slice of a wider plane buffer); K-tile-major (BK, rows_total * BK)
     float* C; int ldc;                         // fp32 result (nullable when the planes below are given)
     unsigned short *Oh, *Ol;                   // optional: the result ALSO / INSTEAD as (hi, lo) bf16 planes [M][N] -- the A operand of the next split-bf16 product
     int M, N, K;
@@ -87,6 +106,8 @@ struct X3Params {
     const float* b_inv; float a_inv, o_scale;  // F16 form: 1 / s_B[n], 1 / s_A, and the scale the planes-out are split at (the next product's s_A)
     // A32 form: A arrives as fp32 [M][K] (row stride lda) and its planes are those of relu(A * a_sc[k] + a_sh[k]) * a_fold, made while the tile is staged
     const float *A32, *a_sc, *a_sh; int lda; float a_fold;   // (lda: the row stride of A in either form, in elements of that form)
+    int ldb, kta, ktb;                         // (A32: kta == BK)
+    int o_kt;                                  // the planes-out [M][N] leave K-tile-major: the A operand of a product that reads it so
     int group;                                 // GMAX form: rows per group (32 or 64); C = out [M / group][N] (row stride ldc), the max over each group's rows
 };
 
@@ -160,8 +181,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
             for (int j = 0; j < TN; ++j) acc[x][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int srow = tid >> 2, sch = tid & 3;                 // staging: (row, 16-byte chunk) of a [rows][32 bf16] plane tile
-    const int lda = p.lda;                                    // A32: this thread's eight k of a row are two 16-byte fp32 loads (set 0: k .. k+3, set 1: k+4 .. k+7)
-    const size_t goa = (size_t)(m0 + srow) * lda + sch * 8, gob = (size_t)(n0 + srow) * K + sch * 8;
+    const int lda = p.lda, ldb = p.ldb;                       // A32: this thread's eight k of a row are two 16-byte fp32 loads (set 0: k .. k+3, set 1: k+4 .. k+7)
+    const long long kta = p.kta, ktb = p.ktb;                 // K tile T of an operand starts T * kt elements behind tile 0 (row-major: BK)
+    const size_t goa = (size_t)(m0 + srow) * lda + sch * 8, gob = (size_t)(n0 + srow) * ldb + sch * 8;
     const float* gA32[2] = {A32 ? p.A32 + goa : nullptr, A32 ? p.A32 + goa + 4 : nullptr};
     const unsigned short* gA[2] = {A32 ? nullptr : p.Ah + goa, A32 ? nullptr : p.Al + goa};
     const unsigned short* gB[2] = {p.Bh + gob, p.Bl + gob};
@@ -172,7 +194,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
     // staging pass i covers rows i * RP .. of the plane tile.  A last PARTIAL pass (BM or BN no multiple of RP) loads unconditionally from its row clamped into
     // the tile (ta / tb: that row's offset from this thread's first row) and stores to the LDS only where the row exists -- a test that is uniform per wave
     // (a wave stages 16 consecutive rows; BM, BN and RP are multiples of 16), so there is still no divergent code around the staging registers
-    const long long ta = (long long)(min(srow + RP * (NA - 1), BM - 1) - srow) * lda, tb = (long long)(min(srow + RP * (NB - 1), BN - 1) - srow) * K;
+    const long long ta = (long long)(min(srow + RP * (NA - 1), BM - 1) - srow) * lda, tb = (long long)(min(srow + RP * (NB - 1), BN - 1) - srow) * ldb;
     // A32: (scale, shift) of k at float (k / 4) * (LROW / 2) + 16 + k % 4 of the first / second A plane image of stage 0 (the pad columns)
     const float* Lf = reinterpret_cast<const float*>(L);
     const int sx_off = sch * 2 * (LROW / 2) + 16;              // + T * 8 * (LROW / 2): this thread's eight k of K tile T
@@ -181,11 +203,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
     _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                                                                                 \
         _Pragma("unroll") for (int i_ = 0; i_ < NA; ++i_)                                                                              \
             if constexpr (A32)                                                                                                         \
-                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA32[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * BK); \
+                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA32[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * kta); \
             else                                                                                                                       \
-                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * BK); \
+                RA[s_][i_] = *reinterpret_cast<const u32x4v*>(gA[s_] + (X3_WHOLE(i_, BM) ? (long long)(RP * i_) * lda : ta) + (T) * kta); \
         _Pragma("unroll") for (int i_ = 0; i_ < NB; ++i_)                                                                              \
-            RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (X3_WHOLE(i_, BN) ? (long long)(RP * i_) * K : tb) + (T) * BK);      \
+            RB[s_][i_] = *reinterpret_cast<const u32x4v*>(gB[s_] + (X3_WHOLE(i_, BN) ? (long long)(RP * i_) * ldb : tb) + (T) * ktb);   \
     }
     /* T: the K tile the registers hold (read by the A32 form only) */
 #define X3_STORE(RA, RB, STG, T)                                                                                                       \
@@ -313,7 +335,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, x3_wgs_per_cu(WGM * WGN) * WGM * WG
                 float* cp = p.C + (size_t)row * p.ldc + col;
                 if (vec) *reinterpret_cast<float4*>(cp) = v; else { cp[0] = v.x; cp[1] = v.y; cp[2] = v.z; cp[3] = v.w; }
             }
-            if constexpr (PLANES) store_planes4<F16>(p.Oh, p.Ol, ((size_t)row * p.N + col) >> 2, v, p.o_scale);   // N % 128 == 0, col % 4 == 0: 8-byte aligned
+            // N % 128 == 0, col % 4 == 0: 8-byte aligned in either layout (o_kt: x3_kt_index of a [M][N] plane)
+            if constexpr (PLANES)
+                store_planes4<F16>(p.Oh, p.Ol, (p.o_kt ? ((size_t)(col >> 5) * p.M + row) * BK + (col & 31) : (size_t)row * p.N + col) >> 2, v, p.o_scale);
         }
 }
 
@@ -413,19 +437,35 @@ bool x3_only_128() {                                               // ACT_X3_TIL
 }
 // the argument-checked product of both formats.  The scales and the tile belong to the F16 form (a_scale = s_A, b_inv = 1 / s_B per row of B, out_scale = the
 // scale the planes-out are split at; tile: 0 = the rule above, 128 / 192 forced); the bf16 form reads none of them and runs the 128 x 128 tile
+// Where an operand's planes lie (ACT_X3_ROWMAJOR | ACT_X3_KTILE).  Row-major: rows ld elements apart (0 = dense, K).  K-tile-major: the planes are those of a
+// [rows_total][K'] matrix of which the operand is rows r0 .. of K tiles c0 / 32 .., the pointers at x3_kt_index(r0, c0, rows_total) -- ld is not read.
+struct X3Layout { int layout = ACT_X3_ROWMAJOR, ld = 0, rows_total = 0; };
+// -> false: a layout the kernel cannot walk (rows: the operand's rows; p1, p2: its planes).  KT bases lie on a 128-byte line: that is what the layout is for
+bool x3_strides(const X3Layout& l, int rows, int K, const uint16_t* p1, const uint16_t* p2, int& ld, int& kt) {
+    if (l.layout == ACT_X3_KTILE) {
+        if (l.rows_total < rows || (long long)l.rows_total * BK > 0x7fffffffLL || (((uintptr_t)p1 | (uintptr_t)p2) & 127)) return false;
+        ld = BK; kt = l.rows_total * BK; return true;
+    }
+    if (l.layout != ACT_X3_ROWMAJOR) return false;
+    ld = l.ld ? l.ld : K; kt = BK;
+    return ld >= K && !(ld & 7);                                    // (K % 64 == 0: the dense stride passes) every row of a plane 16-byte aligned
+}
+
 template <bool F16>
 int multiply_planes(int M, int N, int K, const uint16_t* a1, const uint16_t* a2, float a_scale, const uint16_t* b1, const uint16_t* b2, const float* b_inv,
                     float* C, int ldc, uint16_t* o1, uint16_t* o2, float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile,
-                    int lda = 0) {                                  // lda: row stride of the A planes (0 = dense, K)
-    if (lda == 0) lda = K;
-    if (lda < K || (lda & 7)) return ACT_E_BADARG;                  // (K % 64 == 0: the dense stride passes) every row of a plane 16-byte aligned
+                    const X3Layout& la = X3Layout{}, const X3Layout& lb = X3Layout{}, int out_layout = ACT_X3_ROWMAJOR) {
+    int lda, ldb, kta, ktb;
+    if (!x3_strides(la, M, K, a1, a2, lda, kta) || !x3_strides(lb, N, K, b1, b2, ldb, ktb)) return ACT_E_BADARG;
+    if (out_layout != ACT_X3_ROWMAJOR && (out_layout != ACT_X3_KTILE || !F16 || (((uintptr_t)o1 | (uintptr_t)o2) & 127))) return ACT_E_BADARG;
     if (!a1 || !a2 || !b1 || !b2 || (F16 && !b_inv) || (!C && !o1) || ((o1 == nullptr) != (o2 == nullptr))) return ACT_E_NULLPTR;
     if (!act_sgemm_nt_bf16x3_supported(M, N, K) || (C && ldc < N) || (F16 && (!(a_scale > 0.f) || (o1 && !(out_scale > 0.f))))) return ACT_E_BADARG;
     if ((((uintptr_t)a1 | (uintptr_t)a2 | (uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)o1 | (uintptr_t)o2 | (uintptr_t)b_inv) & 15)) return ACT_E_BADARG;
     if (F16 && tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;       // a forced tile that the shape does not take
     if (F16 && tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
-    p.Ah = a1; p.Al = a2; p.Bh = b1; p.Bl = b2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = o1; p.Ol = o2; p.lda = lda;
+    p.Ah = a1; p.Al = a2; p.Bh = b1; p.Bl = b2; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.Oh = o1; p.Ol = o2;
+    p.lda = lda; p.ldb = ldb; p.kta = kta; p.ktb = ktb; p.o_kt = out_layout == ACT_X3_KTILE;
     if (F16) { p.b_inv = b_inv; p.a_inv = 1.0f / a_scale; p.o_scale = out_scale; }
     if (epilogue) p.epi = *epilogue; else { p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; }
     if (p.epi.accumulate || (p.epi.act != ACT_EPI_NONE && p.epi.act != ACT_EPI_GELU && p.epi.act != ACT_EPI_MUL_GELU_GRAD)) return ACT_E_BADARG;
@@ -454,10 +494,14 @@ extern "C" int act_sgemm_nt_f16x3_gmax_supported(int M, int N, int K, int group)
 }
 // Tile of the group-max product by shape alone: the rule of the storing product (notebook/pn_f16x3.md has both tiles measured at the tokenizer's shape)
 extern "C" int act_sgemm_nt_f16x3_gmax_pick_tile(int M, int N, int K, int cus) { return act_sgemm_nt_f16x3_pick_tile(M, N, K, cus); }
-extern "C" int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift,
-                                           const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2,
-                                           const float* b_inv_scale, const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream) {
+// b_layout / b_rows_total: where the planes of B lie (X3Layout above)
+extern "C" int act_sgemm_nt_f16x3_gmax_layout_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift,
+                                                  const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2,
+                                                  int b_layout, int b_rows_total, const float* b_inv_scale, const float* bias, int group, float* out, int ldo,
+                                                  int tile, act_stream_t stream) {
     const bool a32 = A != nullptr;
+    int ldb, ktb;
+    if (!x3_strides(X3Layout{b_layout, 0, b_rows_total}, N, K, b_h1, b_h2, ldb, ktb)) return ACT_E_BADARG;
     if (!b_h1 || !b_h2 || !b_inv_scale || !out || (a32 ? (!a_col_scale || !a_col_shift) : (!a_h1 || !a_h2))) return ACT_E_NULLPTR;
     if (!act_sgemm_nt_f16x3_gmax_supported(M, N, K, group) || ldo < N || !(a_scale > 0.f) || (a32 && (lda < K || (lda & 3)))) return ACT_E_BADARG;
     if (((uintptr_t)A | (uintptr_t)a_col_scale | (uintptr_t)a_col_shift | (uintptr_t)a_h1 | (uintptr_t)a_h2 | (uintptr_t)b_h1 | (uintptr_t)b_h2 |
@@ -465,12 +509,20 @@ extern "C" int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, 
     if (tile != 0 && tile != 128 && !(tile == 192 && N % 192 == 0)) return ACT_E_BADARG;
     if (tile == 0) tile = x3_only_128() ? 128 : act_sgemm_nt_f16x3_gmax_pick_tile(M, N, K, x3_cu_count());
     X3Params p{};
+    p.ldb = ldb; p.kta = BK; p.ktb = ktb;
     p.A32 = A; p.lda = a32 ? lda : K; p.a_sc = a_col_scale; p.a_sh = a_col_shift; p.a_fold = a_scale; p.Ah = a_h1; p.Al = a_h2; p.Bh = b_h1; p.Bl = b_h2;
     p.C = out; p.ldc = ldo; p.M = M; p.N = N; p.K = K; p.group = group; p.b_inv = b_inv_scale; p.a_inv = 1.0f / a_scale;
     p.epi = act_gemm_epilogue_t{}; p.epi.alpha = 1.0f; p.epi.bias = bias;
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_GEMM_BF16X3, s, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)(M / group) * N));
     return tile == 192 ? launch_x3_gmax<128, 192, 2, 4>(p, a32, s) : launch_x3_gmax<128, 128, 2, 2>(p, a32, s);
+}
+
+extern "C" int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift,
+                                           const uint16_t* a_h1, const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2,
+                                           const float* b_inv_scale, const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream) {
+    return act_sgemm_nt_f16x3_gmax_layout_f32(M, N, K, A, lda, a_col_scale, a_col_shift, a_h1, a_h2, a_scale, b_h1, b_h2, ACT_X3_ROWMAJOR, 0, b_inv_scale, bias,
+                                              group, out, ldo, tile, stream);
 }
 
 extern "C" int act_sgemm_nt_bf16x3_f32(int M, int N, int K, const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* b_hi, const uint16_t* b_lo,
@@ -498,5 +550,41 @@ extern "C" int act_sgemm_nt_f16x3_planes_lda_f32(int M, int N, int K, const uint
                                                  const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
                                                  float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
     if (lda <= 0) return ACT_E_BADARG;
-    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile, lda);
+    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile,
+                                 X3Layout{ACT_X3_ROWMAJOR, lda, 0});
+}
+// the general entry: each operand, and the planes-out, row-major or K-tile-major (X3Layout above; a row-major B is dense)
+extern "C" int act_sgemm_nt_f16x3_planes_layout_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, int a_layout, int lda, int a_rows_total,
+                                                    float a_scale, const uint16_t* b_h1, const uint16_t* b_h2, int b_layout, int b_rows_total,
+                                                    const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2, float out_scale,
+                                                    int out_layout, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile) {
+    if (lda < 0) return ACT_E_BADARG;
+    return multiply_planes<true>(M, N, K, a_h1, a_h2, a_scale, b_h1, b_h2, b_inv_scale, C, ldc, out_h1, out_h2, out_scale, epilogue, stream, tile,
+                                 X3Layout{a_layout, lda, a_rows_total}, X3Layout{b_layout, 0, b_rows_total}, out_layout);
+}
+
+// ---- K-tile-major planes ------------------------------------------------------------------------------------------------------------------------------------
+// a pure copy of one 16-bit plane [R][K] (dense) into the K-tile-major layout; K % 32 == 0, both 16-byte aligned, src != dst
+extern "C" int act_repack_ktile_u16(const uint16_t* src, uint16_t* dst, int R, int K, act_stream_t stream) {
+    if (!src || !dst) return ACT_E_NULLPTR;
+    if (R < 0 || K <= 0 || (K % BK) || src == dst || (((uintptr_t)src | (uintptr_t)dst) & 15)) return ACT_E_BADARG;
+    const long long n8 = (long long)R * K / 8; if (n8 == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 4.0 * R * (double)K);
+    long long g = (n8 + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(repack_ktile_kernel, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const u32x4v*>(src), reinterpret_cast<u32x4v*>(dst), R, K / 8, n8);
+    ACT_LAUNCH_CHECK(); return 0;
+}
+// act_split_f16x2_f32 (no row scales) whose planes leave K-tile-major, as rows 0 .. R of a [rows_total][K] plane; K % 32 == 0, planes 128-byte aligned
+extern "C" int act_split_f16x2_kt_f32(const float* x, int R, int K, int ldx, float scale, uint16_t* h1, uint16_t* h2, int rows_total, act_stream_t stream) {
+    if (!x || !h1 || !h2) return ACT_E_NULLPTR;
+    if (R < 0 || K <= 0 || (K % BK) || ldx < K || (ldx & 3) || !(scale > 0.f) || rows_total < R || (long long)rows_total * BK > 0x7fffffffLL ||
+        ((uintptr_t)x & 15) || (((uintptr_t)h1 | (uintptr_t)h2) & 127))
+        return ACT_E_BADARG;
+    const long long n4 = (long long)R * K / 4; if (n4 == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ActProfScope ps(KID_ELTWISE, s, 0.0, 8.0 * R * (double)K);
+    long long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(split_planes_kernel<true>, dim3((unsigned)g), dim3(256), 0, s, x, K / 4, ldx, K / 4, n4, scale, nullptr, h1, h2, nullptr, nullptr, rows_total);
+    ACT_LAUNCH_CHECK(); return 0;
 }

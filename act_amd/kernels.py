@@ -269,10 +269,11 @@ def split_f16x2_affine_relu(x, col_scale, col_shift, scale):
     return out
 
 
-def gemm_nt_f16x3_gmax(a, a_scale, b_planes, b_inv_scale, group, bias=None, col_scale=None, col_shift=None, tile=0):
+def gemm_nt_f16x3_gmax(a, a_scale, b_planes, b_inv_scale, group, bias=None, col_scale=None, col_shift=None, tile=0, b_layout=0):
     """out[M / group, N] = max over every ``group`` (32 | 64) consecutive rows of ((a' . b^T) / a_scale / b_scale[n] + bias): the last product of the frozen
     tokenizer's mini-PointNet on the split-f16 kernel, nothing but the group max stored.  ``a`` fp32 [M, K] with col_scale / col_shift: a' = the planes of
-    relu(a * col_scale + col_shift) * a_scale, formed while the kernel stages a; ``a`` f16 planes [2, M, K]: a' = those planes.  K <= 512."""
+    relu(a * col_scale + col_shift) * a_scale, formed while the kernel stages a; ``a`` f16 planes [2, M, K]: a' = those planes.  K <= 512.
+    ``b_layout`` X3_KTILE: the two planes of b are K-tile-major (repack_ktile)."""
     planes = a.dtype == torch.float16
     b_planes, b_inv_scale = b_planes.contiguous(), _f32c(b_inv_scale)
     N, Kd = b_planes.shape[1], b_planes.shape[2]
@@ -287,10 +288,73 @@ def gemm_nt_f16x3_gmax(a, a_scale, b_planes, b_inv_scale, group, bias=None, col_
     if a.shape[-1] != Kd or b_inv_scale.numel() != N or M % int(group):
         raise _C.ActHipError("gemm_nt_f16x3_gmax: shapes do not match")
     out = torch.empty(M // int(group), N, dtype=torch.float32, device=a.device)
-    check(lib.act_sgemm_nt_f16x3_gmax_f32(M, N, Kd, *args, float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]), ptr(b_inv_scale),
-                                          ptr(_f32c(bias)) if bias is not None else None, int(group), ptr(out), N, int(tile), stream()),
-          "act_sgemm_nt_f16x3_gmax_f32")
+    check(lib.act_sgemm_nt_f16x3_gmax_layout_f32(M, N, Kd, *args, float(a_scale), ptr(b_planes[0]), ptr(b_planes[1]), int(b_layout), N, ptr(b_inv_scale),
+                                                 ptr(_f32c(bias)) if bias is not None else None, int(group), ptr(out), N, int(tile), stream()),
+          "act_sgemm_nt_f16x3_gmax_layout_f32")
     return out
+
+
+# ---- K-tile-major planes (csrc/gemm_bf16x3.hip, notebook/x3_ktile.md): the layout frozen weight planes are kept in ---------------------------------------
+X3_ROWMAJOR, X3_KTILE = 0, 1
+X3_BK = 32                     # elements per K tile
+
+
+def ktile_index(r, k, rows_total):
+    """where element (r, k) of a plane [rows_total][K] lies in the K-tile-major layout: the 64-byte pieces of all rows of one K tile side by side"""
+    return ((k // X3_BK) * rows_total + r) * X3_BK + k % X3_BK
+
+
+def ktile_rows(kt, R, Kd):
+    """the row-major [R, K] reading of one K-tile-major plane (a view-and-copy on the host side of tests and tools)"""
+    return kt.reshape(Kd // X3_BK, R, X3_BK).permute(1, 0, 2).reshape(R, Kd)
+
+
+def x3_kt(on=None):
+    """ACT_X3_KT (default on): frozen weight planes are kept K-tile-major and the composites hand activation planes on that way.  ``on`` None: query;
+    else set -> the previous setting.  Off is the row-major step, the same bits."""
+    return bool(lib.act_x3_kt(-1 if on is None else int(bool(on))))
+
+
+def repack_ktile(planes):
+    """16-bit planes [..., R, K] (contiguous, K % 32 == 0) -> a tensor of the same shape and dtype whose every [R, K] plane holds the K-tile-major layout"""
+    planes = planes.contiguous()
+    R, Kd = planes.shape[-2:]
+    if planes.element_size() != 2 or Kd % X3_BK:
+        raise _C.ActHipError("repack_ktile: 16-bit planes with K % 32 == 0 expected")
+    out = torch.empty_like(planes)
+    src, dst = planes.reshape(-1, R, Kd), out.view(-1, R, Kd)
+    for i in range(src.shape[0]):
+        check(lib.act_repack_ktile_u16(ptr(src[i]), ptr(dst[i]), R, Kd, stream()), "act_repack_ktile_u16")
+    return out
+
+
+def split_f16x2_kt(x, scale=1.0, out=None, rows_total=None):
+    """split_f16x2 (no row scales) whose planes [2, rows_total, K] leave K-tile-major; x fills rows 0 .. R of them (rows_total None: R)"""
+    x = _f32rows(x, "x")
+    R, Kd = x.shape
+    rows_total = R if rows_total is None else int(rows_total)
+    if out is None:
+        out = torch.empty(2, rows_total, Kd, dtype=torch.float16, device=x.device)
+    check(lib.act_split_f16x2_kt_f32(_C.ptr_rows(x), R, Kd, x.stride(0), float(scale), ptr(out[0]), ptr(out[1]), rows_total, stream()), "act_split_f16x2_kt_f32")
+    return out
+
+
+def gemm_nt_f16x3_layout(M, N, Kd, a, a_scale, b, b_inv_scale, a_layout=0, lda=0, a_rows_total=0, b_layout=0, b_rows_total=0, bias=None, act=EPI_NONE,
+                         res=None, out=None, want_c=True, planes_out=None, out_scale=1.0, out_layout=0, tile=0):
+    """gemm_nt_f16x3 with the layout of each operand and of the planes-out given (act_sgemm_nt_f16x3_planes_layout_f32).  ``a`` / ``b``: a pair of f16
+    tensors whose first elements are the operand's first element in its (h1, h2) planes -- a slice of a wider or K-tile-major buffer starts where the caller
+    says.  X3_KTILE: the operand is rows and K tiles of the K-tile-major planes of a [rows_total][..] matrix.  ``want_c`` False: only ``planes_out`` leaves."""
+    b_inv_scale = _f32c(b_inv_scale)
+    if want_c and out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=a[0].device)
+    e = GemmEpilogue(alpha=1.0, act=act, accumulate=0, rows_per_scale=0, ldr=(res.stride(0) if res is not None else 0), ldaux=0, res_row_div=0,
+                     bias=ptr(bias), rowscale=None, res=ptr(res), aux=None)
+    o1, o2 = (ptr(planes_out[0]), ptr(planes_out[1])) if planes_out is not None else (None, None)
+    check(lib.act_sgemm_nt_f16x3_planes_layout_f32(M, N, Kd, ptr(a[0]), ptr(a[1]), int(a_layout), int(lda), int(a_rows_total), float(a_scale), ptr(b[0]), ptr(b[1]),
+                                                   int(b_layout), int(b_rows_total), ptr(b_inv_scale), ptr(out) if want_c else None,
+                                                   out.stride(0) if want_c else N, o1, o2, float(out_scale), int(out_layout), ctypes.byref(e), stream(),
+                                                   int(tile)), "act_sgemm_nt_f16x3_planes_layout_f32")
+    return out if want_c else planes_out
 
 
 # ---- GEMM autotuner: the step has ~40 distinct (layout, M, N, K) shapes; each is timed once (tile shape x split-K) on first

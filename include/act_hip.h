@@ -447,6 +447,25 @@ int act_sgemm_nt_f16x3_planes_tile_f32(int M, int N, int K, const uint16_t* a_h1
 int act_sgemm_nt_f16x3_planes_lda_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, int lda, float a_scale, const uint16_t* b_h1,
                                       const uint16_t* b_h2, const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2,
                                       float out_scale, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile);
+/* K-TILE-MAJOR PLANES (notebook/x3_ktile.md).  Element (r, k) of a plane [R][K] at ((k / 32) * R + r) * 32 + k % 32: the 64-byte pieces
+ * of the rows of one K tile lie side by side, and the product stages an operand tile in whole 128-byte lines.  Same values, same bits.
+ * act_repack_ktile_u16: a pure copy of one dense plane into that layout (K % 32 == 0, 16-byte aligned, src != dst, else ACT_E_BADARG).
+ * act_split_f16x2_kt_f32: act_split_f16x2_f32 without row scales whose planes leave K-tile-major, as rows 0 .. R of a [rows_total][K] plane.
+ * ..._planes_layout_f32: the product with the layout of each operand and of the planes-out given.  ACT_X3_ROWMAJOR: as the entries above (lda: 0 = K; a
+ * row-major B is dense; *_rows_total not read).  ACT_X3_KTILE: the pointers are at element (r0, c0) of the planes of a
+ * [rows_total][..] matrix -- the operand is its rows r0 .. and columns c0 .. c0 + K, c0 % 32 == 0 -- and lie on a 128-byte line; rows_total >= the operand's
+ * rows (M or N).  out_layout ACT_X3_KTILE: the planes-out [M][N] leave K-tile-major (128-byte aligned).  Any other layout value, rows_total too small or a
+ * misaligned K-tile-major plane is ACT_E_BADARG and launches nothing. */
+enum { ACT_X3_ROWMAJOR = 0, ACT_X3_KTILE = 1 };
+int act_repack_ktile_u16(const uint16_t* src, uint16_t* dst, int R, int K, act_stream_t stream);
+int act_split_f16x2_kt_f32(const float* x, int R, int K, int ldx, float scale, uint16_t* h1, uint16_t* h2, int rows_total, act_stream_t stream);
+int act_sgemm_nt_f16x3_planes_layout_f32(int M, int N, int K, const uint16_t* a_h1, const uint16_t* a_h2, int a_layout, int lda, int a_rows_total,
+                                         float a_scale, const uint16_t* b_h1, const uint16_t* b_h2, int b_layout, int b_rows_total,
+                                         const float* b_inv_scale, float* C, int ldc, uint16_t* out_h1, uint16_t* out_h2, float out_scale,
+                                         int out_layout, const act_gemm_epilogue_t* epilogue, act_stream_t stream, int tile);
+/* ACT_X3_KT (environment, read once; default 1) / act_x3_kt: whether the callers that build the planes of frozen weights (act_amd/composite.py) keep them
+ * K-tile-major, and the composites hand activations on that way; 0 is the row-major step. */
+int act_x3_kt(int on /* < 0: query */);                 /* -> previous setting */
 /* the plane producers in this format: bit-identical to producing fp32 and splitting it with act_split_f16x2_f32 at plane_scale */
 int act_layernorm_fwd_f16_planes_f32(const float* x, const float* pos, const float* gamma, const float* beta, float* xin_out, float* y,
                                      uint16_t* y_h1, uint16_t* y_h2, float plane_scale, float* mean /* nullable */, float* rstd /* nullable */, int T, int D,
@@ -469,6 +488,10 @@ int act_sgemm_nt_f16x3_gmax_pick_tile(int M, int N, int K, int cus);
 int act_sgemm_nt_f16x3_gmax_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift, const uint16_t* a_h1,
                                 const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2, const float* b_inv_scale,
                                 const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream);
+/* the same with the layout of B's planes given (ACT_X3_ROWMAJOR: the entry above; ACT_X3_KTILE and b_rows_total as in act_sgemm_nt_f16x3_planes_layout_f32) */
+int act_sgemm_nt_f16x3_gmax_layout_f32(int M, int N, int K, const float* A, int lda, const float* a_col_scale, const float* a_col_shift, const uint16_t* a_h1,
+                                       const uint16_t* a_h2, float a_scale, const uint16_t* b_h1, const uint16_t* b_h2, int b_layout, int b_rows_total,
+                                       const float* b_inv_scale, const float* bias, int group, float* out, int ldo, int tile, act_stream_t stream);
 
 /* ---- GEMM launch-configuration table (host side) ------------------------------------------------------------------------
  * act_sgemm_f32 (no explicit configuration) first consults this table keyed by (a_kmajor, b_kmajor, M, N, K), then its built-in
@@ -596,6 +619,12 @@ int act_prompt_kv_f16x3(int on /* < 0: query */);       /* -> previous setting *
 int act_prompt_kv_fwd_f16x3_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
                                 const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, const float* w_inv,
                                 float a_scale, const float* bias, float* kv, uint16_t* planes, size_t planes_elems, int tile, act_stream_t stream);
+/* the same with the layout of the weight planes given: ACT_X3_KTILE, w_rows_total as the B operand of act_sgemm_nt_f16x3_planes_layout_f32 (the K,V rows of
+ * a K-tile-major qkv weight: pointers 32 D elements behind the planes, w_rows_total = 3 D) */
+int act_prompt_kv_fwd_f16x3_layout_f32(const float* tok, const float* ppos, int B, int P, int D, int N, float drop_p, uint64_t seed, const uint64_t* seed_dev,
+                                       const float* gamma, const float* beta, float eps, const uint16_t* w_h1, const uint16_t* w_h2, int w_layout,
+                                       int w_rows_total, const float* w_inv, float a_scale, const float* bias, float* kv, uint16_t* planes,
+                                       size_t planes_elems, int tile, act_stream_t stream);
 size_t act_prefix_block_bwd_scratch_floats(const act_block_dims_t* d, int P);
 int act_prefix_block_bwd_f32(const act_block_dims_t* d, int P, const act_block_params_t* w, const float* prm, const float* saved,
                              const float* dout, float* dx, float* dprm, float* scratch, float* workspace, size_t workspace_bytes,
@@ -651,6 +680,8 @@ typedef struct {
     const float* a_scale;                     /* [4 * depth], host memory */
     uint16_t* a_planes;
     size_t a_planes_elems;
+    int w_layout;                             /* bit j (0..3: qkv, proj, fc1, fc2) set: the planes of that weight, in every block, are K-tile-major
+                                               * (act_repack_ktile_u16 of each plane); 0: all row-major.  Any other bit is ACT_E_BADARG */
 } act_vit_f16x3_t;
 int act_prefix_vit_fwd_f16x3_f32(const act_prefix_vit_t* m, const act_vit_f16x3_t* x3, const float* tokens, const float* center, float* out,
                                  float* scratch, float* workspace, size_t workspace_bytes, act_stream_t stream);
@@ -686,6 +717,7 @@ typedef struct {
     const uint16_t* c4_planes;
     const float* c4_inv_scale;
     float a_scale;
+    int w_layout;                             /* ACT_X3_ROWMAJOR (0) | ACT_X3_KTILE: both planes of c4_w K-tile-major */
 } act_pointnet_f16x3_t;
 int act_pointnet_fwd_groups_f16x3_f32(const act_pointnet_dims_t* d, const act_pointnet_params_t* w, const act_pointnet_f16x3_t* x3, const float* x,
                                       int training, int keep_for_backward, float* saved, float* out, const int32_t* groups, int n_groups,
@@ -730,6 +762,7 @@ typedef struct {
     int layers;
     const uint16_t* st_planes[3];
     const float* st_inv_scale[3];
+    int w_layout;                             /* ACT_X3_ROWMAJOR (0) | ACT_X3_KTILE: the planes of w5 and of every stacked matrix K-tile-major */
 } act_dgcnn_f16x3_t;
 int act_dgcnn_features_f16x3_f32(const act_dgcnn_t* m, const act_dgcnn_f16x3_t* x3, const float* f, const int64_t* idx, float* h, float* scratch,
                                  float* workspace, size_t workspace_bytes, act_stream_t stream);
