@@ -222,8 +222,9 @@ __global__ __launch_bounds__(256) void colsum_stage2(const float* __restrict__ p
     }
 }
 
-// cosine distillation loss: rows [R,D] ; loss = mean_r (1 - cos(s_r, t_r)), cos with torch's eps semantics
-// (x.y / max(|x|*|y|, eps)).  Stores per-row dot/norms for the backward.
+// cosine distillation loss: rows [R,D] ; loss = mean_r (1 - cos(s_r, t_r)), cos with the eps semantics of F.cosine_similarity: each norm is
+// clamped on its own, x.y / (max(|x|, eps) * max(|y|, eps)).  Neither ss * tt nor a power of a norm is formed: both leave float32 long before
+// the norms do.  Stores per-row dot / squared norms for the backward.
 __global__ __launch_bounds__(256) void cosine_fwd_kernel(const float* __restrict__ s, const float* __restrict__ t, int R, int D,
                                                          float eps, float* __restrict__ row_loss, float* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
@@ -235,13 +236,15 @@ __global__ __launch_bounds__(256) void cosine_fwd_kernel(const float* __restrict
         dot += a * b; ss += a * a; tt += b * b;
     }
     dot = wave_sum_f32(dot); ss = wave_sum_f32(ss); tt = wave_sum_f32(tt);
-    const float denom = fmaxf(sqrtf(ss * tt), eps);
+    const float ns = fmaxf(sqrtf(ss), eps), nt = fmaxf(sqrtf(tt), eps);
     if (lane == 0) {
-        row_loss[row] = 1.0f - dot / denom;
+        row_loss[row] = 1.0f - dot / (ns * nt);
         stats[row * 3 + 0] = dot; stats[row * 3 + 1] = ss; stats[row * 3 + 2] = tt;
     }
 }
-// d loss / d s_r = -gscale * ( t/denom - dot * s * tt / denom^3 )   (denom = sqrt(ss*tt), clamped region has zero 2nd term)
+// d loss / d s_r = -gscale * ( t / (ns nt) - cos * s / (ns |s|) )   (ns = max(|s|, eps), nt = max(|t|, eps), cos = dot / (ns nt)): autograd's
+// gradient of F.cosine_similarity, which clamps the norms in place under no_grad -- a clamped |s| still passes its gradient s / |s| on, 0 at
+// s = 0.  Where |s| > eps that is the derivative t / (|s| nt) - cos * s / ss; a zero student row gets -gscale * t / (eps nt).
 __global__ __launch_bounds__(256) void cosine_bwd_kernel(const float* __restrict__ s, const float* __restrict__ t,
                                                          const float* __restrict__ stats, const float* __restrict__ gout,
                                                          int R, int D, float eps, float inv_rows, float* __restrict__ ds) {
@@ -249,22 +252,23 @@ __global__ __launch_bounds__(256) void cosine_bwd_kernel(const float* __restrict
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= R) return;
     const float dot = stats[row * 3 + 0], ss = stats[row * 3 + 1], tt = stats[row * 3 + 2];
-    const float nrm = sqrtf(ss * tt);
+    const float ns = sqrtf(ss), nt = fmaxf(sqrtf(tt), eps);
     const float g = -gout[0] * inv_rows;
     float ca, cb;
-    if (nrm > eps) { ca = 1.0f / nrm; cb = dot * tt / (nrm * nrm * nrm); }
-    else { ca = 1.0f / eps; cb = 0.f; }
+    if (ns > eps) { ca = 1.0f / (ns * nt); cb = dot * ca / ss; }
+    else { ca = 1.0f / (eps * nt); cb = ns > 0.f ? dot * ca / (eps * ns) : 0.f; }
     for (int c = lane; c < D; c += 64) {
         const float a = s[(size_t)row * D + c], b = t[(size_t)row * D + c];
         ds[(size_t)row * D + c] = g * (b * ca - a * cb);
     }
 }
-// mean of a vector (deterministic, single block) -> out[0]
+// mean of a vector (deterministic, single block) -> out[0].  SIGNS: the mean of the elements' sign bits instead (the flags of xent_fwd_kernel)
+template <bool SIGNS>
 __global__ __launch_bounds__(1024) void mean_kernel(const float* __restrict__ v, int n, float* __restrict__ out) {
     __shared__ float sh[16];
     float acc = 0.f;
     const int per = (n + 1023) / 1024, k0 = threadIdx.x * per, k1 = min(n, k0 + per);
-    for (int k = k0; k < k1; ++k) acc += v[k];
+    for (int k = k0; k < k1; ++k) acc += SIGNS ? (float)(__float_as_uint(v[k]) >> 31) : v[k];
     acc = wave_sum_f32(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
@@ -513,7 +517,9 @@ extern "C" int act_colsum_f32(const float* in, int R, int C, int ld, float* out,
     ACT_LAUNCH_CHECK(); return 0;
 }
 
-// softmax cross-entropy (nn.CrossEntropyLoss, mean): one wave per row
+// softmax cross-entropy (nn.CrossEntropyLoss, mean): one wave per row.  row_buf [3,R] = {row maximum mx, row loss, ls = log sum exp(z - mx) with the sign bit
+// set where the arg-max is the label}.  mx and ls stay apart: their sum mx + ls is rounded to an ulp of the largest logit, which at logits of 1e4 moved
+// every probability of the backward by 4e-4 of itself; ls >= 0 (the maximum contributes exp(0)), so its sign bit is free for the flag.
 __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ lab, int R, int C,
                                                        float* __restrict__ row_buf) {
     const int lane = threadIdx.x & 63;
@@ -529,11 +535,11 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__
     for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
     se = wave_sum_f32(se);
     if (lane == 0) {
-        const float lse = mx + logf(se);
+        const float ls = logf(se);
         const int64_t l = lab[row];
-        row_buf[row] = lse;
-        row_buf[R + row] = lse - zr[l];
-        row_buf[2 * R + row] = (cand == (int)l) ? 1.0f : 0.0f;
+        row_buf[row] = mx;
+        row_buf[R + row] = ls - (zr[l] - mx);
+        row_buf[2 * R + row] = (cand == (int)l) ? -ls : ls;
     }
 }
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ lab,
@@ -542,7 +548,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)R * C) return;
     const int row = (int)(i / C), c = (int)(i % C);
-    const float p = expf(z[i] - row_buf[row]);
+    const float p = expf((z[i] - row_buf[row]) - fabsf(row_buf[2 * (size_t)R + row]));
     dz[i] = gout[0] * inv_rows * (p - ((int64_t)c == lab[row] ? 1.0f : 0.0f));
 }
 
@@ -553,8 +559,8 @@ extern "C" int act_softmax_xent_fwd_f32(const float* logits, const int64_t* labe
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_COSINE_FWD, s, 0.0, 4.0 * R * (double)C);
     hipLaunchKernelGGL(xent_fwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, labels, R, C, row_buf);
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(1024), 0, s, row_buf + R, R, loss_out);
-    if (acc_out) hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(1024), 0, s, row_buf + 2 * (size_t)R, R, acc_out);
+    hipLaunchKernelGGL(mean_kernel<false>, dim3(1), dim3(1024), 0, s, row_buf + R, R, loss_out);
+    if (acc_out) hipLaunchKernelGGL(mean_kernel<true>, dim3(1), dim3(1024), 0, s, row_buf + 2 * (size_t)R, R, acc_out);
     ACT_LAUNCH_CHECK(); return 0;
 }
 
@@ -601,7 +607,7 @@ extern "C" int act_regression_loss_fwd_f32(const float* student, const float* te
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_COSINE_FWD, s, 0.0, 8.0 * R * (double)D);
     hipLaunchKernelGGL(regression_loss_fwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, student, teacher, R, D, kind, row_loss);
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(1024), 0, s, row_loss, R, loss_out);
+    hipLaunchKernelGGL(mean_kernel<false>, dim3(1), dim3(1024), 0, s, row_loss, R, loss_out);
     ACT_LAUNCH_CHECK(); return 0;
 }
 extern "C" int act_regression_loss_bwd_f32(const float* student, const float* teacher, const float* grad_loss, int R, int D, int kind,
@@ -624,7 +630,7 @@ extern "C" int act_cosine_loss_fwd_f32(const float* student, const float* teache
     hipStream_t s = (hipStream_t)stream;
     ActProfScope ps(KID_COSINE_FWD, s, 0.0, 8.0 * R * (double)D);
     hipLaunchKernelGGL(cosine_fwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, student, teacher, R, D, eps, row_loss, stats);
-    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(1024), 0, s, row_loss, R, loss_out);
+    hipLaunchKernelGGL(mean_kernel<false>, dim3(1), dim3(1024), 0, s, row_loss, R, loss_out);
     ACT_LAUNCH_CHECK(); return 0;
 }
 

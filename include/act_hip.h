@@ -283,7 +283,8 @@ int act_attention_bwd_prefix_f32(const float* kv0, int S0, const float* qkv1, in
                                  act_stream_t stream);
 
 /* Cosine distillation loss (models/act.py:1243-1254; lightly NegativeCosineSimilarity(dim=1, eps=1e-8)):
- * loss = mean over rows of 1 - cos(student_r, teacher_r).  row_loss [R], stats [R,3] are scratch kept for backward. */
+ * loss = mean over rows of 1 - cos(student_r, teacher_r), cos = s.t / (max(|s|, eps) max(|t|, eps)) as F.cosine_similarity has it: every
+ * norm clamped on its own; backward is autograd's gradient of that.  row_loss [R], stats [R,3] are scratch kept for backward. */
 int act_cosine_loss_fwd_f32(const float* student, const float* teacher, int R, int D, float eps, float* loss_out,
                             float* row_loss, float* stats, act_stream_t stream);
 int act_cosine_loss_bwd_f32(const float* student, const float* teacher, const float* stats, const float* grad_loss,
@@ -298,8 +299,9 @@ int act_regression_loss_bwd_f32(const float* student, const float* teacher, cons
 
 /* Classification loss of the finetune path (models/act.py:823-830: nn.CrossEntropyLoss(), mean over rows):
  * logits [R,C], labels int64 [R] -> loss_out[0] = mean_r (logsumexp(logits_r) - logits_r[label_r]); row_buf [3,R] =
- * {logsumexp (kept for backward), row loss, arg-max==label flag}; acc_out (nullable) [1] = fraction of rows whose arg-max
- * (lowest index on ties) equals the label.
+ * {row maximum, row loss, log sum exp(logits_r - maximum) with the sign bit set where arg-max==label} (rows 0 and 2 are kept
+ * for backward: maximum and log-sum are never added, so logits of any size keep their probabilities); acc_out (nullable) [1] =
+ * fraction of rows whose arg-max (lowest index on ties) equals the label.
  * backward: grad_logits = grad_loss * (softmax(logits) - onehot(label)) / R. */
 int act_softmax_xent_fwd_f32(const float* logits, const int64_t* labels, int R, int C, float* loss_out, float* row_buf,
                              float* acc_out, act_stream_t stream);
